@@ -1,8 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — training ray-samples/sec of the MI355X NeRF hot path (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--rays-per-gpu R] [--graph] [--pmc]
+  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--rays-per-gpu R] [--graph] [--dump-outputs DIR]
+                  [--full [--pmc] [--no-extra] [--no-cpu-baseline]]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+
+A plain run sets up, runs W untimed and K timed steps, and prints the result line; `roofline` comes from HIP events recorded
+inside those K steps.  Everything that takes runs of its own — the legs under `extra`, `cpu_baseline`, the PMC passes, the
+eager pass that fills the kernel table of a --graph run — runs only with --full.
+  --dump-outputs DIR  after the timed steps: what the last step handed its caller — the loss, the maps of the render (rank 0's
+                   rays), both networks' parameters after the Adam update and the gradients it applied — as DIR/<name>.npy
+                   (float32 or float64), at most DUMP_LIMIT bytes in all (a larger array is a fixed seeded sample of its elements).  The
+                   inputs are seeded: the same arguments give the same inputs on every run.
 
 One "step" = one full optimisation step of BASELINE config C2 on synthetic DTU-like data, per GPU:
 R rays -> coarse 64 samples -> fine 64+128 samples (D=8/W=256 MLPs with view directions, stratified
@@ -23,7 +32,7 @@ resident in HBM before the timed region.
                    only, 3 steps each) and fills roofline.traffic from THOSE runs instead of the committed lookup.  Default auto: on at
                    N=1 when the extra legs run and rocprofv3 is on PATH (adds ~40 s); any failure falls back to the lookup.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (cpu_baseline and extra: --full only):
   roofline     — dominant kernel of the step, algorithmic FLOPs per launch / its average duration measured
                  with HIP events on the launch stream inside the timed region; peak = fp32 MFMA 157.3 TFLOP/s.
   cpu_baseline — the CPU oracle ("port" of the reference step: stock ATen, fp32) timed on this host's cores on
@@ -147,6 +156,35 @@ def write_detail(out, world):
         return path
     except OSError:
         return None
+
+
+DUMP_LIMIT = 64 << 20
+NPY_HEADER = 256           # bytes reserved per file for the .npy header (numpy writes 128 for the shapes written here)
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT, seed=0):
+    """{name: tensor} -> out_dir/<name>.npy, float64 kept, every other dtype as float32.  Smallest arrays first, each gets at most
+    an equal share of what `limit` has left; an array larger than its share is written as a sample of its flattened elements at
+    indices drawn from `seed` and its size alone (sorted, without repeats), so that two runs sample the same elements.
+    -> {name: elements written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    left, written = limit, {}
+    items = sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    for k, (name, t) in enumerate(items):
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        n, size = t.numel(), torch.finfo(dt).bits // 8
+        keep = min(n, max(0, left // (len(items) - k) - NPY_HEADER) // size)
+        flat = t.reshape(-1)
+        if keep < n:
+            idx = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(dt).cpu().numpy()
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a.reshape(t.shape) if keep == n else a)
+        left -= os.path.getsize(path)
+        written[name] = int(a.size)
+    return written
 
 
 def make_args(tmpdir):
@@ -938,6 +976,7 @@ class Workload:
         rays_od = (rays_o, rays_d)    # origins / directions of this batch: two contiguous [B, 3] row blocks of the pre-split bank
         extra_kw = {} if getattr(self, "global_rows", None) is None else {"_global_rows": self.global_rows}
         rgb, disp, acc, extras = R.render(H_IMG, W_IMG, self.K, chunk=32768, rays=rays_od, retraw=True, **self.kw, **extra_kw)
+        self.maps = dict(extras, rgb_map=rgb, disp_map=disp, acc_map=acc)
         self.opt.zero_grad()
         loss = R.img2mse(rgb, tgt) + R.img2mse(extras['rgb0'], tgt)
         loss.backward()
@@ -949,10 +988,23 @@ class Workload:
         run_nerf.backward (no ones_like fill): 14 launches per step instead of 20."""
         R = self.R
         extra_kw = {} if getattr(self, "global_rows", None) is None else {"_global_rows": self.global_rows}
-        loss = R.render_loss(H_IMG, W_IMG, self.K, tgt, chunk=32768, rays=(rays_o, rays_d), retraw=True, **self.kw, **extra_kw)[0]
+        loss, rgb, disp, acc, extras = R.render_loss(H_IMG, W_IMG, self.K, tgt, chunk=32768, rays=(rays_o, rays_d), retraw=True,
+                                                     **self.kw, **extra_kw)
+        self.maps = dict(extras, rgb_map=rgb, disp_map=disp, acc_map=acc)
         self.opt.zero_grad()
         R.backward(loss)
         return loss
+
+    def outputs(self, loss):
+        """What the last step handed its caller: `loss`, the maps of its render, and both networks' parameters after the Adam
+        update with the gradients that update applied (the maps are the captured graph's outputs when the step was replayed)."""
+        out = {"loss": loss}
+        out.update({k: v for k, v in self.maps.items() if torch.is_tensor(v) and v.is_floating_point()})
+        for tag, k_ in (("coarse", "network_fn"), ("fine", "network_fine")):
+            for name, p in self.kw[k_].named_parameters():
+                out[f"{tag}.{name}"] = p
+                out[f"{tag}.{name}.grad"] = p.grad
+        return out
 
     def body(self, rays_o, rays_d, tgt):
         loss = self.fwd_bwd(rays_o, rays_d, tgt)
@@ -1164,8 +1216,13 @@ def main():
                     help="render_loss: R:764-775 as one call (run_nerf.render_loss + run_nerf.backward, the loss folded into the "
                          "compositing launches); reference_lines: render() + img2mse() + img2mse() + loss.backward() as the "
                          "reference's loop writes them")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the legs that follow the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the legs after the timed region, the CPU baseline, the PMC "
+                         "passes (--pmc auto), the eager kernel-table pass of a --graph run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 or float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the legs that follow the timed region")
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as captured hipGraph(s) (consistentnerf_amd/graph.py); the per-kernel table then comes "
                          "from a separate eager pass of the same steps, and the JSON says so")
@@ -1175,6 +1232,9 @@ def main():
                          "rocprofv3 is on PATH; the committed lookup is the fallback)")
     ap.add_argument("--only-leg", choices=("c3", "c3_ss"), default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    extra_on, cpu_on = a.full and not a.no_extra, a.full and not a.no_cpu_baseline
     if a.only_leg:
         sys.stdout.flush()
         os.dup2(2, 1)
@@ -1231,31 +1291,34 @@ def main():
     wl.set_sharding(per_rank, strong=(per_rank * world == B_PER_GPU and world > 1))
     graphed = wl.graphed(per_rank, a.graph_collective) if a.graph else None
     elapsed, loss, prof = wl.run(per_rank, a.steps, a.warmup, graphed=graphed)
-    if graphed is not None:      # a replayed graph carries no events: the per-kernel table from an eager pass of the same steps
+    if a.dump_outputs and rank == 0:
+        dump_outputs(wl.outputs(loss), a.dump_outputs)
+    table = per_kernel_table(prof, elapsed * 1e3)      # empty after a replayed graph: it carries no events
+    if graphed is not None and a.full:      # the per-kernel table from an eager pass of the same steps
         el_e, _, prof = wl.run(per_rank, a.steps, 0, i0=a.warmup + a.steps)
         table = per_kernel_table(prof, el_e * 1e3)
-    else:
-        table = per_kernel_table(prof, elapsed * 1e3)
     final_loss = loss.item()
-    dom = table[0]
-    traffic, traffic_source = pmc_traffic(dom["kernel"], dom["points"]), (
-        "static lookup: committed rocprofv3 PMC passes of this kernel at this launch size (profiles/*_pmc*/pass2+pass3 "
-        "summaries, 2*FETCH_SIZE + WRITE_SIZE); NOT sampled in this run")
-    pmc_live = None
-    import shutil
-    want_pmc = a.pmc == "on" or (a.pmc == "auto" and not a.no_extra and shutil.which("rocprofv3") is not None)
-    if want_pmc and rank == 0 and world == 1:
-        pmc_live = pmc_rerun(per_rank, dom["kernel"])
-        if pmc_live and pmc_live.get("traffic") is not None:
-            traffic, traffic_source = pmc_live["traffic"], pmc_live["source"]
-    roofline = {"bound": "mfma", "kernel": f'{dom["kernel"]} (M={dom["points"]} points)', "achieved": dom["tflops"],
-                "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": round(dom["tflops"] / PEAK_FP32_MFMA_TFLOPS, 4),
-                "traffic": traffic, "traffic_source": traffic_source, "avg_launch_ms": dom["avg_ms"], "kernels": table}
-    launches_live = pmc_live.pop("launches", None) if pmc_live else None
-    if pmc_live:
-        roofline["pmc"] = pmc_live
-    if graphed is not None:
-        roofline["kernels_measured"] = "separate eager pass of the same steps after the timed (graph-replayed) region"
+    roofline = launches_live = None
+    if table:
+        dom = table[0]
+        traffic, traffic_source = pmc_traffic(dom["kernel"], dom["points"]), (
+            "static lookup: committed rocprofv3 PMC passes of this kernel at this launch size (profiles/*_pmc*/pass2+pass3 "
+            "summaries, 2*FETCH_SIZE + WRITE_SIZE); NOT sampled in this run")
+        pmc_live = None
+        import shutil
+        want_pmc = a.pmc == "on" or (a.pmc == "auto" and extra_on and shutil.which("rocprofv3") is not None)
+        if want_pmc and rank == 0 and world == 1:
+            pmc_live = pmc_rerun(per_rank, dom["kernel"])
+            if pmc_live and pmc_live.get("traffic") is not None:
+                traffic, traffic_source = pmc_live["traffic"], pmc_live["source"]
+        roofline = {"bound": "mfma", "kernel": f'{dom["kernel"]} (M={dom["points"]} points)', "achieved": dom["tflops"],
+                    "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": round(dom["tflops"] / PEAK_FP32_MFMA_TFLOPS, 4),
+                    "traffic": traffic, "traffic_source": traffic_source, "avg_launch_ms": dom["avg_ms"], "kernels": table}
+        launches_live = pmc_live.pop("launches", None) if pmc_live else None
+        if pmc_live:
+            roofline["pmc"] = pmc_live
+        if graphed is not None:
+            roofline["kernels_measured"] = "separate eager pass of the same steps after the timed (graph-replayed) region"
     dist_info = None
     if dist.is_initialized():
         ex = wl.reducer.exposed_ms()
@@ -1283,7 +1346,7 @@ def main():
             "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True,
             "scaling": "strong" if (a.scaling == "strong" and a.rays_per_gpu <= 0) else "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic", "hip_graph": graphed is not None,
-            "route": route_of(table, a.steps),
+            "route": route_of(table, a.steps) if table else None,
             "config": {"workload": f"DTU scan8 3-view (synthetic 512x640 ray bank), {per_rank} rays/GPU/step (global batch "
                                    f"{per_rank * world}), coarse 64 + fine 64+128 samples, D=8 W=256 viewdirs MLPs (random init), "
                                    f"perturb=1, mse(rgb)+mse(rgb0), backward, Adam; {cfgname}",
@@ -1312,7 +1375,7 @@ def main():
                 os.write(json_fd, (json.dumps(compact_line(out, path)) + "\n").encode())
 
     force_leg = os.environ.get("CNERF_BENCH_FORCE_LEG") == "1" and dist.is_initialized()     # (exercise the leg on a 1-rank group)
-    if not a.no_extra and (world > 1 or force_leg) and per_rank == B_PER_GPU and B_PER_GPU % world == 0:
+    if extra_on and (world > 1 or force_leg) and per_rank == B_PER_GPU and B_PER_GPU % world == 0:
         # the same process group on the strong-scaling shard of C4 — a SIDE experiment (eager / split-graph / RCCL recorded inside the
         # graph) that has never seen real multi-GPU hardware.  At world > 1 the contract line therefore goes out FIRST: nothing this
         # leg does (an exception, a collective that never completes, an abort inside the communicator) can void the measurement of
@@ -1355,7 +1418,7 @@ def main():
                 except OSError:
                     pass
     if rank == 0:
-        if world == 1 and not a.no_extra and not force_leg:
+        if world == 1 and extra_on and not force_leg:
             extra = {"note": "same process, after the timed C2 region; not part of `value`"}
             if per_rank == B_PER_GPU:
                 extra["c4_shard"] = shard_leg(wl, B_PER_GPU // 8, 200, 20)
@@ -1403,7 +1466,7 @@ def main():
             out["config"].update({k: (round(v, 4) if isinstance(v, float) else v) for k, v in flat.items()})
             out["roofline"]["whole_step_frac"] = round(
                 per_rank * (NC + NC + NF) * 2 * (MAC_FWD + MAC_DGRAD + MAC_WGRAD) / (elapsed / a.steps) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4)
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and cpu_on:
             out["cpu_baseline"] = cpu_baseline()
         emit()
     os.close(json_fd)

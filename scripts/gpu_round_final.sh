@@ -13,7 +13,7 @@ if [ "${SKIP_BF3:-0}" != "1" ]; then
   grep -E "passed|failed|rc=" $OUT/test_gpu_bf16x3.log | tail -2
   cp gpurun_out/teacher_forced_c2.json $OUT/teacher_forced_c2_bf16x3.json 2>/dev/null
 fi
-timeout 1200 python bench.py > $OUT/bench_line.json 2> $OUT/bench.err; echo "bench rc=$? line bytes=$(wc -c < $OUT/bench_line.json)"
+timeout 1200 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err; echo "bench rc=$? line bytes=$(wc -c < $OUT/bench_line.json)"
 cp gpurun_out/bench_detail.json $OUT/bench_detail.json
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o bench -- python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-extra --pmc off > gpurun_out/prof/bench_under_rocprof.log 2>&1; echo "rocprof rc=$?"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof512 -o bench512 -- python bench.py --rays-per-gpu 512 --steps 200 --warmup 20 --no-cpu-baseline --no-extra --pmc off > gpurun_out/prof512/bench_under_rocprof.log 2>&1; echo "rocprof512 rc=$?"

@@ -50,14 +50,15 @@ def test_masked_psnr_and_metrics_file(tmp_path):
     assert open(p).read() == "PSNR: 23.5\nSSIM: 0.81\nLPIPS: 0.2"
 
 
-def test_pairs_split_lists():
+def test_pairs_split_lists(tmp_path):
     g = golden("pairs")
-    ref = "/root/reference/nerf-pytorch-master/configs/pairs.th"
-    if os.path.exists(ref):            # present in the build container only; the decoded lists are the committed fixture
-        d = F.load_pairs(ref)
-        assert set(d) == set(g.keys())
-        for k in d:
-            assert np.array_equal(d[k], g[k])
+    # configs/pairs.th is torch.save() of {split name: int64 ndarray}: the same archive rebuilt from the decoded fixture
+    p = os.path.join(tmp_path, "pairs.th")
+    torch.save({k: g[k] for k in g}, p)
+    d = F.load_pairs(p)
+    assert set(d) == set(g.keys())
+    for k in d:
+        assert d[k].dtype == np.int64 and np.array_equal(d[k], g[k])
     assert any(k.endswith("_train") for k in g.keys())
 
 

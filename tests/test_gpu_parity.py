@@ -3062,8 +3062,8 @@ def test_bench_gpus_2_launched_plainly_is_its_own_launcher(dev):
 
 
 def test_bench_default_line_is_small_and_complete(dev, tmp_path):
-    """VERDICT r05 item 1 on the REAL line: `python bench.py --steps 3 --warmup 1` (every leg, the PMC passes, the CPU baseline —
-    the shape of the driver's N = 1 command) prints exactly one stdout line of at most bench.LINE_LIMIT (< 6 KB) bytes that carries
+    """VERDICT r05 item 1 on the REAL line: `python bench.py --full --steps 3 --warmup 1` (every leg, the PMC passes, the CPU
+    baseline) prints exactly one stdout line of at most bench.LINE_LIMIT (< 6 KB) bytes that carries
     the contract keys, `roofline` (bound, achieved, peak, frac, traffic, the kernel table, whole_step_frac), `cpu_baseline` and the
     flat leg_* scalars; the legs' detail is in the side file the line names."""
     import json
@@ -3073,8 +3073,8 @@ def test_bench_default_line_is_small_and_complete(dev, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
                                                             "CNERF_FORCE_DIST", "CNERF_DIST_BACKEND")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1"], capture_output=True, text=True,
-                       env=env, timeout=1500, cwd=str(tmp_path))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1"], capture_output=True,
+                       text=True, env=env, timeout=1500, cwd=str(tmp_path))
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, [ln[:200] for ln in lines], r.stderr[-3000:])
     assert len(lines[0].encode()) <= bench.LINE_LIMIT < 6144, len(lines[0])
@@ -3096,8 +3096,47 @@ def test_bench_default_line_is_small_and_complete(dev, tmp_path):
     assert detail["value"] == o["value"] and "hbm_kernels" in detail["extra"] and "c3_ss" in detail["extra"]
 
 
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(dev, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` runs the timed steps and nothing else: one line with the contract scalars and
+    the roofline of those steps, no legs, no CPU baseline, no PMC pass.  --dump-outputs writes what the last step returned.  The
+    same 4 steps split 1 + 3 and 2 + 2 between warm-up and timing end on the same step, from seeded inputs: equal dumps."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
+                                                            "CNERF_FORCE_DIST", "CNERF_DIST_BACKEND")}
+    dumps = []
+    for warm, steps in ((1, 3), (2, 2)):
+        d = tmp_path / f"out_w{warm}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warm),
+                            "--dump-outputs", str(d)], capture_output=True, text=True, env=env, timeout=600, cwd=str(tmp_path))
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert r.returncode == 0 and len(lines) == 1, (r.returncode, [ln[:200] for ln in lines], r.stderr[-3000:])
+        o = json.loads(lines[0])
+        assert o["metric"] == "train_ray_samples_per_sec" and o["unit"] == "ray-samples/s" and o["higher_is_better"] is True
+        assert o["dtype"] == "f32" and o["steps"] == steps and o["warmup"] == warm and o["ms_per_step"] > 0
+        assert abs(o["value"] - 4096 * 256 / (o["ms_per_step"] * 1e-3)) <= 1e-6 * o["value"]
+        assert "cpu_baseline" not in o and "extra" not in o and not any(k.startswith("leg_") for k in o["config"])
+        assert o["roofline"]["bound"] == "mfma" and "pmc" not in o["roofline"]
+        names = os.listdir(d)
+        assert sum(os.path.getsize(d / f) for f in names) <= bench.DUMP_LIMIT
+        arrays = {f[:-4]: np.load(d / f) for f in names}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert abs(float(arrays["loss"]) - o["config"]["final_loss"]) <= 1e-5 * abs(o["config"]["final_loss"])
+        dumps.append(arrays)
+    a, b = dumps
+    assert set(a) == set(b)
+    assert a["rgb_map"].shape == (4096, 3) and a["rgb0"].shape == (4096, 3) and a["fine.pts_linears.3.weight"].shape == (256, 256)
+    assert np.abs(a["fine.pts_linears.3.weight.grad"]).max() > 0 and np.isfinite(a["loss"])
+    # (NaN is a value here: disp0 = 1 / max(1e-10, depth0 / acc0) is 0 / 0 on rays the coarse level leaves empty, as in the reference)
+    differ = [k for k in a if not np.array_equal(a[k], b[k], equal_nan=True)]
+    assert not differ, {k: float(np.nanmax(np.abs(a[k] - b[k]))) for k in differ}
+
+
 def test_bench_gpus_2_default_legs_line_first_then_the_side_leg(dev):
-    """The shape of the driver's N > 1 command — no --no-extra: at world > 1 the contract line is printed BEFORE the C4 strong-shard
+    """`--full` at N > 1, no --no-extra: at world > 1 the contract line is printed BEFORE the C4 strong-shard
     side leg runs (nothing that leg does can void the scaling measurement), stdout still carries exactly one line, the leg's result
     follows on stderr as its own JSON object, and the exit status is the main leg's.  Two ranks over gloo on the one GPU."""
     import json
@@ -3107,7 +3146,7 @@ def test_bench_gpus_2_default_legs_line_first_then_the_side_leg(dev):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
                                                             "CNERF_FORCE_DIST")}
     env.update(CNERF_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4", CNERF_BENCH_LEG_TIMEOUT="600")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1"],
                        capture_output=True, text=True, env=env, timeout=1200)
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, lines, r.stderr[-3000:])

@@ -709,3 +709,26 @@ def test_bench_line_stays_under_the_limit_in_the_worst_case():
     assert len(json.dumps(l2)) <= bench.LINE_LIMIT
     # and a degenerate object (an error line) still comes out
     assert bench.compact_line({"metric": "m", "value": None, "error": "boom"})["error"] == "boom"
+
+
+def test_bench_dump_outputs_stays_within_its_limit_with_a_fixed_sample(tmp_path):
+    """bench.dump_outputs (--dump-outputs): arrays that fit are written whole, float64 kept and other dtypes as float32; a larger one
+    becomes a sorted sample of its flattened elements drawn from the seed and its size only, so two dumps sample alike; the files
+    together never exceed the limit."""
+    import bench
+    big = torch.arange(3_000_000, dtype=torch.float32).reshape(1000, 3000)
+    arrays = {"loss": torch.tensor(1.5), "small": torch.randn(10, 3), "f64": torch.randn(5, dtype=torch.float64),
+              "half": torch.randn(4).half(), "big": big}
+    limit = 4 << 20
+    written = bench.dump_outputs(arrays, str(tmp_path / "a"), limit=limit)
+    bench.dump_outputs(dict(arrays, big=big + 1), str(tmp_path / "b"), limit=limit)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in arrays)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= limit
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert got["loss"].shape == () and got["loss"] == 1.5 and got["loss"].dtype == np.float32
+    assert np.array_equal(got["small"], arrays["small"].numpy()) and got["f64"].dtype == np.float64
+    assert got["half"].dtype == np.float32 and np.array_equal(got["half"], arrays["half"].float().numpy())
+    s = got["big"]
+    assert s.ndim == 1 and 0.3e6 < s.size == written["big"] < 3e6 and np.all(np.diff(s) > 0) and float(s.max()) < 3e6
+    assert np.array_equal(np.load(tmp_path / "b" / "big.npy"), s + 1)
