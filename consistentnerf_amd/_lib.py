@@ -164,6 +164,15 @@ SIGNATURES = {
     "cnerf_loss_ws_floats": (_i64, []),
     "cnerf_masked_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "cnerf_patch_depth_loss": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
+    "cnerf_closs_finish_ssim": (_i, [C.POINTER(ClossTail), _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cnerf_composite_bwd_closs_ssim": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i64, _i, _i, _ClossP, _vp, _vp, _vp, _vp, _f, _f, _f, _vp,
+                                            _i64, _f, _vp, _i64, _vp, _vp]),
+    "cnerf_ssim_ws_floats": (_i64, [_i64, _i64, _i64, _i64, _i]),
+    "cnerf_ssim_fwd": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    "cnerf_ssim_bwd_ws_floats": (_i64, [_i64, _i64, _i64, _i64, _i]),
+    "cnerf_ssim_bwd": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "cnerf_avg_pool2": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "cnerf_patch_ssim_loss": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "cnerf_adam_hyper": (_i, [_i, C.c_double, C.c_double, C.c_double, C.c_double, _f, _f, _vp]),
     "cnerf_adam_step_dev": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "cnerf_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _i, C.c_double, C.c_double, C.c_double, C.c_double, _f, _f, _vp]),

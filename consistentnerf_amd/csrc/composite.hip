@@ -60,6 +60,9 @@ struct ClossBwd {
   const float* patch_d;  // [n_patch] d patch_loss / d depth of this level, or nullptr
   int64_t n_patch;
   float far, rgb_w, depth_w, patch_w;
+  const float* ssim_d;   // [n_ssim * 3] d ssim_level / d rgb of this level (cnerf_closs_finish_ssim), or nullptr
+  int64_t n_ssim;
+  float ssim_w;
 };
 
 struct Sample {
@@ -354,6 +357,13 @@ __global__ __launch_bounds__(WAVES * 64) void composite_bwd_k(const float* __res
       gd += dd * (cl.depth_w * g0);
     }
     if (cl.patch_d && b < cl.n_patch) gd += cl.patch_d[b] * (cl.patch_w * g0);
+    if (cl.ssim_d) {   // loss -= ssim_w ssim_level: autograd's `d * ((-g) * ssim_w)`, zero past the patch rays (the padded gradient)
+      const float gs = (-g0) * cl.ssim_w;
+      const bool in = b < cl.n_ssim;
+      gr += in ? cl.ssim_d[b * 3 + 0] * gs : 0.f;
+      gg += in ? cl.ssim_d[b * 3 + 1] * gs : 0.f;
+      gb += in ? cl.ssim_d[b * 3 + 2] * gs : 0.f;
+    }
   }
   if (g_acc) ga = g_acc[b];
   if (white) ga -= (gr + gg + gb);
@@ -533,14 +543,16 @@ extern "C" int cnerf_composite_fwd_closs(const float* raw, int raw_ch, const flo
   });
 }
 
-extern "C" int cnerf_composite_bwd_closs(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
-                                         const float* noise, int64_t B, int S, int white_bkgd, const cnerf_closs* L, const float* rgb,
-                                         const float* depth, const float* stats, const float* g_loss, float rgb_w, float depth_w,
-                                         float patch_w, const float* patch_d, int64_t n_patch_rays, float* d_raw, void* stream) {
+namespace {
+int composite_bwd_closs_impl(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride, const float* noise,
+                             int64_t B, int S, int white_bkgd, const cnerf_closs* L, const float* rgb, const float* depth,
+                             const float* stats, const float* g_loss, float rgb_w, float depth_w, float patch_w, const float* patch_d,
+                             int64_t n_patch_rays, float ssim_w, const float* ssim_d, int64_t n_ssim_rays, float* d_raw, void* stream) {
   if (!raw || !z || !rays || !L || !L->target || !rgb || !stats || !d_raw || B <= 0 || S <= 0 || raw_ch < 4 || ray_stride < 6 ||
-      (L->prior && (!depth || !(L->far > 0.f))) || n_patch_rays < 0 || n_patch_rays > B)
+      (L->prior && (!depth || !(L->far > 0.f))) || n_patch_rays < 0 || n_patch_rays > B || n_ssim_rays < 0 || n_ssim_rays > B)
     return CNERF_E_ARG;
   ClossBwd c;
+  c.ssim_d = n_ssim_rays > 0 ? ssim_d : nullptr; c.n_ssim = n_ssim_rays; c.ssim_w = ssim_w;
   c.rgb = rgb; c.depth = depth; c.tgt = L->target; c.mask = L->mask; c.prior = L->prior; c.stats = stats; c.g = g_loss;
   c.seg_row = L->seg_row > 0 && L->seg_row < B ? L->seg_row : 0;
   c.patch_d = n_patch_rays > 0 ? patch_d : nullptr; c.n_patch = n_patch_rays; c.far = L->far; c.rgb_w = rgb_w; c.depth_w = depth_w;
@@ -553,4 +565,23 @@ extern "C" int cnerf_composite_bwd_closs(const float* raw, int raw_ch, const flo
     CN_CHECK_LAUNCH();
     return CNERF_OK;
   });
+}
+}  // namespace
+
+extern "C" int cnerf_composite_bwd_closs(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
+                                         const float* noise, int64_t B, int S, int white_bkgd, const cnerf_closs* L, const float* rgb,
+                                         const float* depth, const float* stats, const float* g_loss, float rgb_w, float depth_w,
+                                         float patch_w, const float* patch_d, int64_t n_patch_rays, float* d_raw, void* stream) {
+  return composite_bwd_closs_impl(raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, L, rgb, depth, stats, g_loss, rgb_w,
+                                  depth_w, patch_w, patch_d, n_patch_rays, 0.f, nullptr, 0, d_raw, stream);
+}
+
+extern "C" int cnerf_composite_bwd_closs_ssim(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
+                                              const float* noise, int64_t B, int S, int white_bkgd, const cnerf_closs* L, const float* rgb,
+                                              const float* depth, const float* stats, const float* g_loss, float rgb_w, float depth_w,
+                                              float patch_w, const float* patch_d, int64_t n_patch_rays, float ssim_w, const float* ssim_d,
+                                              int64_t n_ssim_rays, float* d_raw, void* stream) {
+  if (!ssim_d || n_ssim_rays <= 0) return CNERF_E_ARG;
+  return composite_bwd_closs_impl(raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, L, rgb, depth, stats, g_loss, rgb_w,
+                                  depth_w, patch_w, patch_d, n_patch_rays, ssim_w, ssim_d, n_ssim_rays, d_raw, stream);
 }

@@ -2,6 +2,7 @@
 // vanilla MSE (R:769), forward value + gradient seeds for the compositing backward in one launch.
 // Replaces 4 boolean-index gathers (each a host sync) per level.  One workgroup, fixed reduction order.
 #include "common.hpp"
+#include "ssim.hpp"
 
 namespace {
 
@@ -197,6 +198,13 @@ struct ClossTail {
   int coin[4];               // rgb, depth, rgb0, depth0: 1 = the term over the selected rays (mask == 1), 0 = the reference's other branch
   int nparts1;               // ss == 2: workgroups of the first segment
   const float* counts3;      // ss == 2: GLOBAL (selected primary rays, primary rays, warped rays) of a batch sharded over ranks, or nullptr
+  // V's patch SSIM term (cnerf_closs_finish_ssim; sP = 0: none): waves [0, sP) the last level, [sP, 2 sP) the coarse one, after the
+  // depth patch term; terms[8 + level] = ssim_level = (sum_p ssim_p) / 4, loss -= ssim_w ssim_level after the level's patch term
+  int sP;
+  float ssim_w;
+  const float* rgb[2];       // colour maps of the levels [B, 3]
+  const float* tgt;          // [B, 3]
+  float* ssim_d[2];          // [sP * 768] d ssim_level / d rgb per level, or nullptr
 };
 
 __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
@@ -217,6 +225,14 @@ __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
     const float share = patch_wave(a.depth[lv] + (int64_t)p * a.n, a.mono + (int64_t)p * a.n, a.P, a.n, 1.f,
                                    a.patch_d[lv] ? a.patch_d[lv] + (int64_t)p * a.n : nullptr, lane);
     if (lane == 0) pshare[lv][p] = share;
+  }
+  __shared__ float sshare[2][8];
+  if (a.sP > 0 && wv < levels * a.sP) {
+    const int lv = wv / a.sP, p = wv - lv * a.sP;
+    const int64_t off = (int64_t)p * CN_PATCH_SSIM_RAYS * 3;
+    const float share = cn_patch_ssim_wave(a.rgb[lv] + off, a.tgt + off, CN_PATCH_SSIM_SCALE, a.ssim_d[lv] ? a.ssim_d[lv] + off : nullptr,
+                                           lane);
+    if (lane == 0) sshare[lv][p] = share;
   }
   if (a.ss == 2) {
     // The one-render form of the whole `--ss_loss` step (VT:899-969): rays [0, 8 nparts1) are the primary batch (mask = sel, prior =
@@ -343,6 +359,13 @@ __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
     for (int k = 0; k < a.P; ++k) pl += pshare[lv][k];
     loss += a.rgb_w * il;
     if (a.P > 0) loss += a.patch_w * pl;
+    if (a.sP > 0) {
+      float sl = 0.f;
+      for (int k = 0; k < a.sP; ++k) sl += sshare[lv][k];
+      sl = sl / 4.f;
+      loss = loss - a.ssim_w * sl;
+      a.terms[8 + lv] = sl;
+    }
     if (a.has_depth) loss = loss + a.depth_w * dl;
     a.terms[1 + 3 * lv] = il; a.terms[2 + 3 * lv] = dl; a.terms[3 + 3 * lv] = pl;
     a.stats[4 * lv + 0] = (float)(2.0 / (3.0 * N1));
@@ -351,6 +374,7 @@ __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
     a.stats[4 * lv + 3] = 0.f;
   }
   if (levels == 1) { a.terms[4] = a.terms[5] = a.terms[6] = 0.f; }
+  if (a.sP > 0 && levels == 1) a.terms[9] = 0.f;
   a.terms[0] = loss;
   a.terms[7] = 0.f;
 }
@@ -564,8 +588,17 @@ extern "C" int cnerf_patch_depth_loss(const float* depth_pred, const float* mono
 }
 
 namespace {
+struct ClossSsim {            // cnerf_closs_finish_ssim's additions (sP = 0: none)
+  int sP = 0;
+  float ssim_w = 0.f;
+  const float* rgb_last = nullptr;
+  const float* rgb_coarse = nullptr;
+  const float* target = nullptr;
+  float* ssim_d = nullptr;
+};
+
 int closs_finish_impl(const cnerf_closs_sum* t, const int32_t* ss_coins, float* terms, float* stats, float* patch_d, void* stream,
-                      int64_t seg_row = 0, const float* counts3 = nullptr) {
+                      int64_t seg_row = 0, const float* counts3 = nullptr, const ClossSsim& sm = ClossSsim()) {
   if (!t || !terms || !stats || !t->ws_last || t->B <= 0 || t->P < 0 || t->P > 8 || (t->P > 0 && (t->n <= 0 || !t->mono || !t->depth_last)) ||
       (t->P > 0 && t->ws_coarse && !t->depth_coarse) || (t->has_depth && !(t->far > 0.f)) || (int64_t)t->P * t->n > t->B ||
       ((uintptr_t)t->ws_last & 7) != 0 || ((uintptr_t)t->ws_coarse & 7) != 0)
@@ -584,6 +617,9 @@ int closs_finish_impl(const cnerf_closs_sum* t, const int32_t* ss_coins, float* 
   for (int k = 0; k < 4; ++k) a.coin[k] = ss_coins ? (ss_coins[k] != 0) : 0;
   a.nparts1 = (int)(seg_row / CN_CLOSS_RAYS_PER_WG);
   a.counts3 = counts3;
+  a.sP = sm.sP; a.ssim_w = sm.ssim_w; a.rgb[0] = sm.rgb_last; a.rgb[1] = t->ws_coarse ? sm.rgb_coarse : nullptr; a.tgt = sm.target;
+  a.ssim_d[0] = sm.ssim_d;
+  a.ssim_d[1] = (sm.ssim_d && t->ws_coarse) ? sm.ssim_d + (int64_t)sm.sP * CN_PATCH_SSIM_RAYS * 3 : nullptr;
   hipLaunchKernelGGL(closs_tail_k, dim3(1), dim3(T), 0, cn_stream(stream), a);
   CN_CHECK_LAUNCH();
   return CNERF_OK;
@@ -606,4 +642,15 @@ extern "C" int cnerf_closs_finish_ss2(const cnerf_closs_sum* t, const int32_t* c
   // 8 rays of a compositing workgroup, so that every partial belongs to one segment)
   if (!coins4 || !t || t->P != 0 || t->counts || seg_row <= 0 || seg_row >= t->B || seg_row % CN_CLOSS_RAYS_PER_WG != 0) return CNERF_E_ARG;
   return closs_finish_impl(t, coins4, terms12, stats16, nullptr, stream, seg_row, counts3);
+}
+
+extern "C" int cnerf_closs_finish_ssim(const cnerf_closs_sum* t, int ssim_P, float ssim_w, const float* rgb_last, const float* rgb_coarse,
+                                       const float* target, float* terms10, float* stats, float* patch_d, float* ssim_d, void* stream) {
+  // V's patch SSIM term next to the depth patch term: ssim_P patches of 16 x 16 rays = the batch's first ssim_P * 256 rays
+  if (!t || !rgb_last || !target || !terms10 || ssim_P <= 0 || ssim_P > 8 || t->B <= 0 ||
+      (int64_t)ssim_P * CN_PATCH_SSIM_RAYS > t->B || (t->ws_coarse && !rgb_coarse))
+    return CNERF_E_ARG;
+  ClossSsim sm;
+  sm.sP = ssim_P; sm.ssim_w = ssim_w; sm.rgb_last = rgb_last; sm.rgb_coarse = rgb_coarse; sm.target = target; sm.ssim_d = ssim_d;
+  return closs_finish_impl(t, nullptr, terms10, stats, patch_d, stream, 0, nullptr, sm);
 }

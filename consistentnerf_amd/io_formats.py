@@ -4,6 +4,7 @@
   read_cam_file             load_dtu.py:120-132: DTU `*_cam.txt` -> (intrinsics 3x3, extrinsics 4x4, [depth_min, depth_max])
   load_pairs                configs/pairs.th split lists (a torch zip archive holding a plain pickle of numpy arrays)
   img2psnr_mask             alky/vis_utils.py:24-42: mean over images of the PSNR of the foreground-masked MSE
+  img2ssim                  alky/vis_utils.py:44-53: (SSIM, MS-SSIM) of [N, H, W, 3] images, optionally masked (the HIP kernels, ssim.py)
   write_metrics             V:2078-2087: metrics.txt
   llff_poses                load_llff.py: `poses_bounds.npy` -> poses / bounds / 60-pose spiral render path / hold-out view
   pose_spherical, read_transforms   load_blender.py:30-35, 38-70, 212-214: Blender camera ring and `transforms_*.json`
@@ -86,6 +87,23 @@ def img2psnr_mask(x, y, mask):
     mses = (mses * mask).reshape(n, -1).sum(-1) / mask.reshape(n, -1).sum(-1)
     ten = torch.tensor([10.], device=mses.device)
     return torch.stack([-10. * torch.log(m) / torch.log(ten) for m in mses]).mean()
+
+
+def img2ssim(x, y, mask=None):
+    """alky/vis_utils.py:44-53 (V:2053, V:2070): x, y [N, H, W, 3] images in [0, 1] (numpy arrays or tensors), mask [N, H, W] or
+    None -> (ssim, ms_ssim) as 0-d tensors, data_range 1, on the GPU in fp32 (the reference's default tensor type is CUDA float)."""
+    from .ssim import ms_ssim, ssim
+    dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+    if dev is None:
+        raise RuntimeError("img2ssim: needs a GPU (consistentnerf_amd has no CPU path)")
+    t = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32)  # noqa: E731
+    x, y = t(x), t(y)
+    if mask is not None:
+        m = t(mask).unsqueeze(-1)
+        x, y = m * x, m * y
+    x, y = x.permute(0, 3, 1, 2).contiguous(), y.permute(0, 3, 1, 2).contiguous()
+    with torch.no_grad():
+        return ssim(x, y, data_range=1), ms_ssim(x, y, data_range=1)
 
 
 def write_metrics(path, psnr, ssim, lpips):

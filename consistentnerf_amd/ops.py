@@ -636,6 +636,8 @@ class ClossSpec:
     ss_coins: Optional[tuple] = None      # (rgb, depth, rgb0, depth0) draws of VT:941-969: the in-loop consistency step's primary terms
     seg_row: int = 0                      # > 0 (with ss_coins): the batch is [primary rays | warped rays + padding] cut here (ss_batch)
     counts3: Optional[Tensor] = None      # (with seg_row) GLOBAL (selected, primary, warped) ray counts of a batch sharded over ranks
+    ssim_w: float = 0.0                   # V's patch SSIM term (loss -= ssim_w ssim_level per level; 0 = none) over the first
+    ssim_P: int = 0                       # ssim_P patches of 16 x 16 rays (cnerf_closs_finish_ssim)
 
     def c(self) -> Closs:
         return Closs(self.target.data_ptr(), None if self.mask is None else self.mask.data_ptr(),
@@ -660,8 +662,13 @@ class ClossSpec:
         seg = int(self.seg_row)
         if seg and (coins is None or seg % 8 != 0 or not 0 < seg < B):
             raise CnerfError(f"closs: seg_row {seg} needs ss_coins, a multiple of 8 and 0 < seg_row < B = {B}")
+        sP = int(self.ssim_P) if float(self.ssim_w) != 0.0 else 0
+        if sP > 0 and (sP > 8 or sP * PATCH_SSIM_RAYS > B or coins is not None):
+            raise CnerfError(f"closs: the patch SSIM term needs ssim_P <= 8 patches of {PATCH_SSIM_RAYS} rays inside the batch and no "
+                             f"ss_coins (ssim_P={sP}, B={B})")
         return ClossSpec(t, m, pr, float(self.far), float(self.coef), float(self.rgb_w), float(self.depth_w), float(self.patch_w),
-                         mono, P, int(self.n), _chk(self.counts, "counts"), coins, seg, _chk(self.counts3, "counts3") if seg else None)
+                         mono, P, int(self.n), _chk(self.counts, "counts"), coins, seg, _chk(self.counts3, "counts3") if seg else None,
+                         float(self.ssim_w) if sP else 0.0, sP)
 
 
 def composite_forward_closs(raw: Tensor, z: Tensor, rays: Tensor, noise: Optional[Tensor], white_bkgd: bool, L: ClossSpec):
@@ -705,11 +712,37 @@ def closs_finish(L: ClossSpec, B: int, ws_last: Tensor, ws_coarse: Optional[Tens
     return terms, stats, patch_d
 
 
-def composite_backward_closs(raw, z, rays, noise, white_bkgd, L: ClossSpec, rgb, depth, stats4, g_loss, patch_d) -> Tensor:
+def closs_finish_ssim(L: ClossSpec, B: int, ws_last: Tensor, ws_coarse: Optional[Tensor], depth_last: Optional[Tensor],
+                      depth_coarse: Optional[Tensor], rgb_last: Tensor, rgb_coarse: Optional[Tensor], want_grad: bool = True):
+    """cnerf_closs_finish_ssim (L.ssim_P > 0) -> (terms[10], stats[8], patch_d[levels, P * n] | None, ssim_d[levels, ssim_P * 768] |
+    None): closs_finish + V's patch SSIM term of every level."""
+    dev = ws_last.device
+    terms, stats = torch.empty(10, device=dev), torch.empty(8, device=dev)
+    levels = 2 if ws_coarse is not None else 1
+    patch_d = torch.empty(levels, L.P * L.n, device=dev) if (L.P > 0 and want_grad) else None
+    ssim_d = torch.empty(levels, L.ssim_P * PATCH_SSIM_RAYS * 3, device=dev) if want_grad else None
+    a = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    t = ClossTail(a(ws_last), a(ws_coarse), int(B), a(L.counts), L.coef, L.far, L.rgb_w, L.depth_w, L.patch_w,
+                  int(L.prior is not None), a(depth_last) if L.P > 0 else None,
+                  a(depth_coarse) if (L.P > 0 and levels == 2) else None, a(L.mono) if L.P > 0 else None, L.P, L.n)
+    rgb_last, rgb_coarse = _chk(rgb_last, "rgb"), _chk(rgb_coarse, "rgb0") if levels == 2 else None
+    _lib.check(_lib.load().cnerf_closs_finish_ssim(C.byref(t), int(L.ssim_P), float(L.ssim_w), _p(rgb_last), _p(rgb_coarse),
+                                                   _p(L.target), _p(terms), _p(stats), _p(patch_d), _p(ssim_d), _stream()),
+               "cnerf_closs_finish_ssim")
+    return terms, stats, patch_d, ssim_d
+
+
+def composite_backward_closs(raw, z, rays, noise, white_bkgd, L: ClossSpec, rgb, depth, stats4, g_loss, patch_d, ssim_d=None) -> Tensor:
     raw, z, rays, noise = _chk(raw, "raw"), _chk(z, "z"), _chk(rays, "rays"), _chk(noise, "noise")
     B, S = z.shape
     d_raw = torch.empty_like(raw)
     c = L.c()
+    if ssim_d is not None:      # + V's patch SSIM seeds (cnerf_composite_bwd_closs_ssim)
+        _lib.check(_lib.load().cnerf_composite_bwd_closs_ssim(
+            _p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S, int(white_bkgd), C.byref(c), _p(rgb), _p(depth),
+            _p(stats4), _p(g_loss), L.rgb_w, L.depth_w, L.patch_w, _p(patch_d), L.P * L.n if patch_d is not None else 0,
+            float(L.ssim_w), _p(ssim_d), ssim_d.numel() // 3, _p(d_raw), _stream()), "cnerf_composite_bwd_closs_ssim")
+        return d_raw
     _lib.check(_lib.load().cnerf_composite_bwd_closs(_p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S,
                                                      int(white_bkgd), C.byref(c), _p(rgb), _p(depth), _p(stats4), _p(g_loss),
                                                      L.rgb_w, L.depth_w, L.patch_w, _p(patch_d),
@@ -985,6 +1018,69 @@ def patch_depth_loss(depth_pred: Tensor, mono: Tensor, P: int, n: int, g_scale: 
     _lib.check(_lib.load().cnerf_patch_depth_loss(_p(depth_pred), _p(mono), int(P), int(n), float(g_scale), _p(loss),
                                                   _p(d), _stream()), "cnerf_patch_depth_loss")
     return loss, d
+
+
+# ------------------------------------------------------------------------------------------ SSIM (pytorch-msssim 0.2.1)
+PATCH_SSIM_RAYS = 256       # rays of one of V's 16 x 16 patches
+
+
+def _ssim_args(X: Tensor, Y: Tensor, win_size: int):
+    for t, n in ((X, "X"), (Y, "Y")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+            raise CnerfError(f"ssim: {n} must be a float32 GPU tensor (consistentnerf_amd has no CPU path), got "
+                             f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '-')}")
+    if X.dim() != 4 or X.shape != Y.shape or X.numel() == 0:
+        raise CnerfError(f"ssim: X and Y must be non-empty [N, C, H, W] tensors of one shape, got {tuple(X.shape)} / {tuple(Y.shape)}")
+    return X.contiguous(), Y.contiguous()
+
+
+def ssim_forward(X: Tensor, Y: Tensor, win_size: int, win_sigma: float, C1: float, C2: float, want_cs: bool = True):
+    """cnerf_ssim_fwd: (ssim [N, C], cs [N, C] | None) = the per-channel means of the SSIM / contrast-structure maps."""
+    X, Y = _ssim_args(X, Y, win_size)
+    N, Cc, H, W = X.shape
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.cnerf_ssim_ws_floats(N, Cc, H, W, int(win_size)) // 2), device=X.device, dtype=torch.float64)
+    s = torch.empty(N, Cc, device=X.device)
+    cs = torch.empty(N, Cc, device=X.device) if want_cs else None
+    _lib.check(lib.cnerf_ssim_fwd(_p(X), _p(Y), N, Cc, H, W, int(win_size), float(win_sigma), float(C1), float(C2), _p(s), _p(cs),
+                                  _p(ws), _stream()), "cnerf_ssim_fwd")
+    return s, cs
+
+
+def ssim_backward(X: Tensor, Y: Tensor, win_size: int, win_sigma: float, C1: float, C2: float, g_ssim: Tensor, want_dY: bool = True):
+    """cnerf_ssim_bwd: (dX, dY | None), the gradient of sum(g_ssim * ssim) (g_ssim [N, C])."""
+    X, Y = _ssim_args(X, Y, win_size)
+    N, Cc, H, W = X.shape
+    g = _chk(g_ssim.reshape(N, Cc), "g_ssim")
+    lib = _lib.load()
+    ws = torch.empty(lib.cnerf_ssim_bwd_ws_floats(N, Cc, H, W, int(win_size)), device=X.device)
+    dX = torch.empty_like(X)
+    dY = torch.empty_like(Y) if want_dY else None
+    _lib.check(lib.cnerf_ssim_bwd(_p(X), _p(Y), N, Cc, H, W, int(win_size), float(win_sigma), float(C1), float(C2), _p(g), _p(dX),
+                                  _p(dY), _p(ws), _stream()), "cnerf_ssim_bwd")
+    return dX, dY
+
+
+def avg_pool2(X: Tensor) -> Tensor:
+    """cnerf_avg_pool2: avg_pool2d(X, 2, stride=2, padding=[H % 2, W % 2]) with the padding counted (MS-SSIM's level step)."""
+    X = _chk(X, "X")
+    N, Cc, H, W = X.shape
+    out = torch.empty(N, Cc, H // 2 + H % 2, W // 2 + W % 2, device=X.device)
+    _lib.check(_lib.load().cnerf_avg_pool2(_p(X), N, Cc, H, W, _p(out), _stream()), "cnerf_avg_pool2")
+    return out
+
+
+def patch_ssim_loss(rgb: Tensor, target: Tensor, P: int, want_grad: bool = True):
+    """V:1696-1720's SSIM lines (cnerf_patch_ssim_loss): (value[1] = sum_p ssim_p / 4, d value / d rgb [P * 256, 3] | None) over
+    the first P * 256 rays."""
+    rgb, target = _chk(rgb.reshape(-1, 3), "rgb"), _chk(target.reshape(-1, 3), "target")
+    n = int(P) * PATCH_SSIM_RAYS
+    if rgb.shape[0] < n or target.shape[0] < n:
+        raise CnerfError(f"patch_ssim_loss: need {P} x {PATCH_SSIM_RAYS} rays, got {rgb.shape[0]} / {target.shape[0]}")
+    value = torch.empty(1, device=rgb.device)
+    d = torch.empty(n, 3, device=rgb.device) if want_grad else None
+    _lib.check(_lib.load().cnerf_patch_ssim_loss(_p(rgb), _p(target), int(P), _p(value), _p(d), _stream()), "cnerf_patch_ssim_loss")
+    return value, d
 
 
 def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float, beta1=0.9, beta2=0.999, eps=1e-8,

@@ -432,8 +432,12 @@ class _RenderClossFn(torch.autograd.Function):
             raise ops.CnerfError("render_loss: gradients w.r.t. z_vals / rays are not implemented (only w.r.t. raw)")
         rgb, disp, acc, weights, depth, ws = ops.composite_forward_closs(raw, z, rays, noise, white, L)
         want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        terms, stats, patch_d = ops.closs_finish(L, z.shape[0], ws, ws_c, depth, depth_c, want_grad=want)
-        ctx.save_for_backward(raw, raw_c, z, z_c, rays, rgb, rgb_c, depth, depth_c, stats, patch_d)
+        if L.ssim_P > 0:    # + V's patch SSIM term of every level (loss -= ssim_w ssim_level)
+            terms, stats, patch_d, ssim_d = ops.closs_finish_ssim(L, z.shape[0], ws, ws_c, depth, depth_c, rgb, rgb_c, want_grad=want)
+        else:
+            terms, stats, patch_d = ops.closs_finish(L, z.shape[0], ws, ws_c, depth, depth_c, want_grad=want)
+            ssim_d = None
+        ctx.save_for_backward(raw, raw_c, z, z_c, rays, rgb, rgb_c, depth, depth_c, stats, patch_d, ssim_d)
         ctx.noise, ctx.noise_c, ctx.white, ctx.L = noise, noise_c, white, L
         ctx.mark_non_differentiable(terms, rgb, disp, acc, weights, depth)
         ctx.set_materialize_grads(False)
@@ -441,17 +445,18 @@ class _RenderClossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, *_rest):
-        raw, raw_c, z, z_c, rays, rgb, rgb_c, depth, depth_c, stats, patch_d = ctx.saved_tensors
+        raw, raw_c, z, z_c, rays, rgb, rgb_c, depth, depth_c, stats, patch_d, ssim_d = ctx.saved_tensors
         d_raw = d_raw_c = None
         if g_loss is not None:
             L = ctx.L
             w = 8 if L.seg_row else 4       # (two segments: per level [2][4] seed weights, cnerf_closs_finish_ss2)
             if ctx.needs_input_grad[0]:
                 d_raw = ops.composite_backward_closs(raw, z, rays, ctx.noise, ctx.white, L, rgb, depth, stats[0:w], g_loss,
-                                                     None if patch_d is None else patch_d[0])
+                                                     None if patch_d is None else patch_d[0], None if ssim_d is None else ssim_d[0])
             if raw_c is not None and ctx.needs_input_grad[1]:
                 d_raw_c = ops.composite_backward_closs(raw_c, z_c, rays, ctx.noise_c, ctx.white, L, rgb_c, depth_c, stats[w:2 * w],
-                                                       g_loss, None if patch_d is None else patch_d[1])
+                                                       g_loss, None if patch_d is None else patch_d[1],
+                                                       None if ssim_d is None else ssim_d[1])
         return (d_raw, d_raw_c) + (None,) * 10
 
 

@@ -246,13 +246,43 @@ def midas_patch_loss(depth_pred, mono_dpt_s, patch_num=4, patch_size=16):
     return _PatchDepthLossFn.apply(depth_pred, mono_dpt_s, int(patch_num), int(patch_size) * int(patch_size))
 
 
+class _PatchSsimFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rgb, target, patch_num):
+        value, d = ops.patch_ssim_loss(rgb, target, patch_num, ctx.needs_input_grad[0])
+        ctx.save_for_backward(d)
+        ctx.shape = rgb.shape
+        return value[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        d, = ctx.saved_tensors
+        out = torch.zeros(ctx.shape, device=d.device).reshape(-1)
+        out[:d.numel()] = (d * g).reshape(-1)
+        return out.reshape(ctx.shape), None, None
+
+
+def patch_ssim(rgb, target_s, patch_num=4, patch_size=16):
+    """`ssim_fine` / `ssim_coarse` of V:1696-1720 / V:1829-1852: sum over the batch's first patch_num 16 x 16 patches of
+    ssim(rgb_patch.reshape(1, 16, 16, 3), target_patch.reshape(1, 16, 16, 3), data_range=1, size_average=False), divided by V's
+    literal 4 — the NHWC patch read as NCHW, as the reference does (ssim.py).  One launch for the value and d / d rgb; the caller
+    subtracts 0.005 times it (V:1727, V:1858).  Pass the noisy maps under `--use_noise`, as for the other terms."""
+    if int(patch_size) != 16:
+        raise ValueError(f"patch_ssim: the reference reshapes each patch to [1, 16, 16, 3] (patch_size 16), got {patch_size}")
+    return _PatchSsimFn.apply(rgb, target_s.reshape(-1, 3), int(patch_num))
+
+
 # ----------------------------------------------------------------------------- the step's loss as one call
 _TERM_NAMES = ("loss", "img_loss", "depth_loss", "patch_loss", "img_loss0", "depth_loss0", "patch_loss0")
 
 
 def _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, coef, far, rgb_w, depth_w, mono, P, ps, patch_w, counts,
-                       kwargs):
-    """The reference's own sequence (V:1645-1865) on render()'s maps: what render_loss computes, launch by launch."""
+                       kwargs, ssim_w=0.0, ssim_patches=4):
+    """The reference's own sequence (V:1645-1865) on render()'s maps: what render_loss computes, launch by launch.  ssim_w != 0:
+    + V's patch SSIM term of every level over the first ssim_patches 16 x 16 patches (loss -= ssim_w ssim_level, after the
+    level's monocular term)."""
+    if ssim_w != 0 and int(ps) != 16:
+        raise ValueError(f"render_loss: the patch SSIM term needs 16 x 16 patches (V:1699), got patch_size {ps}")
     rgb, disp, acc, depth, extras = render(H, W, K, chunk=chunk, rays=rays, **kwargs)
     tgt = target_s.reshape(-1, 3)
     with_depth = depth_prior is not None
@@ -266,6 +296,10 @@ def _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, coef, 
             pl = midas_patch_loss(d, mono, P, ps)
             part = part + patch_w * pl
             terms["patch_loss" + suffix] = pl.detach()
+        if ssim_w != 0:
+            sl = patch_ssim(c, tgt, ssim_patches, ps)
+            part = part - ssim_w * sl
+            terms["ssim" + suffix] = sl.detach()
         if with_depth:
             part = part + depth_w * dl
             terms["depth_loss" + suffix] = dl.detach()
@@ -279,21 +313,27 @@ def _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, coef, 
 
 
 def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32, rays=None, hardmask_coef=0.2, depth_far=None,
-                rgb_w=1.0, depth_w=1.0, mono=None, patch_num=4, patch_size=16, patch_w=0.001, counts=None, _ss_coins=None, **kwargs):
+                rgb_w=1.0, depth_w=1.0, mono=None, patch_num=4, patch_size=16, patch_w=0.001, counts=None, ssim_w=0.0, _ss_coins=None,
+                **kwargs):
     """The loss of one run_nerf_view.train() step as ONE call (V:1636-1865 with the terms this package builds):
 
         rgb, disp, acc, depth_pred, extras = render(H, W, K, chunk=, rays=batch_rays, retraw=True, **render_kwargs_train)
         img_loss   = img2mse(rgb[m == 1], target_s[m == 1]) + hardmask_coef * img2mse(rgb[m == 0], target_s[m == 0])   # V:1645-1648
         loss       = rgb_w * img_loss + patch_w * mono_depth_mses(depth_pred[:P * ps * ps], mono)                   # V:1672-1726
+        loss      -= ssim_w * sum_p ssim(rgb_p.reshape(1, 16, 16, 3), target_p.reshape(1, 16, 16, 3), data_range=1) / 4   # V:1701-1727
         loss      += depth_w * img2mse(depth_pred[m == 1] / far, depth_prior[m == 1] / far)                         # V:1737
-        ... and the same three terms of the coarse level (V:1786-1788, V:1855-1857, V:1865)
+        ... and the same terms of the coarse level (V:1786-1788, V:1855-1858, V:1865)
 
     with every term folded into the compositing launches (run_nerf._RenderClossFn): one autograd node from both levels' `raw` to
     the scalar.  mask [B] (0 / 1; None = plain img2mse), depth_prior [B] (None = no depth terms), mono [P * ps * ps] (None = no patch
     term), depth_far = the `far` the depths are divided by (default: the render's far bound), counts = global (n1, n0) for a batch
     sharded over ranks.  -> (loss, terms, rgb, disp, acc, depth, extras); terms: dict of detached 0-d tensors (img_loss, depth_loss,
     patch_loss, img_loss0, ...).  Values equal the lines above (fp64-association round-off on the sums), parameter gradients after
-    loss.backward() bit for bit.  Batches beyond one chunk, more than 8 patches, CPU tensors: the lines above, literally."""
+    loss.backward() bit for bit.  Batches beyond one chunk, more than 8 patches, CPU tensors: the lines above, literally.
+    ssim_w (0 = off, the call without the term; 0.005 = V): V's patch SSIM term on the first patch_num 16 x 16 patches of the
+    batch (whether or not `mono` is given), folded into the same launches; terms gain `ssim` / `ssim0`, the level values.  LPIPS
+    stays with the caller: loss + 0.005 * lpips(...) on the returned maps, by autograd."""
+    ssim_w = float(ssim_w)
     far = float(kwargs.get('far', 1.)) if depth_far is None else float(depth_far)
     n = rays[0].reshape(-1, 3).shape[0] if rays is not None else 0
     P = int(patch_num) if mono is not None else 0
@@ -302,6 +342,12 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
     ok = (rays is not None and 0 < n <= chunk and tgt is not None and tgt.is_cuda and tgt.dtype == torch.float32 and tgt.shape[0] == n
           and kwargs.get('c2w') is None and P <= 8 and P * ps2 <= n and not torch.is_tensor(kwargs.get('near'))
           and not torch.is_tensor(kwargs.get('far')))
+    sP = int(patch_num) if ssim_w != 0 else 0
+    if _ss_coins is not None and ssim_w != 0:
+        raise ValueError("render_loss: the in-loop consistency step (VT) has no SSIM term; ssim_w must be 0 with _ss_coins")
+    if sP > 0 and int(patch_size) != 16:
+        raise ValueError(f"render_loss: the patch SSIM term needs 16 x 16 patches (V:1699), got patch_size {patch_size}")
+    ok = ok and sP <= 8 and sP * ops.PATCH_SSIM_RAYS <= n
     if _ss_coins is not None:       # the in-loop consistency step's primary terms (ss_step_loss): VT:941-969 on render()'s maps
         if not ok or mask is None:
             rgb, disp, acc, depth, extras = render(H, W, K, chunk=chunk, rays=rays, **kwargs)
@@ -315,11 +361,16 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
         return loss, {k: t[i] for i, k in enumerate(_TERM_NAMES)}, rgb, disp, acc, depth, extras
     if not ok:
         return _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, hardmask_coef, far, rgb_w, depth_w, mono, P,
-                                  patch_size, patch_w, counts, kwargs)
-    spec = ops.ClossSpec(tgt, mask, depth_prior, far, hardmask_coef, rgb_w, depth_w, patch_w, mono, P, ps2, counts)
+                                  patch_size, patch_w, counts, kwargs, ssim_w=ssim_w, ssim_patches=int(patch_num))
+    spec = ops.ClossSpec(tgt, mask, depth_prior, far, hardmask_coef, rgb_w, depth_w, patch_w, mono, P, ps2, counts, ssim_w=ssim_w,
+                         ssim_P=sP)
     rgb, disp, acc, depth, extras = render(H, W, K, chunk=chunk, rays=rays, _target=spec, **kwargs)
     loss, t = extras.pop('loss'), extras.pop('loss_terms')
     terms = {k: t[i] for i, k in enumerate(_TERM_NAMES)}
+    if sP > 0:
+        terms["ssim"] = t[8]
+        if 'rgb0' in extras:
+            terms["ssim0"] = t[9]
     return loss, terms, rgb, disp, acc, depth, extras
 
 

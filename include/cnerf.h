@@ -21,7 +21,10 @@
 extern "C" {
 #endif
 
-#define CNERF_ABI_VERSION 6   /* 6: + the in-loop consistency step as ONE render whose row count lives on the device: cnerf_ss_batch (the combined
+#define CNERF_ABI_VERSION 6   /* 6 (additions since, every earlier symbol unchanged): SSIM / MS-SSIM (the ssim section below: cnerf_ssim_fwd,
+                                * cnerf_ssim_bwd, cnerf_avg_pool2, cnerf_patch_ssim_loss and their workspace queries) and V's patch SSIM term
+                                * folded into the C3 step (cnerf_closs_finish_ssim, cnerf_composite_bwd_closs_ssim).
+                                * 6: + the in-loop consistency step as ONE render whose row count lives on the device: cnerf_ss_batch (the combined
                                 * batch + its live-row count), cnerf_mlp_fwd_live / cnerf_mlp_bwd_live / cnerf_mlp_bwd_pair_live (launches of a fixed
                                 * capacity that stop at a device-side count), cnerf_closs_finish_ss2 (the two-segment loss tail); cnerf_closs gains
                                 * a trailing `seg_row` (0 = the v5 behaviour), cnerf_ss_ref_rays' meta grows to 8 ints; otherwise v5 unchanged.
@@ -314,6 +317,20 @@ int cnerf_composite_bwd_closs(const float* raw, int raw_ch, const float* z, cons
                               int64_t B, int S, int white_bkgd, const cnerf_closs* L, const float* rgb, const float* depth,
                               const float* stats, const float* g_loss, float rgb_w, float depth_w, float patch_w,
                               const float* patch_d, int64_t n_patch_rays, float* d_raw, void* stream);
+/* V's patch SSIM term (V:1696-1727, coarse V:1817-1858: loss -= 0.005 ssim_level) folded into the same two launches.
+ *   cnerf_closs_finish_ssim = cnerf_closs_finish + per level ssim_level = (sum_p ssim_p) / 4 over the batch's first ssim_P <= 8
+ *       patches of 256 rays (cnerf_patch_ssim_loss's arithmetic on rgb_last / rgb_coarse [B,3] against target [B,3]), accumulated
+ *       after the level's patch term as loss -= ssim_w ssim_level; terms10 = the 8 of cnerf_closs_finish + ssim, ssim0;
+ *       ssim_d[levels][ssim_P 768] = d ssim_level / d rgb (NULL: not wanted).
+ *   cnerf_composite_bwd_closs_ssim = cnerf_composite_bwd_closs + g_rgb += ssim_d ((-g) ssim_w) on the first n_ssim_rays rays
+ *       (ssim_d = the level's slice of cnerf_closs_finish_ssim's). */
+int cnerf_closs_finish_ssim(const cnerf_closs_sum* t, int ssim_P, float ssim_w, const float* rgb_last, const float* rgb_coarse,
+                            const float* target, float* terms10, float* stats, float* patch_d, float* ssim_d, void* stream);
+int cnerf_composite_bwd_closs_ssim(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride, const float* noise,
+                                   int64_t B, int S, int white_bkgd, const cnerf_closs* L, const float* rgb, const float* depth,
+                                   const float* stats, const float* g_loss, float rgb_w, float depth_w, float patch_w,
+                                   const float* patch_d, int64_t n_patch_rays, float ssim_w, const float* ssim_d, int64_t n_ssim_rays,
+                                   float* d_raw, void* stream);
 
 /* ---- a8: inverse-CDF sampling  (sample_pdf H:206-250) ------------------------------------------ */
 /* bins[B,Nb], weights[B,Nb-1], u[B,Nf] (u_row_stride 0 broadcasts one row) -> samples[B,Nf];
@@ -531,6 +548,26 @@ int cnerf_masked_loss(const float* rgb, const float* target, const float* depth,
  * alpha_p = mean(prn - gtn).  d_depth[P*n] (optional) = g_scale * dloss/d depth_pred, autograd's tie rules. */
 int cnerf_patch_depth_loss(const float* depth_pred, const float* mono, int P, int n, float g_scale,
                            float* loss, float* d_depth, void* stream);
+
+/* ---- SSIM / MS-SSIM (pytorch-msssim 0.2.1: V:1701, V:1836, img2ssim of the metrics V:2053-2087) ------------------------------ */
+/* X, Y [N, C, H, W] (N C <= 65535 planes); window = the normalised Gaussian of odd win_size <= 31 taps and win_sigma; C1 / C2 =
+ * (K1 data_range)^2 / (K2 data_range)^2.  The filter is a valid correlation along H, then W, each skipped when the side is shorter
+ * than the window.  cnerf_ssim_fwd: ssim_nc / cs_nc [N C] = the per-plane means of the SSIM and contrast-structure maps (cs_nc
+ * nullable); workspace = cnerf_ssim_ws_floats() floats, 8-byte aligned; per-workgroup fp64 partials summed in index order (no
+ * atomics: identical bits call after call).  cnerf_ssim_bwd: dX (and dY, nullable) [N, C, H, W] = the gradient of sum g_ssim[nc]
+ * ssim_nc[nc]; workspace = cnerf_ssim_bwd_ws_floats() floats (the four coefficient maps). */
+int64_t cnerf_ssim_ws_floats(int64_t N, int64_t C, int64_t H, int64_t W, int win_size);
+int cnerf_ssim_fwd(const float* X, const float* Y, int64_t N, int64_t C, int64_t H, int64_t W, int win_size, float win_sigma,
+                   float C1, float C2, float* ssim_nc, float* cs_nc, float* workspace, void* stream);
+int64_t cnerf_ssim_bwd_ws_floats(int64_t N, int64_t C, int64_t H, int64_t W, int win_size);
+int cnerf_ssim_bwd(const float* X, const float* Y, int64_t N, int64_t C, int64_t H, int64_t W, int win_size, float win_sigma,
+                   float C1, float C2, const float* g_ssim, float* dX, float* dY, float* workspace, void* stream);
+/* avg_pool2d(X, kernel_size=2, stride=2, padding=(H % 2, W % 2)) with the padding counted: out [N, C, H / 2 + H % 2, W / 2 + W % 2] */
+int cnerf_avg_pool2(const float* X, int64_t N, int64_t C, int64_t H, int64_t W, float* out, void* stream);
+/* V's patch term on its own: rgb / target = the first P * 256 rays [P 256, 3] (P <= 16); each patch read as the library reads the
+ * [1, 16, 16, 3] NHWC view (C = ray / 16, H = ray % 16, W = colour; H filtered to 6, W unfiltered).  value[0] = (sum_p ssim_p) / 4
+ * (V's literal 4), d_rgb [P 256, 3] (nullable) = d value / d rgb. */
+int cnerf_patch_ssim_loss(const float* rgb, const float* target, int P, float* value, float* d_rgb, void* stream);
 
 /* ---- f-1: optimiser tail  (clip_grad_value_ V:1983, Adam R:210/780, lr decay R:784-788) --------- */
 /* In-place Adam over n contiguous floats; clip<=0 disables the value clip; step is 1-based.  The hyper-parameters are
