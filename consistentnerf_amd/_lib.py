@@ -4,7 +4,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# CNERF_LIB_PATH: load an experiment build of the same ABI instead (kernel ablations, scripts/kvariants.sh)
+# CNERF_LIB_PATH: load a variant build of the same ABI instead (the -DCN_TIMING build: scripts/ktiming.py, wgrad_trace.py)
 LIB_PATH = os.environ.get("CNERF_LIB_PATH") or os.path.join(_HERE, "libcnerf_hip.so")
 MAX_TENSORS = 48
 

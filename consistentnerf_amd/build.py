@@ -10,8 +10,9 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-# CN_BUILD_TAG=<name> builds an experiment variant (with CN_EXTRA_FLAGS) next to the product library; a variant is
-# only ever loaded when CNERF_LIB_PATH points at it (scripts/kvariants.sh).
+# CN_BUILD_TAG=<name> builds a variant (with CN_EXTRA_FLAGS) next to the product library, e.g. the -DCN_TIMING
+# instrumentation build that scripts/ktiming.py and scripts/wgrad_trace.py read; a variant is only ever loaded when
+# CNERF_LIB_PATH points at it.
 TAG = os.environ.get("CN_BUILD_TAG", "")
 OBJ = os.path.join(CSRC, "build" + ("_" + TAG if TAG else ""))
 LIB = os.path.join(HERE, "libcnerf_hip.so") if not TAG else os.path.join(ROOT, "variants", f"libcnerf_{TAG}.so")

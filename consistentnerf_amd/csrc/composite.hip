@@ -260,9 +260,6 @@ __global__ __launch_bounds__(WV * 64) void composite_fwd_k(const float* __restri
       // wait is written out; `scripts/isa_ticket_check.py` asserts the s_waitcnt vmcnt(0) sits between the two in the ISA.
       __hip_atomic_store(reinterpret_cast<unsigned long long*>(mse.part) + blockIdx.x, (unsigned long long)__double_as_longlong(s),
                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if defined(CN_MSE_HEAVY_FENCE)
-      __threadfence();
-#elif !defined(CN_MSE_RELEASE_TICKET)
       // vmcnt(0): the sc1 store has been acknowledged by the memory side.  Written as inline assembly with a "memory" clobber
       // (ADVICE r05): the mnemonic carries no architecture-specific immediate (the builtin's 0x0f70 is the gfx9 encoding), and the
       // clobber is a compiler-level barrier on BOTH sides — the partial's store cannot sink below the wait, the ticket RMW cannot be
@@ -270,7 +267,6 @@ __global__ __launch_bounds__(WV * 64) void composite_fwd_k(const float* __restri
       // is asserted at BUILD time (consistentnerf_amd/build.py -> scripts/isa_ticket_check.py), not only by a test.
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
-#endif
       // Two-level ticket: same-address atomics at agent scope serialise at ~40 ns each (measured: 8192 workgroups on ONE counter
       // cost 0.36 ms), so a workgroup first tickets inside its group of MSE_GROUP (one counter per group, 256 B apart); the last of
       // a group tickets at the top.  <= MSE_GROUP + ngroups serialised atomics instead of gridDim.x.
@@ -278,14 +274,9 @@ __global__ __launch_bounds__(WV * 64) void composite_fwd_k(const float* __restri
       const unsigned in_grp = grp + 1 == ngroups ? gridDim.x - grp * MSE_GROUP : MSE_GROUP;
       unsigned* gctr = mse.counter + MSE_CTR_STRIDE * (1 + grp);
       bool last = false;
-#ifdef CN_MSE_RELEASE_TICKET   // ablation: the textbook form (release-ordered agent-scope RMW; measured in profiles/r05_ticket_*.txt)
-      constexpr int TICKET_ORDER = __ATOMIC_ACQ_REL;
-#else
-      constexpr int TICKET_ORDER = __ATOMIC_RELAXED;
-#endif
-      if (__hip_atomic_fetch_add(gctr, 1u, TICKET_ORDER, __HIP_MEMORY_SCOPE_AGENT) == in_grp - 1) {
+      if (__hip_atomic_fetch_add(gctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == in_grp - 1) {
         __hip_atomic_store(gctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // re-arm (nobody else touches it any more)
-        last = __hip_atomic_fetch_add(mse.counter, 1u, TICKET_ORDER, __HIP_MEMORY_SCOPE_AGENT) == ngroups - 1;
+        last = __hip_atomic_fetch_add(mse.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ngroups - 1;
       }
       is_last = last;
     }
@@ -295,9 +286,6 @@ __global__ __launch_bounds__(WV * 64) void composite_fwd_k(const float* __restri
       // (its partial complete before it, above).  The partial loads below are agent-scope atomic loads (sc1: served by the memory
       // side, never by this XCD's L2 or the vector L1) and depend on is_last, which came back from the ticket atomic, so they cannot
       // be issued before it returned.
-#ifdef CN_MSE_HEAVY_FENCE
-      __threadfence();
-#endif
       double s = 0.0;
       for (unsigned i = lane; i < gridDim.x; i += 64)
         s += __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(mse.part) + i, __ATOMIC_RELAXED,

@@ -197,12 +197,8 @@ struct Ring {
     // nothing is scheduled across the publish: the ring's only writer is the DMA asm, which the machine scheduler does not
     // see as a store to the LDS the next K-step's ds_reads load from
     __builtin_amdgcn_sched_barrier(0);
-#ifndef CN_ABL_R_NODMA
     __builtin_amdgcn_s_waitcnt(0x0f70 | (OUTSTANDING & 15) | ((OUTSTANDING >> 4) << 14));   // vmcnt only (gfx9 encoding)
-#endif
-#ifndef CN_ABL_R_NOBAR
     __syncthreads();
-#endif
     __builtin_amdgcn_sched_barrier(0);
   }
 };
@@ -212,9 +208,6 @@ struct Ring {
 // Training: the input tiles X (already rectified, fp32) go out to the stash while they are the B operand — the two register
 // quads of K-step s (tile s >> 1, quads 2 (s & 1), + 1) behind tiles 0 and 1 of that step: one 16-byte store per lane each, a
 // wave writes 1 KiB contiguous (mlp_common.hpp TileStores, dealt out for the 16-feature K-steps of this kernel).
-#ifndef CN_STASH_AUX
-#define CN_STASH_AUX 0   // cache-policy bits of the stash / gradient stores (experiment knob: sc0 = 1, nt = 2, sc1 = 16)
-#endif
 struct NoStash {
   __device__ __forceinline__ void operator()(int, int) const {}
 };
@@ -227,11 +220,7 @@ struct StashStores {
     if (t > 1) return;       // (behind tiles 0 and 1: every GEMM has at least two output tiles)
     const int tt = s >> 1, q = 2 * (s & 1) + t;
     const f32x4 v = {X[tt][4 * q], X[tt][4 * q + 1], X[tt][4 * q + 2], X[tt][4 * q + 3]};
-    #ifdef CN_ABL_R_OOBSTORE   // (timing only: the store is issued, its data read, and dropped by the bounds check)
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, voff | 0x40000000, soff + (4 * tt + q) * 1024, CN_STASH_AUX);
-#else
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, voff, soff + (4 * tt + q) * 1024, CN_STASH_AUX);
-#endif
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, voff, soff + (4 * tt + q) * 1024, 0);
   }
 };
 
@@ -244,16 +233,9 @@ __device__ __forceinline__ void gemm_ring_reg3(f32x16 (&Q)[NTO], const f32x16 (&
   static_assert(KS % 4 == 0, "ring slot continuity");
   static_assert(!PAIR || NTO % 2 == 0, "tiles are processed in pairs");
   static_assert(NTO >= 4, "the publish sits behind tile NTO / 2 - 1, the cross-step prefetch in the last tiles");
-#ifdef CN_R_NOPAIR
-  constexpr int TP = 1;
-#else
   constexpr int TP = PAIR ? 2 : 1;
-#endif
-#ifndef CN_R_AHEAD
-#define CN_R_AHEAD 2
-#endif
-  constexpr int NA = 4, AH = (TP == 1) ? CN_R_AHEAD : 2;     // tiles the A reads run ahead of the MFMAs (TP + AH <= NA + ... sets)
-  static_assert(AH + TP <= NA + (TP == 1 ? 0 : 0) && AH >= 2, "register sets");
+  constexpr int NA = 4, AH = 2;     // tiles the A reads run ahead of the MFMAs (TP + AH <= NA register sets)
+  static_assert(AH + TP <= NA, "register sets");
   constexpr int IA[6] = {0, 1, 2, 0, 1, 0}, IB[6] = {2, 1, 0, 1, 0, 0};   // cross terms w_i x_j, i + j < 3, smallest first
   const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   // K-step s + 1 is published in the MIDDLE of K-step s (behind tile NTO/2 - 1), not at its end: the A operands of its first two
@@ -290,50 +272,30 @@ __device__ __forceinline__ void gemm_ring_reg3(f32x16 (&Q)[NTO], const f32x16 (&
           const int tt = t + u;
           const bool do_split = s + 1 < KS && tt < 4;
           Q[tt] = mfma_bf(A[tt % NA][IA[k]], bc[IB[k]], (INIT && s == 0 && k == 0) ? zero : Q[tt]);
-#ifndef CN_ABL_R_NOLDS      // (ablation builds, timings only: -DCN_ABL_R_NOLDS / NODMA / NOSPLIT / NOSIDE / NOBAR)
           if (k < 3) {
             if (tt + AH < NTO) A[(tt + AH) % NA][k] = R.a(s & 3, tt + AH, k);
             else if (s + 1 < KS) A[(tt + AH) % NA][k] = R.a((s + 1) & 3, tt + AH - NTO, k);   // (published behind tile MID - 1)
           }
-#endif
-#ifndef CN_ABL_R_NODMA
           if (k == 3) {
-#else
-          if (k == 3 && false) {
-#endif
 #pragma unroll
             for (int j = tt; j < Ring<NT, NP>::PW; j += NTO) {
               if (s + 2 < KS) R.dma_piece(poff, s + 2, (s + 2) & 3, j);
               else if (poff_next >= 0) R.dma_piece(poff_next, s + 2 - KS, (s + 2) & 3, j);
             }
           }
-#ifndef CN_ABL_R_NOSPLIT
           if (do_split) {
-#else
-          if (do_split && false) {
-#endif
             if (k == 0) split3_s0<RELU>(S[u], X[sn >> 1][8 * (sn & 1) + 2 * tt], X[sn >> 1][8 * (sn & 1) + 2 * tt + 1], bn, tt);
             if (k == 1 || k == 3) split3_residual(S[u]);
             if (k == 2) split3_plane(S[u], bn, 1, tt);
             if (k == 4) split3_plane(S[u], bn, 2, tt);
           }
-#ifndef CN_ABL_R_NOSIDE
           // the side stores ride behind tiles 0 and 1.  (Behind the LAST two tiles — younger than this K-step's DMA pieces in the
           // in-order vmcnt queue, so that no publish ever waits for an HBM store acknowledgement — measured level on the dgrad
-          // and 10 % slower on the training forward: -DCN_R_SIDE_LAST.)
-#ifdef CN_R_SIDE_LAST
-          if (k == 5 && tt >= NTO - 2) side(s, tt - (NTO - 2));
-#else
+          // and 10 % slower on the training forward.)
           if (k == 5) side(s, tt);
-#endif
-#endif
           __builtin_amdgcn_sched_barrier(0);
           if (k == 5 && tt == MID - 1) {     // K-step s + 1 (or the next panel's K-step 0) is published here
-#ifdef CN_ABL_R_WAITSLACK   // (timing only, results race: the publish leaves the previous K-step's stores and later pieces in flight)
-            if (s + 2 < KS || poff_next >= 0) R.template publish<OUT + (SIDE_OPS ? CN_ABL_R_WAITSLACK : 0)>();
-#else
             if (s + 2 < KS || poff_next >= 0) R.template publish<OUT>();
-#endif
             else R.template publish<SIDE_OPS>();      // (no DMA was issued in this K-step: only the side stores may be in flight)
           }
         }
@@ -349,58 +311,56 @@ __device__ __forceinline__ void gemm_ring_reg(f32x16 (&Q)[NTO], const f32x16 (&X
   // SIDE_OPS = vector-memory instructions `side` issues per K-step: they sit in the in-order vmcnt queue between this step's
   // DMA pieces, so the publish may leave that many more operations outstanding
   if constexpr (NP == 3 && NTO >= 4) {       // (the two-tile view GEMM of a W = 128 network keeps the plain schedule below)
-#ifndef CN_BF3_BURST
     gemm_ring_reg3<NTI, NTO, NT, RELU, Side, SIDE_OPS, INIT, PAIR>(Q, X, R, poff, poff_next, side);
-    return;
-#endif
-  }
-  constexpr int KS = 2 * NTI, PW = Ring<NT, NP>::PW + SIDE_OPS;
-  static_assert(KS % 4 == 0, "ring slot continuity");
-  u32x4 bc[NP], bn[NP];
+  } else {
+    constexpr int KS = 2 * NTI, PW = Ring<NT, NP>::PW + SIDE_OPS;
+    static_assert(KS % 4 == 0, "ring slot continuity");
+    u32x4 bc[NP], bn[NP];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) split_pair<NP, RELU>(X[0][2 * q], X[0][2 * q + 1], bc, q);
+    for (int q = 0; q < 4; ++q) split_pair<NP, RELU>(X[0][2 * q], X[0][2 * q + 1], bc, q);
 #pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    u32x4 A[3][NP];       // A operands run two tiles ahead of the MFMAs that consume them (LDS latency)
+    for (int s = 0; s < KS; ++s) {
+      u32x4 A[3][NP];       // A operands run two tiles ahead of the MFMAs that consume them (LDS latency)
 #pragma unroll
-    for (int p = 0; p < NP; ++p) A[0][p] = R.a(s & 3, 0, p);
-    if (NTO > 1) {
+      for (int p = 0; p < NP; ++p) A[0][p] = R.a(s & 3, 0, p);
+      if (NTO > 1) {
 #pragma unroll
-      for (int p = 0; p < NP; ++p) A[1][p] = R.a(s & 3, 1, p);
+        for (int p = 0; p < NP; ++p) A[1][p] = R.a(s & 3, 1, p);
+      }
+#pragma unroll
+      for (int t = 0; t < NTO; ++t) {
+        if (t + 2 < NTO) {
+#pragma unroll
+          for (int p = 0; p < NP; ++p) A[(t + 2) % 3][p] = R.a(s & 3, t + 2, p);
+        }
+        if (INIT && s == 0) products_init<NP>(Q[t], A[t % 3], bc);
+        else products<NP>(Q[t], A[t % 3], bc);
+        // the DMA of K-step s+2, one piece behind each tile's MFMAs (all of them in front would delay the first LDS reads)
+#pragma unroll
+        for (int j = t; j < Ring<NT, NP>::PW; j += NTO) {
+          if (s + 2 < KS) R.dma_piece(poff, s + 2, (s + 2) & 3, j);
+          else if (poff_next >= 0) R.dma_piece(poff_next, s + 2 - KS, (s + 2) & 3, j);
+        }
+        if (s + 1 < KS && t < 4) {
+          const int sn = s + 1;
+          split_pair<NP, RELU>(X[sn >> 1][8 * (sn & 1) + 2 * t], X[sn >> 1][8 * (sn & 1) + 2 * t + 1], bn, t);
+        }
+        side(s, t);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (NTO < 4 && s + 1 < KS) {
+#pragma unroll
+        for (int q = NTO; q < 4; ++q) {
+          const int sn = s + 1;
+          split_pair<NP, RELU>(X[sn >> 1][8 * (sn & 1) + 2 * q], X[sn >> 1][8 * (sn & 1) + 2 * q + 1], bn, q);
+        }
+      }
+#pragma unroll
+      for (int p = 0; p < NP; ++p) bc[p] = bn[p];
+      if (s + 2 < KS) R.template publish<PW>();
+      else if (poff_next >= 0) R.template publish<PW>();
+      else R.template publish<0>();
     }
-#pragma unroll
-    for (int t = 0; t < NTO; ++t) {
-      if (t + 2 < NTO) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) A[(t + 2) % 3][p] = R.a(s & 3, t + 2, p);
-      }
-      if (INIT && s == 0) products_init<NP>(Q[t], A[t % 3], bc);
-      else products<NP>(Q[t], A[t % 3], bc);
-      // the DMA of K-step s+2, one piece behind each tile's MFMAs (all of them in front would delay the first LDS reads)
-#pragma unroll
-      for (int j = t; j < Ring<NT, NP>::PW; j += NTO) {
-        if (s + 2 < KS) R.dma_piece(poff, s + 2, (s + 2) & 3, j);
-        else if (poff_next >= 0) R.dma_piece(poff_next, s + 2 - KS, (s + 2) & 3, j);
-      }
-      if (s + 1 < KS && t < 4) {
-        const int sn = s + 1;
-        split_pair<NP, RELU>(X[sn >> 1][8 * (sn & 1) + 2 * t], X[sn >> 1][8 * (sn & 1) + 2 * t + 1], bn, t);
-      }
-      side(s, t);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (NTO < 4 && s + 1 < KS) {
-#pragma unroll
-      for (int q = NTO; q < 4; ++q) {
-        const int sn = s + 1;
-        split_pair<NP, RELU>(X[sn >> 1][8 * (sn & 1) + 2 * q], X[sn >> 1][8 * (sn & 1) + 2 * q + 1], bn, q);
-      }
-    }
-#pragma unroll
-    for (int p = 0; p < NP; ++p) bc[p] = bn[p];
-    if (s + 2 < KS) R.template publish<PW>();
-    else if (poff_next >= 0) R.template publish<PW>();
-    else R.template publish<0>();
   }
 }
 
@@ -479,32 +439,30 @@ template <int KS, int NTO, int NT, int NP, bool STAGED = true>
 __device__ __forceinline__ void gemm_ring_lds(f32x16 (&Q)[NTO], const float* T, const Ring<NT, NP>& R, int poff, int poff_next,
                                               int m, int hh) {
   if constexpr (NP == 3 && STAGED) {
-#ifndef CN_BF3_BURST
     gemm_ring_lds3<KS, NTO, NT>(Q, T, R, poff, poff_next, m, hh);
-    return;
-#endif
-  }
-  constexpr int PW = Ring<NT, NP>::PW;
+  } else {
+    constexpr int PW = Ring<NT, NP>::PW;
 #pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    if (s + 2 < KS) R.dma(poff, s + 2, (s + 2) & 3);
-    else if (poff_next >= 0) R.dma(poff_next, s + 2 - KS, (s + 2) & 3);
-    const f32x4 c0 = *reinterpret_cast<const f32x4*>(T + enc_off(m, 4 * s + 2 * hh));
-    const f32x4 c1 = *reinterpret_cast<const f32x4*>(T + enc_off(m, 4 * s + 2 * hh + 1));
-    u32x4 b[NP];
-    split_pair<NP, false>(c0[0], c0[1], b, 0);
-    split_pair<NP, false>(c0[2], c0[3], b, 1);
-    split_pair<NP, false>(c1[0], c1[1], b, 2);
-    split_pair<NP, false>(c1[2], c1[3], b, 3);
+    for (int s = 0; s < KS; ++s) {
+      if (s + 2 < KS) R.dma(poff, s + 2, (s + 2) & 3);
+      else if (poff_next >= 0) R.dma(poff_next, s + 2 - KS, (s + 2) & 3);
+      const f32x4 c0 = *reinterpret_cast<const f32x4*>(T + enc_off(m, 4 * s + 2 * hh));
+      const f32x4 c1 = *reinterpret_cast<const f32x4*>(T + enc_off(m, 4 * s + 2 * hh + 1));
+      u32x4 b[NP];
+      split_pair<NP, false>(c0[0], c0[1], b, 0);
+      split_pair<NP, false>(c0[2], c0[3], b, 1);
+      split_pair<NP, false>(c1[0], c1[1], b, 2);
+      split_pair<NP, false>(c1[2], c1[3], b, 3);
 #pragma unroll
-    for (int t = 0; t < NTO; ++t) {
-      u32x4 A[NP];
+      for (int t = 0; t < NTO; ++t) {
+        u32x4 A[NP];
 #pragma unroll
-      for (int p = 0; p < NP; ++p) A[p] = R.a(s & 3, t, p);
-      products<NP>(Q[t], A, b);
+        for (int p = 0; p < NP; ++p) A[p] = R.a(s & 3, t, p);
+        products<NP>(Q[t], A, b);
+      }
+      if (s + 2 < KS || poff_next >= 0) R.template publish<PW>();
+      else R.template publish<0>();
     }
-    if (s + 2 < KS || poff_next >= 0) R.template publish<PW>();
-    else R.template publish<0>();
   }
 }
 

@@ -23,7 +23,6 @@
 // run to run).
 #include <math.h>
 #include <type_traits>
-#include <stdlib.h>
 #include <string.h>
 
 #include "mlp_bf_common.hpp"
@@ -31,19 +30,12 @@
 namespace {
 
 constexpr int MAX_WG_JOBS = 48;
-#ifndef CN_WG_WAVES
-#define CN_WG_WAVES 4
-#endif
-constexpr int NWAVES = CN_WG_WAVES;         // waves per workgroup (1 per SIMD)
+constexpr int NWAVES = 4;                   // waves per workgroup (1 per SIMD)
 constexpr int TM = 32;                      // points per LDS slab
 constexpr int OCTF = 264;                   // LDS pitch (floats) of one 32-point x 8-column block: 256 + 8 (banks)
 constexpr int LDS_BYTES = 160 * 1024;       // all of a CU's LDS: one workgroup per CU
 constexpr int DUMMY_BYTES = 1024;           // landing zone of the no-op DMA pieces (out-of-range reads write zeros)
-#ifdef CN_WGRAD_DYN
-constexpr int LDS_FLOATS = (LDS_BYTES - DUMMY_BYTES - 16) / 4;   // + one ticket word
-#else
 constexpr int LDS_FLOATS = (LDS_BYTES - DUMMY_BYTES) / 4;
-#endif
 
 struct WgJob {
   int net;            // which operand set (WgArgs::net) the job reads / writes: 0, or 1 for the second network of a pair
@@ -78,8 +70,6 @@ struct WgArgs {
   WgJob job[MAX_WG_JOBS];
   WgNet net[2];
   int nj;
-  int total;          // virtual blocks of the launch (CN_WGRAD_DYN)
-  int* counter;       // device ticket counter, zero before the launch (CN_WGRAD_DYN)
 };
 
 // The kernel argument block is read IN PLACE through the constant address space (scalar loads from the kernarg
@@ -102,23 +92,8 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 // while the split partials the workgroups write (0.1-0.3 GB) are read back by the reduction right after the launch: with the
 // stream marked non-temporal the partials survive in the cache hierarchy — wgrad + reduction 1.216 -> 1.188 ms at the 512-ray C4
 // shard, 2.31 -> 2.29 ms at 1024 rays, level at 4096 (`sc1` / `sc0 sc1`: no effect; profiles/r03_wgrad_dma_policy.txt).
-// -DCN_DMA_POL=0 builds without it.
-#ifndef CN_DMA_POL
-#define CN_DMA_POL 1
-#endif
-#if CN_DMA_POL == 1
-#define CN_DMA_POLICY " nt"
-#elif CN_DMA_POL == 2
-#define CN_DMA_POLICY " sc1"
-#elif CN_DMA_POL == 3
-#define CN_DMA_POLICY " sc0 sc1"
-#elif CN_DMA_POL == 4
-#define CN_DMA_POLICY " sc1 nt"
-#else
-#define CN_DMA_POLICY ""
-#endif
 __device__ __forceinline__ void dma16(const i32x4& rs, unsigned lds_addr, int voff, int soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen" CN_DMA_POLICY " lds"
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen nt lds"
                :
                : "s"(__builtin_amdgcn_readfirstlane((int)lds_addr)), "v"(voff), "s"(rs),
                  "s"(__builtin_amdgcn_readfirstlane(soff))
@@ -409,12 +384,8 @@ __device__ __forceinline__ void wgrad_body_bf3(WgNetC& a, WgJobC& jb, float* lds
     }
   };
   auto landed = [&]() __attribute__((always_inline)) {   // this wave's DMA pieces have landed; everybody's: the barrier
-#ifndef CN_ABL_NOWAIT                                    // (ablation builds, timings only: -DCN_ABL_NOWAIT / NOSPLIT / NOREAD / NOBAR)
     __builtin_amdgcn_s_waitcnt(0x0f70);                  // vmcnt(0)
-#endif
-#ifndef CN_ABL_NOBAR
     __syncthreads();
-#endif
   };
   // LDS image (as wgrad_body): block of column octet o at o*OCTF floats, inside it point p, column c at p*8 + c.  Lane (i, hh)
   // reads column 32x + i of points 16 ks + 8 hh + e: one per-lane base + the immediate (4x*OCTF + 128 ks + 8 e) floats; the 32
@@ -488,34 +459,22 @@ __device__ __forceinline__ void wgrad_body_bf3(WgNetC& a, WgJobC& jb, float* lds
               if (h >= 2 * NF) continue;
               const int f = h >> 1, hf = h & 1, fn = f + FPR;     // fn: the fragment read now, split one pair of tile pairs later
               float* v = rw[f % (2 * FPR)];
-#ifdef CN_ABL_NOREAD
-              if (false) {
-#else
               if (fn < NF && k < 2) {        // its values e = 4 hf + 2 k, + 1
-#endif
                 const float* base = lds + nbuf_ * bufF + (fn < AN ? 4 * (tn0 + fn) : xoct + 4 * (tk0 + fn - AN)) * OCTF + lbase + 128 * nks;
                 rw[fn % (2 * FPR)][4 * hf + 2 * k] = base[8 * (4 * hf + 2 * k)];
                 rw[fn % (2 * FPR)][4 * hf + 2 * k + 1] = base[8 * (4 * hf + 2 * k + 1)];
               }
-#ifdef CN_ABL_NOSPLIT
-              if (k == 0 && false) {
-#else
               if (k == 0) {
-#endif
                 split3_s0<false>(SA[u], v[4 * hf], v[4 * hf + 1], pl[set ^ 1][f], 2 * hf);
                 split3_s0<false>(SB[u], v[4 * hf + 2], v[4 * hf + 3], pl[set ^ 1][f], 2 * hf + 1);
               }
-#ifndef CN_ABL_NOSPLIT
               if (k == 1 || k == 3) split3_residual(SA[u]);
               if (k == 2 || k == 4) split3_residual(SB[u]);
               if (k == 2) split3_plane(SA[u], pl[set ^ 1][f], 1, 2 * hf);
               if (k == 3) split3_plane(SB[u], pl[set ^ 1][f], 1, 2 * hf + 1);
               if (k == 4) split3_plane(SA[u], pl[set ^ 1][f], 2, 2 * hf);
-#endif
               if (k == 5) {
-#ifndef CN_ABL_NOSPLIT
                 split3_plane(SB[u], pl[set ^ 1][f], 2, 2 * hf + 1);
-#endif
                 if (BS && f < AN) bsum[f] += (v[4 * hf] + v[4 * hf + 1]) + (v[4 * hf + 2] + v[4 * hf + 3]);
               }
             }
@@ -652,26 +611,7 @@ template <bool MIXED>
 __device__ __forceinline__ void wgrad_kernel_body() {
   extern __shared__ __attribute__((aligned(16))) float lds[];   // [2 buffers][X slab | Y slab]
   WgArgsC& args = *(WgArgsC*)__builtin_amdgcn_kernarg_segment_ptr();
-#ifdef CN_WGRAD_DYN
-  // EXPERIMENT (-DCN_WGRAD_DYN): one resident workgroup per CU pulls virtual block ids from a device counter (first id = blockIdx.x,
-  // then gridDim.x + ticket): the hardware's first-free-CU balance without the workgroup hand-over (LDS release, dispatch, kernarg
-  // loads).  The next ticket is requested at the START of a job (the atomic's round trip hides behind the job) and published to
-  // the other waves through the LDS word in front of the DMA dummy block at its end.
-  volatile int* tick = (volatile int*)(lds + LDS_FLOATS);
-  int vb = (int)blockIdx.x;
-  for (;;) {
-    int nxt = 0;
-    if (threadIdx.x == 0) nxt = (int)gridDim.x + atomicAdd(args.counter, 1);
-    wgrad_one<MIXED>(args, lds, vb);
-    if (threadIdx.x == 0) *tick = nxt;
-    __syncthreads();
-    vb = __builtin_amdgcn_readfirstlane(*tick);
-    __syncthreads();
-    if (vb >= args.total) break;
-  }
-#else
   wgrad_one<MIXED>(args, lds, (int)blockIdx.x);
-#endif
 }
 
 __global__ __launch_bounds__(64 * NWAVES) void wgrad_k(WgArgs a_by_value) {
@@ -802,19 +742,17 @@ bool add_net_jobs(const NetGeom& g, int netidx, const float* stash, const float*
     for (int gn = 1; gn <= NWAVES; gn *= 2) {
       const int gk = NWAVES / gn;
       const int an = (ntn + gn - 1) / gn, ak = (ntk + gk - 1) / gk;
-      if (an > 4 || ak > 4 || an * ak > 64 / NWAVES) continue;   // <= 256 accumulator registers per wave (128 at 8 waves)
+      if (an > 4 || ak > 4 || an * ak > 64 / NWAVES) continue;   // <= 256 accumulator registers per wave
       const int cost = an * ak * 16 + an + ak;
       if (cost < best_cost) { best_cost = cost; best_gk = gk; best_an = an; best_ak = ak; }
     }
     if (best_gk == 0 || best_an == 3 || best_ak == 3 || ntn > 8 || ntk > 8 || nj >= MAX_WG_JOBS) { ok = false; return; }
     // the opt-in bf16x3 body takes the wide GEMMs (>= 8 tiles per wave: 86 % of the MACs at D=8/W=256) whose two slab buffers
     // fit the LDS; the narrow ones (heads, gamma columns) stay exact fp32 in the same grid
-    // (round 5: the 2 x 2 jobs — the two 256 x 63 GEMMs of the encoding columns, 62 % of the narrow GEMMs' CU time — CAN take the
-    //  bf16x3 body (CNERF_BF3_NARROW=1).  Measured level: wgrad 5.97-6.01 ms with, 5.98-6.06 without (profiles/r05_bf3_narrow_ab.txt):
-    //  with two slab buffers these short jobs wait for their DMA whatever the arithmetic.  Default off: they stay exact fp32.)
-    static const bool narrow22 = getenv("CNERF_BF3_NARROW") && atoi(getenv("CNERF_BF3_NARROW")) != 0;
-    const bool wide = (best_an == 4 && best_ak == 4) || (best_an == 4 && best_ak == 2) || (best_an == 2 && best_ak == 4) ||
-                      (narrow22 && best_an == 2 && best_ak == 2);
+    // (round 5: the 2 x 2 jobs — the two 256 x 63 GEMMs of the encoding columns, 62 % of the narrow GEMMs' CU time — were run on
+    //  the bf16x3 body too.  Measured level: wgrad 5.97-6.01 ms with, 5.98-6.06 without (profiles/r05_bf3_narrow_ab.txt): with
+    //  two slab buffers these short jobs wait for their DMA whatever the arithmetic.  They stay exact fp32.)
+    const bool wide = (best_an == 4 && best_ak == 4) || (best_an == 4 && best_ak == 2) || (best_an == 2 && best_ak == 4);
     const bool fits = 2 * (4 * ntn + 4 * ntk) * OCTF <= LDS_FLOATS;
     a.job[nj++] = WgJob{netidx, xcol, ycol, N, K, n_lo, tensor, ld, col0, bias_tensor, best_gk ? best_gk : 2, best_an,
                         best_ak, 1, 0, 0, (bf3 && wide && fits) ? 1 : 0};
@@ -845,15 +783,6 @@ bool add_net_jobs(const NetGeom& g, int netidx, const float* stash, const float*
   return ok;
 }
 
-// CNERF_WGRAD_NSPLIT="a" or "a,b": tuning knob (scripts/kbench_pair.py) — every GEMM of network 0 (and 1) gets exactly a (b) ranges
-void forced_counts(int* f) {
-  f[0] = f[1] = 0;
-  if (const char* e = getenv("CNERF_WGRAD_NSPLIT")) {
-    f[0] = f[1] = atoi(e);
-    if (const char* c = strchr(e, ',')) f[1] = atoi(c + 1);
-  }
-}
-
 // ---- how many point ranges each GEMM gets -------------------------------------------------------------------------------
 // A workgroup occupies a whole CU (160 KiB of LDS) for (its range's slabs) x (its GEMM's time per slab: 1024 cycles per 32x32
 // tile of the busiest wave + ~560 of barrier — measured 17000-17220 / 8830-8920 / 4705-4860 / 2563-2582 / 1540-1680 cycles
@@ -872,13 +801,10 @@ void forced_counts(int* f) {
 // launches (bit-identical gradients, tests), and every GEMM of a network shares it (GEMMs that write columns of one parameter
 // tensor must: one reduction per tensor).
 void plan_ranges(WgArgs& a, int nj, const int* cap, int* ns_out) {
-  int forced[2];
-  forced_counts(forced);
   for (int i = 0; i < nj; ++i) {
     const int net = a.job[i].net;
     const int64_t slabs = a.net[net].Mp / TM;
     int v = slabs >= 3072 ? 64 : (slabs >= 512 ? 32 : (int)(slabs / 16));
-    if (forced[0] > 0) v = forced[net] > 0 ? forced[net] : forced[0];
     const int64_t vmin = (slabs * TM + 98303) / 98304;   // <= 98304 points per range: 32-bit byte offsets of a range's rows
     if (v < vmin) v = (int)vmin;
     if (v > cap[net]) v = cap[net];
@@ -964,25 +890,8 @@ int cn_wgrad_launch_n(int n, const NetGeom* const* g, const float* const* stash,
       return (int)hipGetLastError();
     attr_set[bf3 ? 1 : 0][dev] = true;
   }
-#ifdef CN_WGRAD_DYN
-  static int* tickets[64] = {};
-  static int ncu[64] = {};
-  if (!tickets[dev]) {
-    if (hipMalloc(reinterpret_cast<void**>(&tickets[dev]), 256) != hipSuccess) return (int)hipGetLastError();
-    if (hipDeviceGetAttribute(&ncu[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return (int)hipGetLastError();
-    if (const char* e = getenv("CNERF_WGRAD_DYN_GRID")) ncu[dev] = atoi(e);
-  }
-  if (hipMemsetAsync(tickets[dev], 0, 4, st) != hipSuccess) return (int)hipGetLastError();
-  b.total = first;
-  b.counter = tickets[dev];
-  const int grid = first < ncu[dev] ? first : ncu[dev];
-#else
-  b.total = first;
-  b.counter = nullptr;
-  const int grid = first;
-#endif
-  if (bf3) hipLaunchKernelGGL(wgrad_mixed_k, dim3(grid), dim3(64 * NWAVES), lds_bytes, st, b);
-  else hipLaunchKernelGGL(wgrad_k, dim3(grid), dim3(64 * NWAVES), lds_bytes, st, b);
+  if (bf3) hipLaunchKernelGGL(wgrad_mixed_k, dim3(first), dim3(64 * NWAVES), lds_bytes, st, b);
+  else hipLaunchKernelGGL(wgrad_k, dim3(first), dim3(64 * NWAVES), lds_bytes, st, b);
   CN_CHECK_LAUNCH();
   r.accumulate = accumulate;
   hipLaunchKernelGGL(wgrad_reduce_k, dim3(64, nr), dim3(256), 0, st, r);

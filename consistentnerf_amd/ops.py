@@ -285,10 +285,6 @@ def mlp_forward(spec: NetSpec, packed: Tensor, B: int, S: int, *, pts: Optional[
 
 
 PRECISION_PLANES = {"bf16": 1, "bf16x2": 2, "bf16x3": 3}
-# which kernels of a bf16x3 training step run in that arithmetic (ablation switches; all on by default)
-import os as _os
-DGRAD_BF3 = _os.environ.get("CNERF_BF3_DGRAD", "1") != "0"
-WGRAD_BF3 = _os.environ.get("CNERF_BF3_WGRAD", "1") != "0"
 
 
 def pack_weights_bf(spec: NetSpec, params: Sequence[Tensor], planes: int, out: Optional[Tensor] = None) -> Tensor:
@@ -352,7 +348,7 @@ def mlp_forward_embedded(spec: NetSpec, packed: Tensor, x: Tensor, want_stash: b
 def mlp_backward(spec: NetSpec, packed: Tensor, d_raw: Tensor, B: int, S: int, stash: Tensor,
                  grads: Optional[List[Tensor]] = None, accumulate: bool = False, packed_bf: Optional[Tensor] = None,
                  live: Optional[Tensor] = None) -> List[Tensor]:
-    """packed_bf (the three-plane buffer of pack_weights_bf): the dgrad runs in the opt-in bf16x3 arithmetic.
+    """packed_bf (the three-plane buffer of pack_weights_bf): the dgrad and wgrad run in the opt-in bf16x3 arithmetic.
     live: the forward ran through mlp_forward(live=...) — the backward stops at the same device-side row count (exact fp32)."""
     lib, net = _lib.load(), spec.c()
     d_raw = _chk(d_raw, "d_raw")
@@ -369,17 +365,17 @@ def mlp_backward(spec: NetSpec, packed: Tensor, d_raw: Tensor, B: int, S: int, s
             _lib.check(lib.cnerf_mlp_bwd_live(C.byref(net), _p(packed), _p(d_raw), B, S, _p(stash), _p(ws), C.byref(ptrs),
                                               int(accumulate), _p(live), _stream()), "cnerf_mlp_bwd_live")
         return grads
-    if packed_bf is not None and DGRAD_BF3:
+    bf = packed_bf is not None
+    if bf:
         with _timed("mlp_dgrad_bf3", B * S):
             _lib.check(lib.cnerf_mlp_dgrad_bf(C.byref(net), _p(packed_bf), _p(d_raw), B, S, _p(stash), _p(ws), _stream()),
                        "cnerf_mlp_dgrad_bf")
     else:
-      with _timed("mlp_dgrad", B * S):
-        _lib.check(lib.cnerf_mlp_dgrad(C.byref(net), _p(packed), _p(d_raw), B, S, _p(stash), _p(ws), _stream()),
-                   "cnerf_mlp_dgrad")
-    bf_w = packed_bf is not None and WGRAD_BF3
-    with _timed("mlp_wgrad_bf3" if bf_w else "mlp_wgrad", B * S):
-        _lib.check((lib.cnerf_mlp_wgrad_bf if bf_w else lib.cnerf_mlp_wgrad)(C.byref(net), B, S, _p(stash), _p(ws), C.byref(ptrs),
+        with _timed("mlp_dgrad", B * S):
+            _lib.check(lib.cnerf_mlp_dgrad(C.byref(net), _p(packed), _p(d_raw), B, S, _p(stash), _p(ws), _stream()),
+                       "cnerf_mlp_dgrad")
+    with _timed("mlp_wgrad_bf3" if bf else "mlp_wgrad", B * S):
+        _lib.check((lib.cnerf_mlp_wgrad_bf if bf else lib.cnerf_mlp_wgrad)(C.byref(net), B, S, _p(stash), _p(ws), C.byref(ptrs),
                                                                              int(accumulate), _stream()), "cnerf_mlp_wgrad")
     return grads
 
@@ -389,8 +385,8 @@ def mlp_backward_pair(spec0: NetSpec, packed0: Tensor, d_raw0: Tensor, B0: int, 
                       accumulate: bool = False, packed_bf0: Optional[Tensor] = None, packed_bf1: Optional[Tensor] = None,
                       live: Optional[Tensor] = None, first0: int = 0, first1: int = 0):
     """cnerf_mlp_bwd_pair: the backward of two independent networks (coarse / fine) as one dgrad grid, one wgrad grid and
-    one reduction; gradients are written (or accumulated) into grads0 / grads1.  packed_bf0 AND packed_bf1: the dgrad grid runs
-    in the opt-in bf16x3 arithmetic.  live: both levels belong to one ray batch whose live row count sits on the device
+    one reduction; gradients are written (or accumulated) into grads0 / grads1.  packed_bf0 AND packed_bf1: the dgrad and wgrad
+    grids run in the opt-in bf16x3 arithmetic.  live: both levels belong to one ray batch whose live row count sits on the device
     (mlp_forward(live=...)): cnerf_mlp_bwd_pair_live (exact fp32); first0 / first1: that level's first rays carry zero seeds and are
     left out of its backward."""
     lib = _lib.load()
@@ -414,19 +410,19 @@ def mlp_backward_pair(spec0: NetSpec, packed0: Tensor, d_raw0: Tensor, B0: int, 
                                                      _p(stash1), _p(ws1), C.byref(p1), int(accumulate), _p(live), int(first0),
                                                      int(first1), _stream()), "cnerf_mlp_wgrad_pair_live")
         return
-    if packed_bf0 is not None and packed_bf1 is not None and DGRAD_BF3:
+    bf = packed_bf0 is not None and packed_bf1 is not None
+    if bf:
         with _timed("mlp_dgrad_bf3", B0 * S0 + B1 * S1):
             _lib.check(lib.cnerf_mlp_dgrad_bf_pair(C.byref(n0), _p(packed_bf0), _p(d_raw0), B0, S0, _p(stash0), _p(ws0),
                                                    C.byref(n1), _p(packed_bf1), _p(d_raw1), B1, S1, _p(stash1), _p(ws1), _stream()),
                        "cnerf_mlp_dgrad_bf_pair")
     else:
-      with _timed("mlp_dgrad", B0 * S0 + B1 * S1):
-        _lib.check(lib.cnerf_mlp_dgrad_pair(C.byref(n0), _p(packed0), _p(d_raw0), B0, S0, _p(stash0), _p(ws0),
-                                            C.byref(n1), _p(packed1), _p(d_raw1), B1, S1, _p(stash1), _p(ws1), _stream()),
-                   "cnerf_mlp_dgrad_pair")
-    bf_w = packed_bf0 is not None and packed_bf1 is not None and WGRAD_BF3
-    with _timed("mlp_wgrad_bf3" if bf_w else "mlp_wgrad", B0 * S0 + B1 * S1):
-        _lib.check((lib.cnerf_mlp_wgrad_bf_pair if bf_w else lib.cnerf_mlp_wgrad_pair)(
+        with _timed("mlp_dgrad", B0 * S0 + B1 * S1):
+            _lib.check(lib.cnerf_mlp_dgrad_pair(C.byref(n0), _p(packed0), _p(d_raw0), B0, S0, _p(stash0), _p(ws0),
+                                                C.byref(n1), _p(packed1), _p(d_raw1), B1, S1, _p(stash1), _p(ws1), _stream()),
+                       "cnerf_mlp_dgrad_pair")
+    with _timed("mlp_wgrad_bf3" if bf else "mlp_wgrad", B0 * S0 + B1 * S1):
+        _lib.check((lib.cnerf_mlp_wgrad_bf_pair if bf else lib.cnerf_mlp_wgrad_pair)(
             C.byref(n0), B0, S0, _p(stash0), _p(ws0), C.byref(p0), C.byref(n1), B1, S1, _p(stash1), _p(ws1), C.byref(p1),
             int(accumulate), _stream()), "cnerf_mlp_wgrad_pair")
 

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Micro-bench of the merged coarse+fine backward (GPU box): cnerf_mlp_dgrad_pair and cnerf_mlp_wgrad_pair at B rays
-(fine 192 + coarse 64 samples), HIP events.  usage: python scripts/kbench_pair.py [B] [reps]
-CNERF_WGRAD_NSPLIT=<n> forces one range count for every GEMM (the pre-round-3 behaviour was Mp/4096 capped at 128)."""
+(fine 192 + coarse 64 samples), HIP events.  usage: python scripts/kbench_pair.py [B] [reps]"""
 import ctypes as C
 import os
 import sys
@@ -61,16 +60,7 @@ def main():
     t_wg = timeit(wg)
     M = B * 256
     tf = lambda k, ms, m=M: 2 * MAC[k] * m / (ms * 1e-3) / 1e12  # noqa: E731
-    if len(sys.argv) > 3:     # sweep of forced range counts "a,b" (fine, coarse) in one process
-        res = []
-        for cfg in sys.argv[3:]:
-            os.environ["CNERF_WGRAD_NSPLIT"] = cfg
-            res.append((timeit(wg), cfg))
-        os.environ.pop("CNERF_WGRAD_NSPLIT")
-        print(f"B={B} planned {t_wg:.3f} ms | " + " | ".join(f"{cfg}: {ms:.3f}" for ms, cfg in res))
-        print(f"   best: {min(res)}")
-        return
-    print(f"B={B:5d} nsplit={os.environ.get('CNERF_WGRAD_NSPLIT', 'planned'):>7s} | fwd+stash {t_f[0]:.3f} + {t_f[1]:.3f} ms "
+    print(f"B={B:5d} | fwd+stash {t_f[0]:.3f} + {t_f[1]:.3f} ms "
           f"({tf('fwd', t_f[0], B * 192):.1f} / {tf('fwd', t_f[1], B * 64):.1f} TF) | dgrad pair {t_dg:.3f} ms {tf('dgrad', t_dg):.1f} TF | "
           f"wgrad pair (+reduce) {t_wg:.3f} ms {tf('wgrad', t_wg):.1f} TF", flush=True)
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Prints the point-range plan of the weight-gradient launch (csrc/wgrad.hip::plan_ranges) for a ray batch — no GPU needed.
-usage: python scripts/wgrad_plan.py [rays=512]      (CNERF_WGRAD_NSPLIT="a,b" forces the fine / coarse counts)"""
+usage: python scripts/wgrad_plan.py [rays=512]"""
 import ctypes as C
 import os
 import sys
