@@ -2,9 +2,32 @@
 // bf16x3 dgrad): packed-buffer geometry, the plane split, the MFMA products, and the LDS ring through which the four waves of
 // a workgroup share one panel stream.  See mlp_fwd_bf.hip for the arithmetic and the mapping.
 #pragma once
+#include "cnerf.h"
 #include "mlp_common.hpp"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+// Element type of a plane.  PL_F16 ("fp16x2": two planes, inference only) shares the panel layout, the ring and the k order of
+// the two-plane bf16 form byte for byte; its operands carry exact power-of-two factors so that both planes stay inside fp16's
+// narrow exponent range (the rule and the range it implies: header of mlp_fwd_bf.hip):
+//   packed weights = w * 2^F16_SW                        (pack_bf_k)
+//   encodings      = gamma * 2^F16_SX                    (at the split)
+//   accumulators   = true value * 2^(F16_SW + F16_SX)    (biases are packed with that factor, the heads' weights with its inverse)
+//   activations    = accumulator * 2^-F16_SW             (at the split: the true activation * 2^F16_SX)
+enum { PL_BF16 = 0, PL_F16 = 1 };
+constexpr int F16_SW = 8, F16_SX = 4;
+template <int FMT>
+struct PlaneShift {   // exponent of the factor applied at the split to an encoding / to an accumulator
+  static constexpr int ENC = FMT == PL_F16 ? F16_SX : 0, REG = FMT == PL_F16 ? -F16_SW : 0;
+};
+// `planes` of the C ABI (1, 2, 3, CNERF_PLANES_FP16X2) -> plane count and element type; false: not a mode
+static inline bool bf_mode(int planes, int* NP, int* fmt) {
+  *fmt = planes == CNERF_PLANES_FP16X2 ? PL_F16 : PL_BF16;
+  *NP = planes == CNERF_PLANES_FP16X2 ? 2 : planes;
+  return *NP >= 1 && *NP <= 3;
+}
 
 struct BfGeom {                 // byte offsets into the packed buffer of cnerf_pack_weights_bf
   int64_t p_l0, p_trunk[16], p_skip, p_feat, p_views, p_viewsd;   // bf16 panels [K/16][N/32][NP][2 half-waves][32 lanes][8]
@@ -57,12 +80,26 @@ __device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
 }
 
+constexpr float pow2f(int e) { return e >= 0 ? (float)(1 << e) : 1.f / (float)(1 << -e); }      // |e| < 31
+
 // One register pair -> one dword of every plane (element 2q in the low half, 2q+1 in the high half).
-template <int NP, bool RELU>
+// PL_F16: the pair is first multiplied by 2^SH (exact); h = fp16(x), l = fp16(x - h), and x - h is exact in fp32.  The
+// conversions go through the compiler like the bf16 one: v_cvt_pk_f16_f32 (RNE) and, for the residual, v_cvt_f32_f16.
+template <int NP, bool RELU, int FMT = PL_BF16, int SH = 0>
 __device__ __forceinline__ void split_pair(float x0, float x1, u32x4 (&b)[NP], int q) {
   if (RELU) {   // one v_max each (fmaxf also emits a canonicalising v_max per operand: every VALU slot counts here)
     asm("v_max_f32 %0, 0, %1" : "=v"(x0) : "v"(x0));
     asm("v_max_f32 %0, 0, %1" : "=v"(x1) : "v"(x1));
+  }
+  if constexpr (FMT == PL_F16) {
+    static_assert(NP == 2, "fp16 planes come in pairs");
+    constexpr float sc = pow2f(SH);
+    f32x2 x = {x0 * sc, x1 * sc};
+    const f16x2 h = __builtin_convertvector(x, f16x2);
+    b[0][q] = __builtin_bit_cast(unsigned, h);
+    x = x - __builtin_convertvector(h, f32x2);
+    b[1][q] = __builtin_bit_cast(unsigned, __builtin_convertvector(x, f16x2));
+    return;
   }
   unsigned h = cvt_pk_bf16(x0, x1);
   b[0][q] = h;
@@ -102,26 +139,29 @@ __device__ __forceinline__ void split3_plane(Split3& S, u32x4 (&pl)[3], int p, i
   pl[p][q] = S.h;
 }
 
+template <int FMT = PL_BF16>
 __device__ __forceinline__ f32x16 mfma_bf(const u32x4& a, const u32x4& b, const f32x16& c) {
+  if constexpr (FMT == PL_F16)
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
 // the NP (NP + 1) / 2 cross terms w_i x_j with i + j < NP, smallest first
-template <int NP>
+template <int NP, int FMT = PL_BF16>
 __device__ __forceinline__ void products(f32x16& q, const u32x4 (&a)[NP], const u32x4 (&b)[NP]) {
 #pragma unroll
   for (int sum = NP - 1; sum >= 0; --sum)
 #pragma unroll
-    for (int i = 0; i <= sum; ++i) q = mfma_bf(a[i], b[sum - i], q);
+    for (int i = 0; i <= sum; ++i) q = mfma_bf<FMT>(a[i], b[sum - i], q);
 }
 // the same, starting the accumulation (C = 0 for the first product)
-template <int NP>
+template <int NP, int FMT = PL_BF16>
 __device__ __forceinline__ void products_init(f32x16& q, const u32x4 (&a)[NP], const u32x4 (&b)[NP]) {
   const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int sum = NP - 1; sum >= 0; --sum)
 #pragma unroll
-    for (int i = 0; i <= sum; ++i) q = mfma_bf(a[i], b[sum - i], (sum == NP - 1 && i == 0) ? z : q);
+    for (int i = 0; i <= sum; ++i) q = mfma_bf<FMT>(a[i], b[sum - i], (sum == NP - 1 && i == 0) ? z : q);
 }
 
 struct BfPanel {
@@ -305,11 +345,14 @@ __device__ __forceinline__ void gemm_ring_reg3(f32x16 (&Q)[NTO], const f32x16 (&
   }
 }
 
-template <int NTI, int NTO, int NT, int NP, bool RELU, class Side = NoStash, int SIDE_OPS = 0, bool INIT = false, bool PAIR = true>
+template <int NTI, int NTO, int NT, int NP, bool RELU, class Side = NoStash, int SIDE_OPS = 0, bool INIT = false, bool PAIR = true,
+          int FMT = PL_BF16>
 __device__ __forceinline__ void gemm_ring_reg(f32x16 (&Q)[NTO], const f32x16 (&X)[NTI], const Ring<NT, NP>& R, int poff,
                                               int poff_next, Side side = Side()) {
   // SIDE_OPS = vector-memory instructions `side` issues per K-step: they sit in the in-order vmcnt queue between this step's
   // DMA pieces, so the publish may leave that many more operations outstanding
+  constexpr int SH = PlaneShift<FMT>::REG;
+  static_assert(FMT == PL_BF16 || NP == 2, "fp16 planes come in pairs");
   if constexpr (NP == 3 && NTO >= 4) {       // (the two-tile view GEMM of a W = 128 network keeps the plain schedule below)
     gemm_ring_reg3<NTI, NTO, NT, RELU, Side, SIDE_OPS, INIT, PAIR>(Q, X, R, poff, poff_next, side);
   } else {
@@ -317,7 +360,7 @@ __device__ __forceinline__ void gemm_ring_reg(f32x16 (&Q)[NTO], const f32x16 (&X
     static_assert(KS % 4 == 0, "ring slot continuity");
     u32x4 bc[NP], bn[NP];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) split_pair<NP, RELU>(X[0][2 * q], X[0][2 * q + 1], bc, q);
+    for (int q = 0; q < 4; ++q) split_pair<NP, RELU, FMT, SH>(X[0][2 * q], X[0][2 * q + 1], bc, q);
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
       u32x4 A[3][NP];       // A operands run two tiles ahead of the MFMAs that consume them (LDS latency)
@@ -333,8 +376,8 @@ __device__ __forceinline__ void gemm_ring_reg(f32x16 (&Q)[NTO], const f32x16 (&X
 #pragma unroll
           for (int p = 0; p < NP; ++p) A[(t + 2) % 3][p] = R.a(s & 3, t + 2, p);
         }
-        if (INIT && s == 0) products_init<NP>(Q[t], A[t % 3], bc);
-        else products<NP>(Q[t], A[t % 3], bc);
+        if (INIT && s == 0) products_init<NP, FMT>(Q[t], A[t % 3], bc);
+        else products<NP, FMT>(Q[t], A[t % 3], bc);
         // the DMA of K-step s+2, one piece behind each tile's MFMAs (all of them in front would delay the first LDS reads)
 #pragma unroll
         for (int j = t; j < Ring<NT, NP>::PW; j += NTO) {
@@ -343,7 +386,7 @@ __device__ __forceinline__ void gemm_ring_reg(f32x16 (&Q)[NTO], const f32x16 (&X
         }
         if (s + 1 < KS && t < 4) {
           const int sn = s + 1;
-          split_pair<NP, RELU>(X[sn >> 1][8 * (sn & 1) + 2 * t], X[sn >> 1][8 * (sn & 1) + 2 * t + 1], bn, t);
+          split_pair<NP, RELU, FMT, SH>(X[sn >> 1][8 * (sn & 1) + 2 * t], X[sn >> 1][8 * (sn & 1) + 2 * t + 1], bn, t);
         }
         side(s, t);
         __builtin_amdgcn_sched_barrier(0);
@@ -352,7 +395,7 @@ __device__ __forceinline__ void gemm_ring_reg(f32x16 (&Q)[NTO], const f32x16 (&X
 #pragma unroll
         for (int q = NTO; q < 4; ++q) {
           const int sn = s + 1;
-          split_pair<NP, RELU>(X[sn >> 1][8 * (sn & 1) + 2 * q], X[sn >> 1][8 * (sn & 1) + 2 * q + 1], bn, q);
+          split_pair<NP, RELU, FMT, SH>(X[sn >> 1][8 * (sn & 1) + 2 * q], X[sn >> 1][8 * (sn & 1) + 2 * q + 1], bn, q);
         }
       }
 #pragma unroll
@@ -435,9 +478,10 @@ __device__ __forceinline__ void gemm_ring_lds3(f32x16 (&Q)[NTO], const float* T,
   }
 }
 
-template <int KS, int NTO, int NT, int NP, bool STAGED = true>
+template <int KS, int NTO, int NT, int NP, bool STAGED = true, int FMT = PL_BF16>
 __device__ __forceinline__ void gemm_ring_lds(f32x16 (&Q)[NTO], const float* T, const Ring<NT, NP>& R, int poff, int poff_next,
                                               int m, int hh) {
+  static_assert(FMT == PL_BF16 || NP == 2, "fp16 planes come in pairs");
   if constexpr (NP == 3 && STAGED) {
     gemm_ring_lds3<KS, NTO, NT>(Q, T, R, poff, poff_next, m, hh);
   } else {
@@ -449,16 +493,16 @@ __device__ __forceinline__ void gemm_ring_lds(f32x16 (&Q)[NTO], const float* T, 
       const f32x4 c0 = *reinterpret_cast<const f32x4*>(T + enc_off(m, 4 * s + 2 * hh));
       const f32x4 c1 = *reinterpret_cast<const f32x4*>(T + enc_off(m, 4 * s + 2 * hh + 1));
       u32x4 b[NP];
-      split_pair<NP, false>(c0[0], c0[1], b, 0);
-      split_pair<NP, false>(c0[2], c0[3], b, 1);
-      split_pair<NP, false>(c1[0], c1[1], b, 2);
-      split_pair<NP, false>(c1[2], c1[3], b, 3);
+      split_pair<NP, false, FMT, PlaneShift<FMT>::ENC>(c0[0], c0[1], b, 0);
+      split_pair<NP, false, FMT, PlaneShift<FMT>::ENC>(c0[2], c0[3], b, 1);
+      split_pair<NP, false, FMT, PlaneShift<FMT>::ENC>(c1[0], c1[1], b, 2);
+      split_pair<NP, false, FMT, PlaneShift<FMT>::ENC>(c1[2], c1[3], b, 3);
 #pragma unroll
       for (int t = 0; t < NTO; ++t) {
         u32x4 A[NP];
 #pragma unroll
         for (int p = 0; p < NP; ++p) A[p] = R.a(s & 3, t, p);
-        products<NP>(Q[t], A, b);
+        products<NP, FMT>(Q[t], A, b);
       }
       if (s + 2 < KS || poff_next >= 0) R.template publish<PW>();
       else R.template publish<0>();

@@ -8,6 +8,28 @@
 //     NP = 3  "bf16x3":        + w0 x2 + w1 x1 + w2 x0  (6 of the 9 cross terms) ~2^-23, i.e. fp32-like
 // Positional encodings, biases, the sigma / rgb heads and the accumulators stay fp32.
 //
+// "fp16x2" (PL_F16, inference only; the kernels' MODE = CNERF_PLANES_FP16X2): the two-plane form on v_mfma_f32_32x32x16_f16.  An
+// fp16 plane carries 11 significand bits, so x = h + l with h = fp16(x), l = fp16(x - h) carries 22 and the three products
+// w_h x_h + w_h x_l + w_l x_h reach the bf16x3 tier at the MFMA count, panel bytes and ring traffic of bf16x2 — the ring, the DMA,
+// the panel layout and the k order are the two-plane bf16 ones, unchanged.  fp16 has 5 exponent bits (normal range 2^-14 ..
+// 65504), so every operand carries an EXACT power-of-two factor (mlp_bf_common.hpp: F16_SW = 8, F16_SX = 4), chosen so that the
+// result does not depend on the matrix pipe honouring fp16 subnormals:
+//     weights      packed as planes of w * 2^8                       biases packed * 2^12, sigma / rgb head weights * 2^-12
+//     encodings    split as planes of gamma * 2^4
+//     accumulators hold 2^12 * (the true pre-activation), fp32       (fp32 range: no concern)
+//     activations  split as planes of relu(acc) * 2^-8 = 2^4 * (the true activation); the heads read acc with their pre-scaled
+//                  weights on the VALU in fp32, their biases are unscaled: raw comes out in true units
+// All factors are powers of two: apart from the two fp16 roundings of the split the arithmetic is that of the unscaled network.
+// RANGE the rule implies (conversion to fp16 stays finite inside it):  |w| < 2^8 (65504 / 2^8 = 255.8) for every GEMM weight;
+// |gamma(x)| <= max(1, |x_i|) < 4094, i.e. sample positions |x_i| < 4094; every hidden activation and feature |a| < 4094
+// (65504 / 2^4).  Resolution: an operand keeps 22 bits down to 2^-3 in scaled units (|w| >= 2^-11, |a| >= 2^-7); below that its
+// low plane is an fp16 subnormal and keeps absolute steps of 2^-24 scaled if the pipe honours subnormals, and is dropped if it
+// flushes them — an absolute error of at most 2^-14 scaled = 2^-22 per weight, 2^-18 per activation, which is what the CPU
+// restatement (tests/test_fp16x2_cpu.py, worst case "flush") bounds end to end.
+// OUTSIDE the range a conversion overflows to fp16 infinity and the accumulators of that point take inf / NaN; the following
+// ReLU (v_max_f32) turns NaN into 0, so the caller may see non-finite OR finite-but-wrong raw values for the affected points
+// (every point, when it is a weight that is out of range).  Nothing detects this: networks that can leave the range use bf16x3.
+//
 // Mapping: as mlp_fwd.hip — one wave64 owns 32 points and walks them through the whole network, every layer computed
 // transposed (Out^T = W . H^T), hidden activations never leave the register file.  The C layout of a 32x32 MFMA tile
 // (lane = point m + 32 hh, register r <-> feature 8(r>>2) + 4hh + (r&3)) is turned into the bf16 B operand of the next
@@ -17,6 +39,7 @@
 // runs on the VALU one register pair at a time in the gaps between MFMAs (v_cvt_pk_bf16_f32 + shift/and + sub).
 // Bound: with the weights streamed per wave from L2 the kernel needs 16 B/clk/wave at NP = 2, 3 — the L2->CU limit
 // (64 B/clk/CU) — so it is weight-stream-bound before it is MFMA-bound; sharing the panels through LDS is the next step.
+#include <math.h>
 #include <stdlib.h>
 
 #include "encode.hpp"
@@ -43,8 +66,13 @@ struct BfPackJob {
                            //                                        column col0 + r, contracted index k = source row
   int64_t dst;             // byte offset
 };
-struct BfCopyJob { const float* src; int n; int64_t dst; };
-struct BfPackArgs { BfPackJob job[48]; BfCopyJob cp[24]; int njobs, ncopies, NP; unsigned char* out; };
+struct BfCopyJob { const float* src; int n; float scale; int64_t dst; };      // scale: a power of two (1 for the bf16 modes)
+struct BfPackArgs { BfPackJob job[48]; BfCopyJob cp[24]; int njobs, ncopies, NP, fmt; unsigned char* out; };
+
+__device__ __forceinline__ unsigned f16_rne(float x) {    // round-to-nearest-even fp16 (v_cvt_f16_f32), as 16 bits
+  return __builtin_bit_cast(unsigned short, (_Float16)x);
+}
+__device__ __forceinline__ float f16_value(unsigned h) { return (float)__builtin_bit_cast(_Float16, (unsigned short)h); }
 
 __global__ void pack_bf_k(BfPackArgs a_by_value) {
   (void)a_by_value;   // job table read in place from the kernarg segment (a by-value copy indexed by blockIdx.y lives in scratch)
@@ -52,7 +80,7 @@ __global__ void pack_bf_k(BfPackArgs a_by_value) {
   if ((int)blockIdx.y >= a.njobs) {
     const __attribute__((address_space(4))) BfCopyJob& c = a.cp[blockIdx.y - a.njobs];
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < c.n; i += gridDim.x * blockDim.x)
-      reinterpret_cast<float*>(a.out + c.dst)[i] = c.src[i];
+      reinterpret_cast<float*>(a.out + c.dst)[i] = c.src[i] * c.scale;      // (x * 1.0f keeps the bits of every finite x)
     return;
   }
   const __attribute__((address_space(4))) BfPackJob& j = a.job[blockIdx.y];
@@ -66,13 +94,15 @@ __global__ void pack_bf_k(BfPackArgs a_by_value) {
     float w = 0.f;
     if (k < j.K && row < j.N) w = j.kind == 2 ? j.src[(int64_t)k * j.ld + j.col0 + row] : j.src[(int64_t)row * j.ld + j.col0 + k];
     unsigned short* dst = reinterpret_cast<unsigned short*>(a.out + j.dst);
+    const bool f16 = a.fmt == PL_F16;
+    if (f16) w = w * (float)(1 << F16_SW);                       // exact; the planes below split the scaled weight
     for (int p = 0; p < NP; ++p) {
-      const unsigned h = bf16_rne(w);
+      const unsigned h = f16 ? f16_rne(w) : bf16_rne(w);
       // piece layout [hh][i][e]: lane (i, hh) = lane 32 hh + i reads its 16 bytes at lane * 16 — consecutive lanes, consecutive
       // 16-byte chunks (with [i][hh] the lanes of a half-wave sat 32 bytes apart: a 2-way LDS bank conflict on every ds_read_b128
       // of the ring, SQ_LDS_BANK_CONFLICT = 50 % of the active LDS cycles)
       dst[((((int64_t)(s * NTO + to) * NP + p) * 2 + hh) * 32 + i) * 8 + e] = (unsigned short)h;
-      w = w - __uint_as_float(h << 16);                          // exact: what this plane left over
+      w = w - (f16 ? f16_value(h) : __uint_as_float(h << 16));   // exact: what this plane left over
     }
   }
 }
@@ -108,7 +138,7 @@ struct ASets { static constexpr int N = NP == 1 ? 4 : (NP == 2 ? 2 : 1); };
 
 // Q[t] += Panel . relu?(X) for the K = 32 NTI features held in C-layout registers X.  A-operand register sets: set
 // s % NSET holds K-step s and is refilled in place with K-step s + NSET behind its last use.
-template <int NTI, int NTO, int NP, bool RELU, int NTM>
+template <int NTI, int NTO, int NP, bool RELU, int NTM, int FMT = PL_BF16>
 __device__ __forceinline__ void gemm_bf_reg(f32x16 (&Q)[NTO], const f32x16 (&X)[NTI], const BfPanel& P, int poff) {
   constexpr int KS = 2 * NTI, NSET = ASets<NP>::N;
   u32x4 A[NSET][NTO][NP];
@@ -116,7 +146,7 @@ __device__ __forceinline__ void gemm_bf_reg(f32x16 (&Q)[NTO], const f32x16 (&X)[
   for (int s = 0; s < NSET && s < KS; ++s) a_fetch<NTO, NP, NTM>(A[s], P, poff, s);
   u32x4 bc[NP], bn[NP];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) split_pair<NP, RELU>(X[0][2 * q], X[0][2 * q + 1], bc, q);
+  for (int q = 0; q < 4; ++q) split_pair<NP, RELU, FMT, PlaneShift<FMT>::REG>(X[0][2 * q], X[0][2 * q + 1], bc, q);
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
@@ -124,7 +154,7 @@ __device__ __forceinline__ void gemm_bf_reg(f32x16 (&Q)[NTO], const f32x16 (&X)[
     // product-major — no two consecutive MFMAs on one accumulator — measured 15 % SLOWER: more operands live, a read burst)
 #pragma unroll
     for (int t = 0; t < NTO; ++t) {
-      products<NP>(Q[t], A[s % NSET][t], bc);
+      products<NP, FMT>(Q[t], A[s % NSET][t], bc);
       if (s + NSET < KS) {
 #pragma unroll
         for (int p = 0; p < NP; ++p)
@@ -133,7 +163,7 @@ __device__ __forceinline__ void gemm_bf_reg(f32x16 (&Q)[NTO], const f32x16 (&X)[
       // the next K-step's B planes, one register pair behind each of the first four tiles' MFMAs
       if (s + 1 < KS && t < 4) {
         const int sn = s + 1;
-        split_pair<NP, RELU>(X[sn >> 1][8 * (sn & 1) + 2 * t], X[sn >> 1][8 * (sn & 1) + 2 * t + 1], bn, t);
+        split_pair<NP, RELU, FMT, PlaneShift<FMT>::REG>(X[sn >> 1][8 * (sn & 1) + 2 * t], X[sn >> 1][8 * (sn & 1) + 2 * t + 1], bn, t);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -141,7 +171,7 @@ __device__ __forceinline__ void gemm_bf_reg(f32x16 (&Q)[NTO], const f32x16 (&X)[
 #pragma unroll
       for (int q = NTO; q < 4; ++q) {
         const int sn = s + 1;
-        split_pair<NP, RELU>(X[sn >> 1][8 * (sn & 1) + 2 * q], X[sn >> 1][8 * (sn & 1) + 2 * q + 1], bn, q);
+        split_pair<NP, RELU, FMT, PlaneShift<FMT>::REG>(X[sn >> 1][8 * (sn & 1) + 2 * q], X[sn >> 1][8 * (sn & 1) + 2 * q + 1], bn, q);
       }
     }
 #pragma unroll
@@ -151,19 +181,19 @@ __device__ __forceinline__ void gemm_bf_reg(f32x16 (&Q)[NTO], const f32x16 (&X)[
 
 // Q[t] += Panel . T for KS (even) K-steps of 16 channels read from the fp32 encoding tile T (channels 16 s + 8 hh + e);
 // two A-operand sets alternate so that the panel pieces of step s + 1 are in flight under the MFMAs of step s.
-template <int NTO, int NP, int NTM>
+template <int NTO, int NP, int NTM, int FMT = PL_BF16>
 __device__ __forceinline__ void gemm_bf_lds(f32x16 (&Q)[NTO], const float* T, int KS, const BfPanel& P, int poff, int m, int hh) {
   u32x4 A0[NTO][NP], A1[NTO][NP];
   auto step = [&](u32x4 (&A)[NTO][NP], int s) __attribute__((always_inline)) {
     const f32x4 c0 = *reinterpret_cast<const f32x4*>(T + enc_off(m, 4 * s + 2 * hh));
     const f32x4 c1 = *reinterpret_cast<const f32x4*>(T + enc_off(m, 4 * s + 2 * hh + 1));
     u32x4 b[NP];
-    split_pair<NP, false>(c0[0], c0[1], b, 0);
-    split_pair<NP, false>(c0[2], c0[3], b, 1);
-    split_pair<NP, false>(c1[0], c1[1], b, 2);
-    split_pair<NP, false>(c1[2], c1[3], b, 3);
+    split_pair<NP, false, FMT, PlaneShift<FMT>::ENC>(c0[0], c0[1], b, 0);
+    split_pair<NP, false, FMT, PlaneShift<FMT>::ENC>(c0[2], c0[3], b, 1);
+    split_pair<NP, false, FMT, PlaneShift<FMT>::ENC>(c1[0], c1[1], b, 2);
+    split_pair<NP, false, FMT, PlaneShift<FMT>::ENC>(c1[2], c1[3], b, 3);
 #pragma unroll
-    for (int t = 0; t < NTO; ++t) products<NP>(Q[t], A[t], b);
+    for (int t = 0; t < NTO; ++t) products<NP, FMT>(Q[t], A[t], b);
   };
   a_fetch<NTO, NP, NTM>(A0, P, poff, 0);
   for (int s = 0; s < KS; s += 2) {
@@ -178,8 +208,16 @@ __device__ __forceinline__ void gemm_bf_lds(f32x16 (&Q)[NTO], const float* T, in
   }
 }
 
-template <int NT, int NP>
+// MODE: the `planes` value of the C ABI — 1, 2, 3 bf16 planes, or CNERF_PLANES_FP16X2 (two fp16 planes).  (A template
+// parameter of the kernels themselves, so that the bf16 instantiations keep their names and their device code.)
+template <int MODE>
+struct PlaneMode {
+  static constexpr int NP = MODE == CNERF_PLANES_FP16X2 ? 2 : MODE, FMT = MODE == CNERF_PLANES_FP16X2 ? PL_F16 : PL_BF16;
+};
+
+template <int NT, int MODE>
 __global__ __launch_bounds__(64) void mlp_fwd_bf_k(BfArgs args_by_value) {
+  constexpr int NP = PlaneMode<MODE>::NP, FMT = PlaneMode<MODE>::FMT;
   constexpr int W = NT * 32, NTH = NT / 2;
   (void)args_by_value;
   const CN_CONST BfArgs& a = *(const CN_CONST BfArgs*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -218,7 +256,7 @@ __global__ __launch_bounds__(64) void mlp_fwd_bf_k(BfArgs args_by_value) {
   f32x16 X[NT], Y[NT];
   // layer 0: gamma(x) from LDS -> Y
   bias_init<NT>(Y, P, (int)bg.b_trunk[0], hh);
-  gemm_bf_lds<NT, NP, NT>(Y, Tx, g.in_chp / 16, P, (int)bg.p_l0, m, hh);
+  gemm_bf_lds<NT, NP, NT, FMT>(Y, Tx, g.in_chp / 16, P, (int)bg.p_l0, m, hh);
   pin<NT>(Y);
   // trunk layers l = 1..D-1 and feature_linear (l = D): Out = bias + W . relu(In) (+ the gamma(x) segment of the skip layer)
   float sig = 0.f;
@@ -242,11 +280,11 @@ __global__ __launch_bounds__(64) void mlp_fwd_bf_k(BfArgs args_by_value) {
       sig += *reinterpret_cast<const float*>(a.pk + bg.b_alpha);
     }
     // (the feature layer's input is already rectified: max(x, 0) once more is the identity — one GEMM body serves both)
-    gemm_bf_reg<NT, NT, NP, true, NT>(Out, In, P, (int)(l < g.D ? bg.p_trunk[l] : bg.p_feat));
+    gemm_bf_reg<NT, NT, NP, true, NT, FMT>(Out, In, P, (int)(l < g.D ? bg.p_trunk[l] : bg.p_feat));
     {
       if (l == g.skip + 1) {
         pin<NT>(Out);
-        gemm_bf_lds<NT, NP, NT>(Out, Tx, g.in_chp / 16, P, (int)bg.p_skip, m, hh);
+        gemm_bf_lds<NT, NP, NT, FMT>(Out, Tx, g.in_chp / 16, P, (int)bg.p_skip, m, hh);
       }
     }
     pin<NT>(Out);
@@ -263,9 +301,9 @@ __global__ __launch_bounds__(64) void mlp_fwd_bf_k(BfArgs args_by_value) {
   // views_linears (H:120-123) on cat([feature, gamma(d)]): Y (registers, no activation on the feature) + Td (LDS)
   f32x16 V[NTH];
   bias_init<NTH>(V, P, (int)bg.b_views, hh);
-  gemm_bf_reg<NT, NTH, NP, false, NT>(V, Y, P, (int)bg.p_views);
+  gemm_bf_reg<NT, NTH, NP, false, NT, FMT>(V, Y, P, (int)bg.p_views);
   pin<NTH>(V);
-  gemm_bf_lds<NTH, NP, NT>(V, Td, g.dir_chp / 16, P, (int)bg.p_viewsd, m, hh);
+  gemm_bf_lds<NTH, NP, NT, FMT>(V, Td, g.dir_chp / 16, P, (int)bg.p_viewsd, m, hh);
   // rgb_linear (H:125) on relu(V), fp32 on the VALU
   float o[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -285,8 +323,10 @@ __global__ __launch_bounds__(64) void mlp_fwd_bf_k(BfArgs args_by_value) {
   if (hh == 0) buf_store(ors, m * 16, 0, f32x4{o[0] + brgb[0], o[1] + brgb[1], o[2] + brgb[2], sig});
 }
 
-template <int NT, int NP, bool TRAIN>
+template <int NT, int MODE, bool TRAIN>
 __global__ __launch_bounds__(256) void mlp_fwd_bfs_k(BfArgs args_by_value) {
+  constexpr int NP = PlaneMode<MODE>::NP, FMT = PlaneMode<MODE>::FMT;
+  static_assert(!TRAIN || FMT == PL_BF16, "the training forward is the three-plane bf16 arithmetic");
   constexpr int W = NT * 32, NTH = NT / 2;
   constexpr int MD = (NT + 1) / 2, MDV = (NTH + 1) / 2;
   (void)args_by_value;
@@ -356,7 +396,7 @@ __global__ __launch_bounds__(256) void mlp_fwd_bfs_k(BfArgs args_by_value) {
   bias_init<NT>(Y, P, (int)bg.b_trunk[0], hh);
   pin<NT>(Y);                                  // (the bias loads are older than nothing the ring waits for below)
   R.template publish<Ring<NT, NP>::PW>();      // K-step 0 of layer 0 has landed everywhere
-  gemm_ring_lds<4, NT, NT, NP, !TRAIN>(Y, Tx, R, (int)bg.p_l0, (int)(g.D > 1 ? bg.p_trunk[1] : bg.p_feat), m, hh);
+  gemm_ring_lds<4, NT, NT, NP, !TRAIN, FMT>(Y, Tx, R, (int)bg.p_l0, (int)(g.D > 1 ? bg.p_trunk[1] : bg.p_feat), m, hh);
   pin<NT>(Y);
   float sig = 0.f;
   auto layer = [&](f32x16 (&In)[NT], f32x16 (&Out)[NT], int l) __attribute__((always_inline)) {
@@ -393,10 +433,10 @@ __global__ __launch_bounds__(256) void mlp_fwd_bfs_k(BfArgs args_by_value) {
       gemm_ring_reg<NT, NT, NT, NP, false, StashStores<NT>, 2, false, false>(Out, In, R, (int)(l < g.D ? bg.p_trunk[l] : bg.p_feat), nxt,
                                                                              StashStores<NT>{In, srs, svo, tm_col(g.s_h[l - 1])});
     else
-      gemm_ring_reg<NT, NT, NT, NP, true>(Out, In, R, (int)(l < g.D ? bg.p_trunk[l] : bg.p_feat), nxt);
+      gemm_ring_reg<NT, NT, NT, NP, true, NoStash, 0, false, true, FMT>(Out, In, R, (int)(l < g.D ? bg.p_trunk[l] : bg.p_feat), nxt);
     if (skip) {
       pin<NT>(Out);
-      gemm_ring_lds<4, NT, NT, NP, !TRAIN>(Out, Tx, R, (int)bg.p_skip, (int)(l + 1 < g.D ? bg.p_trunk[l + 1] : bg.p_feat), m, hh);
+      gemm_ring_lds<4, NT, NT, NP, !TRAIN, FMT>(Out, Tx, R, (int)bg.p_skip, (int)(l + 1 < g.D ? bg.p_trunk[l + 1] : bg.p_feat), m, hh);
     }
     pin<NT>(Out);
   };
@@ -416,9 +456,9 @@ __global__ __launch_bounds__(256) void mlp_fwd_bfs_k(BfArgs args_by_value) {
     gemm_ring_reg<NT, NTH, NT, NP, false, StashStores<NT>, 2, false, false>(V, Y, R, (int)bg.p_views, (int)bg.p_viewsd,
                                                                             StashStores<NT>{Y, srs, svo, tm_col(g.s_feat)});
   else
-    gemm_ring_reg<NT, NTH, NT, NP, false>(V, Y, R, (int)bg.p_views, (int)bg.p_viewsd);
+    gemm_ring_reg<NT, NTH, NT, NP, false, NoStash, 0, false, true, FMT>(V, Y, R, (int)bg.p_views, (int)bg.p_viewsd);
   pin<NTH>(V);
-  gemm_ring_lds<2, NTH, NT, NP, !TRAIN>(V, Td, R, (int)bg.p_viewsd, -1, m, hh);
+  gemm_ring_lds<2, NTH, NT, NP, !TRAIN, FMT>(V, Td, R, (int)bg.p_viewsd, -1, m, hh);
   if (TRAIN) {
     unsigned bv[MDV];
     relu_bits<NTH, true>(V, bv);
@@ -443,14 +483,14 @@ __global__ __launch_bounds__(256) void mlp_fwd_bfs_k(BfArgs args_by_value) {
   if (hh == 0) buf_store(ors, m * 16, 0, f32x4{o[0] + brgb[0], o[1] + brgb[1], o[2] + brgb[2], sig});
 }
 
-template <int NT, int NP, bool TRAIN>
+template <int NT, int MODE, bool TRAIN>
 int launch_bfs(const BfArgs& a, hipStream_t st) {
-  const size_t lds = (size_t)4 * Ring<NT, NP>::SLOT + 4 * 16384;
+  const size_t lds = (size_t)4 * Ring<NT, PlaneMode<MODE>::NP>::SLOT + 4 * 16384;
   static bool attr_set[64] = {};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return CNERF_E_NODEVICE;
   if (!attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_fwd_bfs_k<NT, NP, TRAIN>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_fwd_bfs_k<NT, MODE, TRAIN>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds) != hipSuccess)
       return (int)hipGetLastError();
     attr_set[dev] = true;
@@ -462,21 +502,29 @@ int launch_bfs(const BfArgs& a, hipStream_t st) {
       if (e != hipSuccess) return (int)e;
     }
   }
-  hipLaunchKernelGGL((mlp_fwd_bfs_k<NT, NP, TRAIN>), dim3((unsigned)cn_div_up(a.M, 128)), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((mlp_fwd_bfs_k<NT, MODE, TRAIN>), dim3((unsigned)cn_div_up(a.M, 128)), dim3(256), lds, st, a);
   CN_CHECK_LAUNCH();
   return CNERF_OK;
 }
 
 template <int NT>
-int launch_bf(const BfArgs& a, int NP, hipStream_t st) {
+int launch_bf(const BfArgs& a, int NP, int fmt, hipStream_t st) {
   // shared-panel kernel by default; the per-wave one on request (CNERF_BF_PERWAVE=1: A/B measurements) or when the
   // encodings are not the 64- / 32-channel tiles its unrolled K-steps assume
   const char* e = getenv("CNERF_BF_PERWAVE");
   if (a.stash != nullptr) {   // training: the shared-panel kernel at three planes (the fp32-equivalent arithmetic) only
-    if (NP != 3 || a.g.in_chp != 64 || a.g.dir_chp != 32) return CNERF_E_UNSUPPORTED;
+    if (NP != 3 || fmt != PL_BF16 || a.g.in_chp != 64 || a.g.dir_chp != 32) return CNERF_E_UNSUPPORTED;
     return launch_bfs<NT, 3, true>(a, st);
   }
-  if (!(e && e[0] == '1') && a.g.in_chp == 64 && a.g.dir_chp == 32) {
+  const bool shared = !(e && e[0] == '1') && a.g.in_chp == 64 && a.g.dir_chp == 32;
+  if (fmt == PL_F16) {        // two fp16 planes: the same choice between the two kernels
+    if (NP != 2) return CNERF_E_ARG;
+    if (shared) return launch_bfs<NT, CNERF_PLANES_FP16X2, false>(a, st);
+    hipLaunchKernelGGL((mlp_fwd_bf_k<NT, CNERF_PLANES_FP16X2>), dim3((unsigned)cn_div_up(a.M, 32)), dim3(64), 0, st, a);
+    CN_CHECK_LAUNCH();
+    return CNERF_OK;
+  }
+  if (shared) {
     switch (NP) {
       case 1: return launch_bfs<NT, 1, false>(a, st);
       case 2: return launch_bfs<NT, 2, false>(a, st);
@@ -500,7 +548,8 @@ int launch_bf(const BfArgs& a, int NP, hipStream_t st) {
 extern "C" int64_t cnerf_packed_bf_bytes(const cnerf_net* net, int planes) {
   NetGeom g;
   BfGeom b;
-  if (cn_make_geom(net, &g) || make_bf_geom(g, planes, &b)) return -1;
+  int NP, fmt;
+  if (cn_make_geom(net, &g) || !bf_mode(planes, &NP, &fmt) || make_bf_geom(g, NP, &b)) return -1;
   return b.total;
 }
 
@@ -510,41 +559,47 @@ extern "C" int cnerf_pack_weights_bf(const cnerf_net* net, const cnerf_ptrs* par
   BfGeom b;
   int rc = cn_make_geom(net, &g);
   if (rc) return rc;
-  if ((rc = make_bf_geom(g, planes, &b))) return rc;
+  int NP, fmt;
+  if (!bf_mode(planes, &NP, &fmt)) return CNERF_E_UNSUPPORTED;
+  if ((rc = make_bf_geom(g, NP, &b))) return rc;
   if (!params || !packed_bf) return CNERF_E_ARG;
   const int nt = cnerf_num_tensors(net);
   for (int i = 0; i < nt; ++i)
     if (!params->p[i]) return CNERF_E_ARG;
   BfPackArgs a;
-  a.njobs = a.ncopies = 0; a.NP = planes; a.out = static_cast<unsigned char*>(packed_bf);
+  a.njobs = a.ncopies = 0; a.NP = NP; a.fmt = fmt; a.out = static_cast<unsigned char*>(packed_bf);
   const int W = g.W, Wh = g.Wh, D = g.D;
   bool overflow = false;
   auto panel = [&](const float* src, int ld, int col0, int N, int K, int Kp, int kind, int64_t dst) {
     if (a.njobs >= 48) { overflow = true; return; }
     a.job[a.njobs++] = BfPackJob{src, ld, col0, N, K, g.NT, Kp, kind, dst};
   };
-  auto copy = [&](const float* src, int n, int64_t dst) { a.cp[a.ncopies++] = BfCopyJob{src, n, dst}; };
+  // PL_F16: the accumulators hold 2^(F16_SW + F16_SX) times the true value (mlp_bf_common.hpp) — the biases added to them carry
+  // that factor (shift +1), the head weights that read them its inverse (-1), the heads' own biases none (0)
+  auto copy = [&](const float* src, int n, int64_t dst, int shift = 0) {
+    a.cp[a.ncopies++] = BfCopyJob{src, n, fmt == PL_F16 ? ldexpf(1.f, shift * (F16_SW + F16_SX)) : 1.f, dst};
+  };
   auto Wt = [&](int l) { return params->p[2 * l]; };
   auto Bt = [&](int l) { return params->p[2 * l + 1]; };
   panel(Wt(0), g.in_ch, 0, W, g.in_ch, g.in_chp, 0, b.p_l0);
-  copy(Bt(0), W, b.b_trunk[0]);
+  copy(Bt(0), W, b.b_trunk[0], 1);
   for (int l = 1; l < D; ++l) {
     const bool sk = g.skip >= 0 && l == g.skip + 1;
     panel(Wt(l), sk ? W + g.in_ch : W, sk ? g.in_ch : 0, W, W, W, 1, b.p_trunk[l]);
     if (sk) panel(Wt(l), W + g.in_ch, 0, W, g.in_ch, g.in_chp, 0, b.p_skip);
-    copy(Bt(l), W, b.b_trunk[l]);
+    copy(Bt(l), W, b.b_trunk[l], 1);
   }
   const int base = 2 * D;
   panel(params->p[base + 2], W, 0, W, W, W, 1, b.p_feat);
-  copy(params->p[base + 3], W, b.b_feat);
+  copy(params->p[base + 3], W, b.b_feat, 1);
   panel(params->p[base + 0], W + g.dir_ch, 0, Wh, W, W, 1, b.p_views);
   panel(params->p[base + 0], W + g.dir_ch, W, Wh, g.dir_ch, g.dir_chp, 0, b.p_viewsd);
-  copy(params->p[base + 1], Wh, b.b_views);
-  copy(params->p[base + 4], W, b.v_alpha);
+  copy(params->p[base + 1], Wh, b.b_views, 1);
+  copy(params->p[base + 4], W, b.v_alpha, -1);
   copy(params->p[base + 5], 1, b.b_alpha);
-  copy(params->p[base + 6], 3 * Wh, b.v_rgb);
+  copy(params->p[base + 6], 3 * Wh, b.v_rgb, -1);
   copy(params->p[base + 7], 3, b.b_rgb);
-  if (planes == 3) {   // the transposed panels of the bf16x3 dgrad (mlp_bwd_bf.hip)
+  if (NP == 3) {   // the transposed panels of the bf16x3 dgrad (mlp_bwd_bf.hip)
     for (int l = 1; l < D; ++l) {
       const bool sk = g.skip >= 0 && l == g.skip + 1;
       panel(Wt(l), sk ? W + g.in_ch : W, sk ? g.in_ch : 0, W, W, W, 2, b.pt_trunk[l]);
@@ -564,7 +619,9 @@ extern "C" int cnerf_mlp_fwd_bf(const cnerf_net* net, const void* packed_bf, int
   BfArgs a;
   int rc = cn_make_geom(net, &a.g);
   if (rc) return rc;
-  if ((rc = make_bf_geom(a.g, planes, &a.b))) return rc;
+  int NP, fmt;
+  if (!bf_mode(planes, &NP, &fmt)) return CNERF_E_UNSUPPORTED;
+  if ((rc = make_bf_geom(a.g, NP, &a.b))) return rc;
   if (!packed_bf || !raw || B < 0 || S <= 0) return CNERF_E_ARG;
   if (!pts && (!rays || !z || ray_stride < 8)) return CNERF_E_ARG;
   if (!dirs && (!rays || ray_stride < 11)) return CNERF_E_ARG;
@@ -574,8 +631,8 @@ extern "C" int cnerf_mlp_fwd_bf(const cnerf_net* net, const void* packed_bf, int
   a.M = B * S; a.S = S; a.rs = ray_stride;
   a.cam = cn_no_raygen();
   switch (a.g.NT) {
-    case 4: return launch_bf<4>(a, planes, cn_stream(stream));
-    case 8: return launch_bf<8>(a, planes, cn_stream(stream));
+    case 4: return launch_bf<4>(a, NP, fmt, cn_stream(stream));
+    case 8: return launch_bf<8>(a, NP, fmt, cn_stream(stream));
   }
   return CNERF_E_UNSUPPORTED;
 }
@@ -596,8 +653,8 @@ extern "C" int cnerf_mlp_fwd_bf_train(const cnerf_net* net, const void* packed_b
   a.M = B * S; a.S = S; a.rs = ray_stride;
   a.cam = cn_no_raygen();
   switch (a.g.NT) {
-    case 4: return launch_bf<4>(a, 3, cn_stream(stream));
-    case 8: return launch_bf<8>(a, 3, cn_stream(stream));
+    case 4: return launch_bf<4>(a, 3, PL_BF16, cn_stream(stream));
+    case 8: return launch_bf<8>(a, 3, PL_BF16, cn_stream(stream));
   }
   return CNERF_E_UNSUPPORTED;
 }

@@ -284,11 +284,21 @@ def mlp_forward(spec: NetSpec, packed: Tensor, B: int, S: int, *, pts: Optional[
     return raw, stash
 
 
-PRECISION_PLANES = {"bf16": 1, "bf16x2": 2, "bf16x3": 3}
+# NeRF.inference_precision -> the `planes` argument of cnerf_packed_bf_bytes / cnerf_pack_weights_bf / cnerf_mlp_fwd_bf
+PLANES_FP16X2 = 18                  # CNERF_PLANES_FP16X2: two fp16 planes per operand, three products on the f16 matrix cores
+PRECISION_PLANES = {"bf16": 1, "bf16x2": 2, "bf16x3": 3, "fp16x2": PLANES_FP16X2}
+# The fp16x2 scale rule (csrc/mlp_bf_common.hpp F16_SW / F16_SX; header of csrc/mlp_fwd_bf.hip): weights are packed as planes of
+# w * 2^FP16X2_WEIGHT_SHIFT, encodings and activations split as planes of x * 2^FP16X2_ACT_SHIFT, so the fp32 accumulators hold
+# 2^(sum) times the true value; biases are packed with that factor and the sigma / rgb head weights with its inverse.
+FP16X2_WEIGHT_SHIFT, FP16X2_ACT_SHIFT = 8, 4
+FP16X2_MAX_WEIGHT = 65504.0 / 2 ** FP16X2_WEIGHT_SHIFT       # |w| above this overflows the fp16 plane
+FP16X2_MAX_ACTIVATION = 65504.0 / 2 ** FP16X2_ACT_SHIFT      # likewise sample positions, hidden activations and features
+_BF_PROFILE = {1: "mlp_fwd_bf1", 2: "mlp_fwd_bf2", 3: "mlp_fwd_bf3", PLANES_FP16X2: "mlp_fwd_fp16x2"}
 
 
 def pack_weights_bf(spec: NetSpec, params: Sequence[Tensor], planes: int, out: Optional[Tensor] = None) -> Tensor:
-    """cnerf_pack_weights_bf: the bf16-plane panels of the opt-in reduced-precision inference forward (a byte buffer)."""
+    """cnerf_pack_weights_bf: the bf16-plane (planes = 1, 2, 3) or fp16-plane (PLANES_FP16X2) panels of the opt-in
+    reduced-precision inference forward (a byte buffer).  One launch, no host synchronisation: capturable."""
     lib, net = _lib.load(), spec.c()
     params = [_chk(p, f"param{i}") for i, p in enumerate(params)]
     n = lib.cnerf_packed_bf_bytes(C.byref(net), int(planes))
@@ -303,12 +313,12 @@ def pack_weights_bf(spec: NetSpec, params: Sequence[Tensor], planes: int, out: O
 
 def mlp_forward_bf(spec: NetSpec, packed_bf: Tensor, planes: int, B: int, S: int, *, pts: Optional[Tensor] = None,
                    rays: Optional[Tensor] = None, z: Optional[Tensor] = None, dirs: Optional[Tensor] = None) -> Tensor:
-    """cnerf_mlp_fwd_bf: inference forward on the bf16 matrix cores (opt-in)."""
+    """cnerf_mlp_fwd_bf: inference forward on the bf16 / f16 matrix cores (opt-in); `planes` as packed."""
     lib, net = _lib.load(), spec.c()
     pts, rays, z, dirs = _chk(pts, "pts"), _chk(rays, "rays"), _chk(z, "z"), _chk(dirs, "dirs")
     raw = torch.empty(B, S, spec.raw_ch, device=packed_bf.device, dtype=torch.float32)
     rs = rays.shape[1] if rays is not None else 0
-    with _timed("mlp_fwd_bf%d" % planes, B * S):
+    with _timed(_BF_PROFILE.get(int(planes), "mlp_fwd_bf%d" % planes), B * S):
         _lib.check(lib.cnerf_mlp_fwd_bf(C.byref(net), _p(packed_bf), int(planes), _p(pts), _p(rays), rs, _p(dirs), _p(z), B, S,
                                         _p(raw), _stream()), "cnerf_mlp_fwd_bf")
     return raw

@@ -93,7 +93,8 @@ def _prepack_pair(model_a, model_b):
 
 
 def _packed_bf_gen(model, planes):
-    """bf16-plane panels of `model` (opt-in reduced-precision forward / the bf16x3 training kernels), re-packed when a parameter
+    """bf16- / fp16-plane panels of `model` (opt-in reduced-precision forward / the bf16x3 training kernels; `planes` = the mode's
+    value in ops.PRECISION_PLANES, distinct per mode), re-packed when a parameter or the mode
     changed.  Same two-buffer / generation protocol as _packed_gen: the copy a training forward used survives ONE optimizer step
     before its backward (forward A, step, forward B, backward A is legal with the fp32 panels, so it is here); a second re-pack
     overwrites it and the backward refuses (_packed_bf_still_valid).  Returns (buffer, generation)."""
@@ -509,8 +510,9 @@ def run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk=1024 * 64
     params = fn.kernel_tensors()
     prec = getattr(fn, "inference_precision", "fp32")
     if prec != "fp32" and not (torch.is_grad_enabled() and any(p.requires_grad for p in params)):
-        # OPT-IN reduced-precision inference (NeRF.inference_precision = "bf16" | "bf16x2" | "bf16x3"): bf16 matrix cores,
-        # fp32 accumulation; never taken when a gradient could be asked for
+        # OPT-IN reduced-precision inference (NeRF.inference_precision = "bf16" | "bf16x2" | "bf16x3" | "fp16x2"): bf16 / f16
+        # matrix cores, fp32 accumulation; never taken when a gradient could be asked for.  `planes` is the mode's code in the
+        # C ABI (fp16x2 has one of its own), which is also what keys the packed-panel cache: a change of mode re-packs
         if prec not in ops.PRECISION_PLANES:
             raise ValueError(f"inference_precision must be fp32 or one of {sorted(ops.PRECISION_PLANES)}")
         planes = ops.PRECISION_PLANES[prec]

@@ -139,7 +139,9 @@ class NeRF(nn.Module):
         return ts
 
     # OPT-IN: "bf16" | "bf16x2" | "bf16x3" run the INFERENCE forward (no autograd graph) on the bf16 matrix cores with the
-    # operands split into 1 / 2 / 3 bf16 planes and fp32 accumulation (csrc/mlp_fwd_bf.hip).  Training and everything
+    # operands split into 1 / 2 / 3 bf16 planes and fp32 accumulation (csrc/mlp_fwd_bf.hip); "fp16x2" runs it on the f16
+    # matrix cores with two fp16 planes per operand: the accuracy tier of bf16x3 at the cost of bf16x2, for weights below 2^8 and
+    # positions / activations below 4094 in magnitude (ops.FP16X2_MAX_WEIGHT / _MAX_ACTIVATION).  Training and everything
     # under autograd always use the exact-fp32 kernels; so does this module unless the attribute is set.
     inference_precision = "fp32"
 

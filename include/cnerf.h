@@ -134,8 +134,15 @@ int cnerf_mlp_fwd_live(const cnerf_net* net, const float* packed, const float* r
  * matrix cores with every operand split into `planes` bf16 terms and fp32 accumulation:
  *   planes = 1 plain bf16 (error per product ~2^-9), 2 "bf16x2": w0x0 + w0x1 + w1x0 (~2^-16), 3 "bf16x3": the 6 cross terms
  *   with i + j < 3 (~2^-23, fp32-like).  Encodings, biases, the sigma / rgb heads and accumulators stay fp32.
+ *   planes = CNERF_PLANES_FP16X2 "fp16x2": two fp16 planes per operand (x = h + l, 22 significand bits), the three products
+ *   w_h x_h + w_h x_l + w_l x_h on the f16 matrix cores: the accuracy tier of bf16x3 at the cost of bf16x2.  Operands carry
+ *   exact power-of-two factors (weights 2^8 when packed, encodings / activations 2^4 at the split), so that fp16 subnormals
+ *   never matter; valid for GEMM weights |w| < 2^8 and sample positions / activations below 4094 in magnitude — outside
+ *   that range raw values may be non-finite or wrong, undetected (csrc/mlp_fwd_bf.hip).  A packed buffer belongs to the
+ *   `planes` value it was packed with.  Every other value of `planes` is rejected (CNERF_E_UNSUPPORTED; -1 from _bytes).
  * Networks with view directions, W in {128, 256}.  packed_bf: cnerf_packed_bf_bytes(net, planes) bytes, filled by
  * cnerf_pack_weights_bf from the same 2D+8 parameter tensors as cnerf_pack_weights. */
+#define CNERF_PLANES_FP16X2 18
 int64_t cnerf_packed_bf_bytes(const cnerf_net* net, int planes);
 int cnerf_pack_weights_bf(const cnerf_net* net, const cnerf_ptrs* params, int planes, void* packed_bf, void* stream);
 int cnerf_mlp_fwd_bf(const cnerf_net* net, const void* packed_bf, int planes, const float* pts, const float* rays,

@@ -14,7 +14,8 @@ help (a join point may be reached from the shorter path).  Usage:  isa_hazards.p
 """
 import re, sys
 
-PASSES = {"v_mfma_f32_32x32x2_f32": 16, "v_mfma_f32_32x32x2f32": 16, "v_mfma_f32_32x32x16_bf16": 8}
+PASSES = {"v_mfma_f32_32x32x2_f32": 16, "v_mfma_f32_32x32x2f32": 16, "v_mfma_f32_32x32x16_bf16": 8,
+          "v_mfma_f32_32x32x16_f16": 8}
 REG = re.compile(r"\b([va])(?:\[(\d+):(\d+)\]|(\d+)\b)")
 
 

@@ -74,6 +74,18 @@ def main():
             print(f"          fwd bf16 x{planes} (inference, opt-in) {t_bf:7.3f} ms = {tf('fwd', t_bf):7.1f} TFLOP/s fp32-equivalent, "
                   f"{t_inf / t_bf:5.2f}x the fp32 kernel  (per-wave panel streaming instead of the shared LDS ring: {t_pw:7.3f} ms)",
                   flush=True)
+        # two fp16 planes per operand on the f16 matrix cores: same shapes, same process, against the bf16 lines above
+        pk = ops.pack_weights_bf(spec, m.kernel_tensors(), ops.PLANES_FP16X2)
+        t_hf = timeit(lambda: ops.mlp_forward_bf(spec, pk, ops.PLANES_FP16X2, B, S, rays=rays, z=z))
+        os.environ["CNERF_BF_PERWAVE"] = "1"
+        t_pw = timeit(lambda: ops.mlp_forward_bf(spec, pk, ops.PLANES_FP16X2, B, S, rays=rays, z=z))
+        del os.environ["CNERF_BF_PERWAVE"]
+        pks = {p_: ops.pack_weights_bf(spec, m.kernel_tensors(), p_) for p_ in (2, 3)}
+        t_b = {p_: timeit(lambda: ops.mlp_forward_bf(spec, pks[p_], p_, B, S, rays=rays, z=z)) for p_ in (2, 3)}
+        t_hf = min(t_hf, timeit(lambda: ops.mlp_forward_bf(spec, pk, ops.PLANES_FP16X2, B, S, rays=rays, z=z)))
+        print(f"          fwd fp16x2 (inference, opt-in) {t_hf:7.3f} ms = {tf('fwd', t_hf):7.1f} TFLOP/s fp32-equivalent, "
+              f"{t_inf / t_hf:5.2f}x the fp32 kernel, {t_hf / t_b[3]:5.2f}x the bf16x3 time, {t_hf / t_b[2]:5.2f}x the bf16x2 time "
+              f"(bf16x2 {t_b[2]:7.3f} ms, bf16x3 {t_b[3]:7.3f} ms re-timed next to it; per-wave panel streaming: {t_pw:7.3f} ms)", flush=True)
         # the opt-in bf16x3 TRAINING forward (same stash): time, and its stash / raw against the fp32 kernel's
         pk3 = ops.pack_weights_bf(spec, m.kernel_tensors(), 3)
         raw3, stash3 = ops.mlp_forward_bf_train(spec, pk3, B, S, rays=rays, z=z)
