@@ -18,6 +18,28 @@ static inline hipStream_t cn_stream(void* s) { return reinterpret_cast<hipStream
 static inline int64_t cn_div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t cn_round_up(int64_t a, int64_t b) { return cn_div_up(a, b) * b; }
 
+// A tile-major [Mp][rows] array (stash, gradient workspace: NetGeom below) whose last 32-point tile row holds padding points
+// (Mp > M): the producing kernel drops their stores and wgrad reads them, so the row is zero-filled in front of the producer.
+static inline hipError_t cn_zero_padding_tile_row(float* a, int64_t M, int64_t Mp, int rows, hipStream_t st) {
+  return Mp > M ? hipMemsetAsync(a + (Mp - 32) * rows, 0, (size_t)32 * rows * sizeof(float), st) : hipSuccess;
+}
+
+// Dynamic LDS beyond 64 KiB is a per-device function attribute: set once per device this process launches `Kernel` on
+// (idempotent, so a race between two host threads only repeats the call).
+template <auto Kernel>
+int cn_lds_opt_in(size_t bytes) {
+  static bool done[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return CNERF_E_NODEVICE;
+  if (!done[dev]) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) !=
+        hipSuccess)
+      return (int)hipGetLastError();
+    done[dev] = true;
+  }
+  return CNERF_OK;
+}
+
 // wave64 helpers (one wavefront = 64 lanes on CDNA4)
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

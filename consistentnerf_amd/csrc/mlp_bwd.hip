@@ -7,17 +7,9 @@
 //   2. wgrad (wgrad.hip): NT GEMMs contracted over points, dW_l = dZ_l^T . H_{l-1}, split over point ranges.
 //   3. a fixed-order reduction of the split partials into the parameter gradients (deterministic).
 // ReLU masks come from the sign-bit words the forward packed into the stash (1 bit per hidden unit, s_mask).
+#include "mlp_bwd_host.hpp"
 #include "mlp_common.hpp"
 #include "timing.hpp"
-
-int cn_wgrad_launch(const NetGeom& g, const float* stash, const float* G, int64_t M, int64_t Mp, float* partials,
-                    int nsplit, const cnerf_ptrs* grads, int accumulate, hipStream_t st, int bf3 = 0);
-int cn_wgrad_launch_n(int n, const NetGeom* const* g, const float* const* stash, const float* const* G, const int64_t* Mp,
-                      float* const* partials, const int* nsplit, const cnerf_ptrs* const* grads, int accumulate,
-                      hipStream_t st, int bf3 = 0, const int* live = nullptr, const int* live_mul = nullptr,
-                      const int* live_sub = nullptr);
-int cn_wgrad_nsplit(int64_t Mp);
-int64_t cn_param_floats(const NetGeom& g);
 
 namespace {
 
@@ -200,10 +192,8 @@ int launch(const BwdArgs& a, int nlev, hipStream_t st) {
   for (int i = 0; i < nlev; ++i) {
     const BwdLevel& L = a.lv[i];
     grid += (unsigned)cn_div_up(L.M, 32);
-    if (L.Mp > L.M) {   // last gradient tile row holds padding points: the kernel drops their stores, wgrad reads them
-      hipError_t e = hipMemsetAsync(L.G + (L.Mp - 32) * a.g.g_rows, 0, (size_t)32 * a.g.g_rows * sizeof(float), st);
-      if (e != hipSuccess) return (int)e;
-    }
+    const hipError_t e = cn_zero_padding_tile_row(L.G, L.M, L.Mp, a.g.g_rows, st);
+    if (e != hipSuccess) return (int)e;
   }
   if (a.g.viewdirs) hipLaunchKernelGGL((mlp_dgrad_k<NT, true>), dim3(grid), dim3(64), 0, st, a);
   else hipLaunchKernelGGL((mlp_dgrad_k<NT, false>), dim3(grid), dim3(64), 0, st, a);
@@ -220,6 +210,129 @@ int dispatch(const BwdArgs& a, int nlev, hipStream_t st) {
   return CNERF_E_UNSUPPORTED;
 }
 
+// ---- the host path of every cnerf_mlp_{bwd,dgrad,wgrad}* entry point ---------------------------------------------------
+// An entry point fills a Call and hands it to run(): validate -> operands -> dgrad and / or wgrad.
+
+// One level as the C ABI passes it: arrays UNSHIFTED, first_ray = rays in front of them that carry zero seeds and are left out.
+struct Level {
+  const cnerf_net* net;
+  const void* packed;        // cnerf_pack_weights floats, or with Call::bf3 cnerf_pack_weights_bf(.., 3, ..) bytes (dgrad)
+  const float* d_raw;        // (dgrad)
+  int64_t B;
+  int S;
+  const float* stash;
+  float* workspace;
+  const cnerf_ptrs* grads;   // (wgrad)
+  int64_t first_ray;
+};
+
+struct Call {
+  Level lv[2];
+  int n;                       // 1, or 2: the coarse and the fine network of a training step (independent once the forward is done)
+  bool live;                   // a _live form: both levels stop at live_rays[0] rays
+  const int32_t* live_rays;    // device
+  int bf3, accumulate;
+  void* stream;
+};
+
+enum { DGRAD = 1, WGRAD = 2 };
+
+bool same_arch(const cnerf_net& a, const cnerf_net& b) {
+  return a.D == b.D && a.W == b.W && a.multires == b.multires && a.multires_views == b.multires_views &&
+         a.use_viewdirs == b.use_viewdirs && a.output_ch == b.output_ch && a.skip == b.skip;
+}
+
+// Every argument rule of the backward, once.  Geometry first (an architecture outside the envelope is CNERF_E_UNSUPPORTED
+// whatever else is wrong with the call), then the arguments (CNERF_E_ARG); an empty level (B == 0) is held to the same rules as
+// any other and then takes no part in a launch.  Fills nets[i].g.
+int validate(const Call& c, int stages, CnBwdNet* nets) {
+  for (int i = 0; i < c.n; ++i) {
+    int rc = cn_make_geom(c.lv[i].net, &nets[i].g);
+    if (rc) return rc;
+    if ((stages & DGRAD) && c.bf3 && (rc = cn_dgrad_bf3_supported(nets[i].g))) return rc;
+  }
+  if (c.live && !c.live_rays) return CNERF_E_ARG;
+  if (c.live && c.bf3) return CNERF_E_UNSUPPORTED;      // (the device-side row count is the exact-fp32 bodies')
+  for (int i = 0; i < c.n; ++i) {
+    const Level& L = c.lv[i];
+    if (!L.stash || !L.workspace || L.B < 0 || L.S <= 0) return CNERF_E_ARG;
+    if ((stages & DGRAD) && (!L.packed || !L.d_raw)) return CNERF_E_ARG;
+    if ((stages & WGRAD) && !L.grads) return CNERF_E_ARG;
+    // tile rows are 32 points: a launch that stops at live * S points or starts at first_ray * S needs whole tiles per ray
+    if (c.live && L.S % 32 != 0) return CNERF_E_ARG;
+    if (L.first_ray && (!c.live || L.first_ray < 0 || L.first_ray >= L.B)) return CNERF_E_ARG;
+  }
+  if (c.n == 2) {
+    if (c.live && c.lv[0].B != c.lv[1].B) return CNERF_E_ARG;      // the two levels of ONE ray batch
+    if (stages & WGRAD)      // one gradient tensor in both sets: two reductions into it would race
+      for (int i = 0; i < CNERF_MAX_TENSORS; ++i)
+        if (c.lv[0].grads->p[i] && c.lv[0].grads->p[i] == c.lv[1].grads->p[i]) return CNERF_E_ARG;
+  }
+  return CNERF_OK;
+}
+
+// A level as the kernels take it — the ONE place where first_ray becomes addresses and counts (dgrad and wgrad must agree on
+// them: a mismatch is an out-of-bounds read on the device, not an error code).  The level's first `first_ray` rays are left out:
+// d_raw and the stash advance past their points (whole tile rows, validate()), the gradient workspace holds the launched rays'
+// rows only, and the device-side live count is reduced by the same number.
+void operands(const Level& L, bool live, CnBwdNet& n) {
+  const int64_t o = L.first_ray * L.S;
+  n.packed = L.packed;
+  n.d_raw = L.d_raw ? L.d_raw + o * n.g.out_ch : nullptr;      // (out_ch = 4 with viewdirs: floats per point of d_raw)
+  n.stash = L.stash + o * n.g.s_rows;
+  n.G = L.workspace;
+  n.M = L.B * L.S - o;
+  n.Mp = cn_round_up(n.M, 32);
+  n.partials = L.workspace + (int64_t)n.g.g_rows * n.Mp;
+  n.cap = cn_wgrad_nsplit(n.Mp);
+  n.grads = L.grads;
+  n.live_mul = live ? L.S : 0;
+  n.live_sub = (int)L.first_ray;
+}
+
+// nets[0, n) of one architecture in ONE grid: blocks [0, nb0) walk nets[0], the rest nets[1]
+int dgrad(const CnBwdNet* nets, int n, const Call& c) {
+  if (c.bf3) return cn_dgrad_bf3(nets, n, cn_stream(c.stream));
+  BwdArgs a;
+  a.g = nets[0].g;
+  for (int i = 0; i < 2; ++i) {
+    const CnBwdNet& s = nets[i < n ? i : 0];
+    a.lv[i] = BwdLevel{static_cast<const float*>(s.packed), s.d_raw, s.stash, s.G, s.M, s.Mp, s.live_mul, s.live_sub};
+  }
+  a.nb0 = (unsigned)cn_div_up(nets[0].M, 32);
+  a.live = c.live_rays;
+  return dispatch(a, n, cn_stream(c.stream));
+}
+
+// Two non-empty levels of the same architecture share one grid (the 8 rounds of the coarse level ride behind the 24 of the fine
+// one); otherwise one launch per non-empty level.
+int run_dgrad(const Call& c, const CnBwdNet* nets) {
+  if (c.n == 2 && nets[0].M > 0 && nets[1].M > 0 && same_arch(*c.lv[0].net, *c.lv[1].net)) return dgrad(nets, 2, c);
+  for (int i = 0; i < c.n; ++i) {
+    const int rc = nets[i].M > 0 ? dgrad(&nets[i], 1, c) : CNERF_OK;
+    if (rc) return rc;
+  }
+  return CNERF_OK;
+}
+
+// The non-empty levels in one wgrad grid + one reduction, whatever their architectures.
+int run_wgrad(const Call& c, const CnBwdNet* nets) {
+  CnBwdNet run[2];
+  int n = 0;
+  for (int i = 0; i < c.n; ++i)
+    if (nets[i].M > 0) run[n++] = nets[i];
+  return n ? cn_wgrad_launch(run, n, c.accumulate, cn_stream(c.stream), c.bf3, c.live_rays) : CNERF_OK;
+}
+
+int run(const Call& c, int stages) {
+  CnBwdNet nets[2];
+  int rc = validate(c, stages, nets);
+  if (rc) return rc;
+  for (int i = 0; i < c.n; ++i) operands(c.lv[i], c.live, nets[i]);
+  if ((stages & DGRAD) && (rc = run_dgrad(c, nets))) return rc;
+  return (stages & WGRAD) ? run_wgrad(c, nets) : CNERF_OK;
+}
+
 }  // namespace
 
 #ifdef CN_TIMING
@@ -233,220 +346,105 @@ extern "C" int64_t cnerf_mlp_bwd_ws_floats(const cnerf_net* net, int64_t M) {
   return (int64_t)g.g_rows * Mp + (int64_t)cn_wgrad_nsplit(Mp) * cn_round_up(cn_param_floats(g), 64);
 }
 
-static int dgrad_one(const cnerf_net* net, const float* packed, const float* d_raw, int64_t B, int S, const float* stash,
-                     float* workspace, const int32_t* live, void* stream, int64_t first = 0) {
-  BwdArgs a;
-  int rc = cn_make_geom(net, &a.g);
-  if (rc) return rc;
-  if (!packed || !d_raw || !stash || !workspace || B < 0 || S <= 0 || (live && S % 32 != 0)) return CNERF_E_ARG;
-  if (first && (!live || first < 0 || first >= B)) return CNERF_E_ARG;
-  if (B == 0) return CNERF_OK;
-  const int64_t o = first * S;      // (first_ray: operands advanced past the rays that are left out, see dgrad_pair)
-  d_raw += o * (a.g.viewdirs ? 4 : a.g.out_ch);
-  stash += o * a.g.s_rows;
-  B -= first;
-  a.lv[0] = BwdLevel{packed, d_raw, stash, workspace, B * S, cn_round_up(B * S, 32), live ? S : 0, first};
-  a.lv[1] = a.lv[0];
-  a.nb0 = (unsigned)cn_div_up(B * S, 32);
-  a.live = live;
-  return dispatch(a, 1, cn_stream(stream));
-}
+// ---- one network --------------------------------------------------------------------------------------------------------
 extern "C" int cnerf_mlp_dgrad(const cnerf_net* net, const float* packed, const float* d_raw, int64_t B, int S,
                                const float* stash, float* workspace, void* stream) {
-  return dgrad_one(net, packed, d_raw, B, S, stash, workspace, nullptr, stream);
+  return run(Call{{{net, packed, d_raw, B, S, stash, workspace}}, 1, false, nullptr, 0, 0, stream}, DGRAD);
 }
-
-static int wgrad_one(const cnerf_net* net, int64_t B, int S, const float* stash, float* workspace, const cnerf_ptrs* grads,
-                     int accumulate, void* stream, int bf3, const int32_t* live = nullptr);
 extern "C" int cnerf_mlp_wgrad(const cnerf_net* net, int64_t B, int S, const float* stash, float* workspace,
                                const cnerf_ptrs* grads, int accumulate, void* stream) {
-  return wgrad_one(net, B, S, stash, workspace, grads, accumulate, stream, 0);
+  return run(Call{{{net, nullptr, nullptr, B, S, stash, workspace, grads}}, 1, false, nullptr, 0, accumulate, stream}, WGRAD);
 }
-// OPT-IN bf16x3 weight gradients (second bench line only): the wide GEMMs on the bf16 matrix cores at three planes per operand
-extern "C" int cnerf_mlp_wgrad_bf(const cnerf_net* net, int64_t B, int S, const float* stash, float* workspace,
-                                  const cnerf_ptrs* grads, int accumulate, void* stream) {
-  return wgrad_one(net, B, S, stash, workspace, grads, accumulate, stream, 1);
-}
-static int wgrad_one(const cnerf_net* net, int64_t B, int S, const float* stash, float* workspace, const cnerf_ptrs* grads,
-                     int accumulate, void* stream, int bf3, const int32_t* live) {
-  NetGeom g;
-  int rc = cn_make_geom(net, &g);
-  if (rc) return rc;
-  if (!stash || !workspace || !grads || B < 0 || S <= 0 || (live && S % 32 != 0)) return CNERF_E_ARG;
-  if (B == 0) return CNERF_OK;
-  const int64_t M = B * S, Mp = cn_round_up(M, 32);
-  const int nsplit = cn_wgrad_nsplit(Mp);
-  float* partials = workspace + (int64_t)g.g_rows * Mp;
-  if (live) {
-    const NetGeom* gp = &g;
-    return cn_wgrad_launch_n(1, &gp, &stash, &workspace, &Mp, &partials, &nsplit, &grads, accumulate, cn_stream(stream), bf3, live, &S);
-  }
-  return cn_wgrad_launch(g, stash, workspace, M, Mp, partials, nsplit, grads, accumulate, cn_stream(stream), bf3);
-}
-
 extern "C" int cnerf_mlp_bwd(const cnerf_net* net, const float* packed, const float* d_raw, int64_t B, int S,
                              const float* stash, float* workspace, const cnerf_ptrs* grads, int accumulate,
                              void* stream) {
-  if (!grads) return CNERF_E_ARG;
-  int rc = cnerf_mlp_dgrad(net, packed, d_raw, B, S, stash, workspace, stream);
-  if (rc) return rc;
-  return cnerf_mlp_wgrad(net, B, S, stash, workspace, grads, accumulate, stream);
+  return run(Call{{{net, packed, d_raw, B, S, stash, workspace, grads}}, 1, false, nullptr, 0, accumulate, stream}, DGRAD | WGRAD);
 }
-
 // cnerf_mlp_bwd of a batch padded to a fixed capacity of B rays whose LIVE row count sits in device memory (cnerf_mlp_fwd_live)
 extern "C" int cnerf_mlp_bwd_live(const cnerf_net* net, const float* packed, const float* d_raw, int64_t B, int S,
                                   const float* stash, float* workspace, const cnerf_ptrs* grads, int accumulate,
                                   const int32_t* live_rays, void* stream) {
-  if (!grads || !live_rays) return CNERF_E_ARG;
-  int rc = dgrad_one(net, packed, d_raw, B, S, stash, workspace, live_rays, stream);
-  if (rc) return rc;
-  return wgrad_one(net, B, S, stash, workspace, grads, accumulate, stream, 0, live_rays);
+  return run(Call{{{net, packed, d_raw, B, S, stash, workspace, grads}}, 1, true, live_rays, 0, accumulate, stream}, DGRAD | WGRAD);
+}
+// OPT-IN bf16x3 (second bench line only): the dgrad GEMMs, and the wide wgrad GEMMs, on the bf16 matrix cores at three planes per
+// operand (mlp_bwd_bf.hip, wgrad.hip)
+extern "C" int cnerf_mlp_dgrad_bf(const cnerf_net* net, const void* packed_bf, const float* d_raw, int64_t B, int S,
+                                  const float* stash, float* workspace, void* stream) {
+  return run(Call{{{net, packed_bf, d_raw, B, S, stash, workspace}}, 1, false, nullptr, 1, 0, stream}, DGRAD);
+}
+extern "C" int cnerf_mlp_wgrad_bf(const cnerf_net* net, int64_t B, int S, const float* stash, float* workspace,
+                                  const cnerf_ptrs* grads, int accumulate, void* stream) {
+  return run(Call{{{net, nullptr, nullptr, B, S, stash, workspace, grads}}, 1, false, nullptr, 1, accumulate, stream}, WGRAD);
 }
 
+// ---- two networks ---------------------------------------------------------------------------------------------------------
 // Backward of TWO independent networks in one dgrad grid + one wgrad grid (+ one reduction): the coarse and the fine
 // network of a render_rays training step (R:311-421) — their backward passes share nothing once the forward is done
 // (the fine level's sample depths are detached, R:397).  The dgrad grid is shared when both have the same architecture,
-// otherwise two dgrad launches; the wgrad grid is always shared.  net0 / net1 must be different parameter sets (two
-// reductions into one gradient tensor would race).  Workspaces as for cnerf_mlp_bwd, one per network.
-static int dgrad_pair(const cnerf_net* net0, const float* packed0, const float* d_raw0, int64_t B0, int S0, const float* stash0,
-                      float* workspace0, const cnerf_net* net1, const float* packed1, const float* d_raw1, int64_t B1, int S1,
-                      const float* stash1, float* workspace1, const int32_t* live, void* stream, int64_t first0 = 0, int64_t first1 = 0);
+// otherwise two dgrad launches; the wgrad grid is always shared.  net0 / net1 must be different parameter sets.
+// Workspaces as for cnerf_mlp_bwd, one per network.
 extern "C" int cnerf_mlp_dgrad_pair(const cnerf_net* net0, const float* packed0, const float* d_raw0, int64_t B0, int S0,
                                     const float* stash0, float* workspace0, const cnerf_net* net1, const float* packed1,
                                     const float* d_raw1, int64_t B1, int S1, const float* stash1, float* workspace1,
                                     void* stream) {
-  return dgrad_pair(net0, packed0, d_raw0, B0, S0, stash0, workspace0, net1, packed1, d_raw1, B1, S1, stash1, workspace1, nullptr,
-                    stream);
+  return run(Call{{{net0, packed0, d_raw0, B0, S0, stash0, workspace0}, {net1, packed1, d_raw1, B1, S1, stash1, workspace1}},
+                  2, false, nullptr, 0, 0, stream}, DGRAD);
 }
-static int dgrad_pair(const cnerf_net* net0, const float* packed0, const float* d_raw0, int64_t B0, int S0, const float* stash0,
-                      float* workspace0, const cnerf_net* net1, const float* packed1, const float* d_raw1, int64_t B1, int S1,
-                      const float* stash1, float* workspace1, const int32_t* live, void* stream, int64_t first0, int64_t first1) {
-  BwdArgs a;
-  NetGeom g1;
-  int rc = cn_make_geom(net0, &a.g);
-  if (rc) return rc;
-  if ((rc = cn_make_geom(net1, &g1))) return rc;
-  if (!packed0 || !d_raw0 || !stash0 || !workspace0 || !packed1 || !d_raw1 || !stash1 || !workspace1 || B0 < 0 || B1 < 0 ||
-      S0 <= 0 || S1 <= 0)
-    return CNERF_E_ARG;
-  const int64_t M0 = B0 * S0, M1 = B1 * S1;
-  const bool same = net0->D == net1->D && net0->W == net1->W && net0->multires == net1->multires &&
-                    net0->multires_views == net1->multires_views && net0->use_viewdirs == net1->use_viewdirs &&
-                    net0->output_ch == net1->output_ch && net0->skip == net1->skip;
-  if (live && (S0 % 32 != 0 || S1 % 32 != 0)) return CNERF_E_ARG;
-  if ((first0 || first1) && (!live || first0 < 0 || first1 < 0 || first0 >= B0 || first1 >= B1)) return CNERF_E_ARG;
-  if (same && M0 > 0 && M1 > 0) {
-    // first_ray: the level's first `first` rays carry zero seeds and are left out — operands advanced past them (tile rows are
-    // 32 points: first * S is a multiple of 32), the device-side count reduced by the same
-    const int64_t o0 = first0 * S0, o1 = first1 * S1;
-    const int rc0 = a.g.viewdirs ? 4 : a.g.out_ch;      // floats per point of d_raw (same architecture: same for both levels)
-    a.lv[0] = BwdLevel{packed0, d_raw0 + o0 * rc0, stash0 + o0 * a.g.s_rows, workspace0, M0 - o0, cn_round_up(M0 - o0, 32), live ? S0 : 0, first0};
-    a.lv[1] = BwdLevel{packed1, d_raw1 + o1 * rc0, stash1 + o1 * g1.s_rows, workspace1, M1 - o1, cn_round_up(M1 - o1, 32), live ? S1 : 0, first1};
-    a.nb0 = (unsigned)cn_div_up(M0 - o0, 32);
-    a.live = live;
-    return dispatch(a, 2, cn_stream(stream));
-  }
-  // (two architectures: one dgrad launch per network)
-  if ((rc = dgrad_one(net0, packed0, d_raw0, B0, S0, stash0, workspace0, live, stream, first0))) return rc;
-  return dgrad_one(net1, packed1, d_raw1, B1, S1, stash1, workspace1, live, stream, first1);
-}
-
-static int wgrad_two(const cnerf_net* net0, int64_t B0, int S0, const float* stash0, float* workspace0, const cnerf_ptrs* grads0,
-                     const cnerf_net* net1, int64_t B1, int S1, const float* stash1, float* workspace1,
-                     const cnerf_ptrs* grads1, int accumulate, void* stream, int bf3, const int32_t* live = nullptr, int64_t first0 = 0,
-                     int64_t first1 = 0);
 extern "C" int cnerf_mlp_wgrad_pair(const cnerf_net* net0, int64_t B0, int S0, const float* stash0, float* workspace0,
                                     const cnerf_ptrs* grads0, const cnerf_net* net1, int64_t B1, int S1,
                                     const float* stash1, float* workspace1, const cnerf_ptrs* grads1, int accumulate,
                                     void* stream) {
-  return wgrad_two(net0, B0, S0, stash0, workspace0, grads0, net1, B1, S1, stash1, workspace1, grads1, accumulate, stream, 0);
+  return run(Call{{{net0, nullptr, nullptr, B0, S0, stash0, workspace0, grads0}, {net1, nullptr, nullptr, B1, S1, stash1, workspace1, grads1}},
+                  2, false, nullptr, 0, accumulate, stream}, WGRAD);
 }
-extern "C" int cnerf_mlp_wgrad_bf_pair(const cnerf_net* net0, int64_t B0, int S0, const float* stash0, float* workspace0,
-                                       const cnerf_ptrs* grads0, const cnerf_net* net1, int64_t B1, int S1,
-                                       const float* stash1, float* workspace1, const cnerf_ptrs* grads1, int accumulate,
-                                       void* stream) {
-  return wgrad_two(net0, B0, S0, stash0, workspace0, grads0, net1, B1, S1, stash1, workspace1, grads1, accumulate, stream, 1);
-}
-static int wgrad_two(const cnerf_net* net0, int64_t B0, int S0, const float* stash0, float* workspace0, const cnerf_ptrs* grads0,
-                     const cnerf_net* net1, int64_t B1, int S1, const float* stash1, float* workspace1,
-                     const cnerf_ptrs* grads1, int accumulate, void* stream, int bf3, const int32_t* live, int64_t first0,
-                     int64_t first1) {
-  if (!grads0 || !grads1 || !stash0 || !stash1 || !workspace0 || !workspace1 || B0 < 0 || B1 < 0 || S0 <= 0 || S1 <= 0 ||
-      (live && (S0 % 32 != 0 || S1 % 32 != 0)))
-    return CNERF_E_ARG;
-  if ((first0 || first1) && (!live || first0 < 0 || first1 < 0 || first0 >= B0 || first1 >= B1)) return CNERF_E_ARG;
-  if (B0 == 0) return wgrad_one(net1, B1, S1, stash1, workspace1, grads1, accumulate, stream, bf3, live);
-  if (B1 == 0) return wgrad_one(net0, B0, S0, stash0, workspace0, grads0, accumulate, stream, bf3, live);
-  for (int i = 0; i < CNERF_MAX_TENSORS; ++i)
-    if (grads0->p[i] && grads0->p[i] == grads1->p[i]) return CNERF_E_ARG;
-  NetGeom g0, g1;
-  int rc = cn_make_geom(net0, &g0);
-  if (rc) return rc;
-  if ((rc = cn_make_geom(net1, &g1))) return rc;
-  const int64_t Mp0 = cn_round_up((B0 - first0) * S0, 32), Mp1 = cn_round_up((B1 - first1) * S1, 32);
-  stash0 += first0 * S0 * g0.s_rows;      // (first_ray: see dgrad_pair; the gradient workspace holds only the launched rays' rows)
-  stash1 += first1 * S1 * g1.s_rows;
-  const NetGeom* gs[2] = {&g0, &g1};
-  const float* stashes[2] = {stash0, stash1};
-  const float* Gs[2] = {workspace0, workspace1};
-  const int64_t Mps[2] = {Mp0, Mp1};
-  const int ns[2] = {cn_wgrad_nsplit(Mp0), cn_wgrad_nsplit(Mp1)};
-  float* parts[2] = {workspace0 + (int64_t)g0.g_rows * Mp0, workspace1 + (int64_t)g1.g_rows * Mp1};
-  const cnerf_ptrs* grs[2] = {grads0, grads1};
-  const int muls[2] = {S0, S1};
-  const int subs[2] = {(int)first0, (int)first1};
-  return cn_wgrad_launch_n(2, gs, stashes, Gs, Mps, parts, ns, grs, accumulate, cn_stream(stream), bf3, live, live ? muls : nullptr,
-                           live ? subs : nullptr);
-}
-
 extern "C" int cnerf_mlp_bwd_pair(const cnerf_net* net0, const float* packed0, const float* d_raw0, int64_t B0, int S0,
                                   const float* stash0, float* workspace0, const cnerf_ptrs* grads0,
                                   const cnerf_net* net1, const float* packed1, const float* d_raw1, int64_t B1, int S1,
                                   const float* stash1, float* workspace1, const cnerf_ptrs* grads1, int accumulate,
                                   void* stream) {
-  if (!grads0 || !grads1) return CNERF_E_ARG;
-  for (int i = 0; i < CNERF_MAX_TENSORS; ++i)
-    if (grads0->p[i] && grads0->p[i] == grads1->p[i]) return CNERF_E_ARG;
-  int rc = cnerf_mlp_dgrad_pair(net0, packed0, d_raw0, B0, S0, stash0, workspace0, net1, packed1, d_raw1, B1, S1, stash1,
-                                workspace1, stream);
-  if (rc) return rc;
-  return cnerf_mlp_wgrad_pair(net0, B0, S0, stash0, workspace0, grads0, net1, B1, S1, stash1, workspace1, grads1, accumulate,
-                              stream);
+  return run(Call{{{net0, packed0, d_raw0, B0, S0, stash0, workspace0, grads0}, {net1, packed1, d_raw1, B1, S1, stash1, workspace1, grads1}},
+                  2, false, nullptr, 0, accumulate, stream}, DGRAD | WGRAD);
+}
+extern "C" int cnerf_mlp_dgrad_bf_pair(const cnerf_net* net0, const void* packed_bf0, const float* d_raw0, int64_t B0, int S0,
+                                       const float* stash0, float* workspace0, const cnerf_net* net1, const void* packed_bf1,
+                                       const float* d_raw1, int64_t B1, int S1, const float* stash1, float* workspace1,
+                                       void* stream) {
+  return run(Call{{{net0, packed_bf0, d_raw0, B0, S0, stash0, workspace0}, {net1, packed_bf1, d_raw1, B1, S1, stash1, workspace1}},
+                  2, false, nullptr, 1, 0, stream}, DGRAD);
+}
+extern "C" int cnerf_mlp_wgrad_bf_pair(const cnerf_net* net0, int64_t B0, int S0, const float* stash0, float* workspace0,
+                                       const cnerf_ptrs* grads0, const cnerf_net* net1, int64_t B1, int S1,
+                                       const float* stash1, float* workspace1, const cnerf_ptrs* grads1, int accumulate,
+                                       void* stream) {
+  return run(Call{{{net0, nullptr, nullptr, B0, S0, stash0, workspace0, grads0}, {net1, nullptr, nullptr, B1, S1, stash1, workspace1, grads1}},
+                  2, false, nullptr, 1, accumulate, stream}, WGRAD);
 }
 
-// the two halves of cnerf_mlp_bwd_pair_live, separately launchable (cf. cnerf_mlp_dgrad_pair / cnerf_mlp_wgrad_pair)
+// cnerf_mlp_bwd_pair of two levels of ONE ray batch padded to a fixed capacity (B0 == B1 rays) whose LIVE row count sits in device
+// memory: both levels' dgrad tiles and wgrad point ranges stop at live_rays * S of their level; and its two halves
 extern "C" int cnerf_mlp_dgrad_pair_live(const cnerf_net* net0, const float* packed0, const float* d_raw0, int64_t B0, int S0,
                                          const float* stash0, float* workspace0, const cnerf_net* net1, const float* packed1,
                                          const float* d_raw1, int64_t B1, int S1, const float* stash1, float* workspace1,
                                          const int32_t* live_rays, int64_t first_ray0, int64_t first_ray1, void* stream) {
-  if (!live_rays || B0 != B1) return CNERF_E_ARG;
-  return dgrad_pair(net0, packed0, d_raw0, B0, S0, stash0, workspace0, net1, packed1, d_raw1, B1, S1, stash1, workspace1, live_rays,
-                    stream, first_ray0, first_ray1);
+  return run(Call{{{net0, packed0, d_raw0, B0, S0, stash0, workspace0, nullptr, first_ray0},
+                   {net1, packed1, d_raw1, B1, S1, stash1, workspace1, nullptr, first_ray1}},
+                  2, true, live_rays, 0, 0, stream}, DGRAD);
 }
 extern "C" int cnerf_mlp_wgrad_pair_live(const cnerf_net* net0, int64_t B0, int S0, const float* stash0, float* workspace0,
                                          const cnerf_ptrs* grads0, const cnerf_net* net1, int64_t B1, int S1, const float* stash1,
                                          float* workspace1, const cnerf_ptrs* grads1, int accumulate, const int32_t* live_rays,
                                          int64_t first_ray0, int64_t first_ray1, void* stream) {
-  if (!live_rays || B0 != B1 || !grads0 || !grads1) return CNERF_E_ARG;
-  for (int i = 0; i < CNERF_MAX_TENSORS; ++i)
-    if (grads0->p[i] && grads0->p[i] == grads1->p[i]) return CNERF_E_ARG;
-  return wgrad_two(net0, B0, S0, stash0, workspace0, grads0, net1, B1, S1, stash1, workspace1, grads1, accumulate, stream, 0,
-                   live_rays, first_ray0, first_ray1);
+  return run(Call{{{net0, nullptr, nullptr, B0, S0, stash0, workspace0, grads0, first_ray0},
+                   {net1, nullptr, nullptr, B1, S1, stash1, workspace1, grads1, first_ray1}},
+                  2, true, live_rays, 0, accumulate, stream}, WGRAD);
 }
-
-// cnerf_mlp_bwd_pair of two levels of ONE ray batch padded to a fixed capacity (B0 == B1 rays) whose LIVE row count sits in device
-// memory: both levels' dgrad tiles and wgrad point ranges stop at live_rays * S of their level
 extern "C" int cnerf_mlp_bwd_pair_live(const cnerf_net* net0, const float* packed0, const float* d_raw0, int64_t B0, int S0,
                                        const float* stash0, float* workspace0, const cnerf_ptrs* grads0,
                                        const cnerf_net* net1, const float* packed1, const float* d_raw1, int64_t B1, int S1,
                                        const float* stash1, float* workspace1, const cnerf_ptrs* grads1, int accumulate,
                                        const int32_t* live_rays, int64_t first_ray0, int64_t first_ray1, void* stream) {
-  if (!grads0 || !grads1 || !live_rays || B0 != B1) return CNERF_E_ARG;
-  for (int i = 0; i < CNERF_MAX_TENSORS; ++i)
-    if (grads0->p[i] && grads0->p[i] == grads1->p[i]) return CNERF_E_ARG;
-  int rc = dgrad_pair(net0, packed0, d_raw0, B0, S0, stash0, workspace0, net1, packed1, d_raw1, B1, S1, stash1, workspace1, live_rays,
-                      stream, first_ray0, first_ray1);
-  if (rc) return rc;
-  return wgrad_two(net0, B0, S0, stash0, workspace0, grads0, net1, B1, S1, stash1, workspace1, grads1, accumulate, stream, 0,
-                   live_rays, first_ray0, first_ray1);
+  return run(Call{{{net0, packed0, d_raw0, B0, S0, stash0, workspace0, grads0, first_ray0},
+                   {net1, packed1, d_raw1, B1, S1, stash1, workspace1, grads1, first_ray1}},
+                  2, true, live_rays, 0, accumulate, stream}, DGRAD | WGRAD);
 }
+

@@ -8,8 +8,7 @@
 // workgroup (128 points) share ONE stream of pre-split transposed weight panels through the LDS ring, the B planes are split on
 // the VALU in the gaps between MFMAs.  The sigma / rgb heads stay fp32 on the VALU.  Output: the same G the fp32 wgrad reads.
 #include "mlp_bf_common.hpp"
-
-int cn_make_geom(const cnerf_net* net, NetGeom* g);
+#include "mlp_bwd_host.hpp"
 
 namespace {
 
@@ -147,23 +146,14 @@ __global__ __launch_bounds__(256) void mlp_dgrad_bfs_k(BfBwdArgs args_by_value) 
 template <int NT>
 int launch(const BfBwdArgs& a, int nlev, hipStream_t st) {
   const size_t lds = (size_t)4 * Ring<NT, 3>::SLOT;
-  static bool attr_set[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return CNERF_E_NODEVICE;
-  if (!attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_dgrad_bfs_k<NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-      return (int)hipGetLastError();
-    attr_set[dev] = true;
-  }
+  const int rc = cn_lds_opt_in<mlp_dgrad_bfs_k<NT>>(lds);
+  if (rc) return rc;
   unsigned grid = 0;
   for (int i = 0; i < nlev; ++i) {
     const BfBwdLevel& L = a.lv[i];
     grid += (unsigned)cn_div_up(L.M, 128);
-    if (L.Mp > L.M) {   // last gradient tile row holds padding points: the kernel drops their stores, wgrad reads them
-      hipError_t e = hipMemsetAsync(L.G + (L.Mp - 32) * a.g.g_rows, 0, (size_t)32 * a.g.g_rows * sizeof(float), st);
-      if (e != hipSuccess) return (int)e;
-    }
+    const hipError_t e = cn_zero_padding_tile_row(L.G, L.M, L.Mp, a.g.g_rows, st);
+    if (e != hipSuccess) return (int)e;
   }
   hipLaunchKernelGGL((mlp_dgrad_bfs_k<NT>), dim3(grid), dim3(256), lds, st, a);
   CN_CHECK_LAUNCH();
@@ -181,43 +171,20 @@ int dispatch(const BfBwdArgs& a, int nlev, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int cnerf_mlp_dgrad_bf(const cnerf_net* net, const void* packed_bf, const float* d_raw, int64_t B, int S,
-                                  const float* stash, float* workspace, void* stream) {
-  BfBwdArgs a;
-  int rc = cn_make_geom(net, &a.g);
-  if (rc) return rc;
-  if ((rc = make_bf_geom(a.g, 3, &a.b))) return rc;
-  if (!packed_bf || !d_raw || !stash || !workspace || B < 0 || S <= 0) return CNERF_E_ARG;
-  if (B == 0) return CNERF_OK;
-  a.lv[0] = BfBwdLevel{static_cast<const unsigned char*>(packed_bf), d_raw, stash, workspace, B * S, cn_round_up(B * S, 32)};
-  a.lv[1] = a.lv[0];
-  a.nb0 = (unsigned)cn_div_up(B * S, 128);
-  return dispatch(a, 1, cn_stream(stream));
+int cn_dgrad_bf3_supported(const NetGeom& g) {
+  BfGeom b;
+  return make_bf_geom(g, 3, &b);
 }
 
-// Two independent networks of the same architecture (coarse and fine of one training step) in ONE grid; different
-// architectures take two launches.
-extern "C" int cnerf_mlp_dgrad_bf_pair(const cnerf_net* net0, const void* packed_bf0, const float* d_raw0, int64_t B0, int S0,
-                                       const float* stash0, float* workspace0, const cnerf_net* net1, const void* packed_bf1,
-                                       const float* d_raw1, int64_t B1, int S1, const float* stash1, float* workspace1,
-                                       void* stream) {
+int cn_dgrad_bf3(const CnBwdNet* nets, int n, hipStream_t st) {
   BfBwdArgs a;
-  int rc = cn_make_geom(net0, &a.g);
+  a.g = nets[0].g;
+  const int rc = make_bf_geom(a.g, 3, &a.b);
   if (rc) return rc;
-  if ((rc = make_bf_geom(a.g, 3, &a.b))) return rc;
-  if (!packed_bf0 || !d_raw0 || !stash0 || !workspace0 || !packed_bf1 || !d_raw1 || !stash1 || !workspace1 || B0 < 0 || B1 < 0 ||
-      S0 <= 0 || S1 <= 0)
-    return CNERF_E_ARG;
-  const int64_t M0 = B0 * S0, M1 = B1 * S1;
-  const bool same = net0->D == net1->D && net0->W == net1->W && net0->multires == net1->multires &&
-                    net0->multires_views == net1->multires_views && net0->use_viewdirs == net1->use_viewdirs &&
-                    net0->output_ch == net1->output_ch && net0->skip == net1->skip;
-  if (same && M0 > 0 && M1 > 0) {
-    a.lv[0] = BfBwdLevel{static_cast<const unsigned char*>(packed_bf0), d_raw0, stash0, workspace0, M0, cn_round_up(M0, 32)};
-    a.lv[1] = BfBwdLevel{static_cast<const unsigned char*>(packed_bf1), d_raw1, stash1, workspace1, M1, cn_round_up(M1, 32)};
-    a.nb0 = (unsigned)cn_div_up(M0, 128);
-    return dispatch(a, 2, cn_stream(stream));
+  for (int i = 0; i < 2; ++i) {
+    const CnBwdNet& s = nets[i < n ? i : 0];
+    a.lv[i] = BfBwdLevel{static_cast<const unsigned char*>(s.packed), s.d_raw, s.stash, s.G, s.M, s.Mp};
   }
-  if ((rc = cnerf_mlp_dgrad_bf(net0, packed_bf0, d_raw0, B0, S0, stash0, workspace0, stream))) return rc;
-  return cnerf_mlp_dgrad_bf(net1, packed_bf1, d_raw1, B1, S1, stash1, workspace1, stream);
+  a.nb0 = (unsigned)cn_div_up(nets[0].M, 128);
+  return dispatch(a, n, st);
 }

@@ -263,10 +263,8 @@ template <int NT>
 int launch(const FwdArgs& a, hipStream_t st) {
   const unsigned grid = (unsigned)cn_div_up(a.M, 32);
   if (a.stash != nullptr) {
-    if (a.Mp > a.M) {   // last tile row holds padding points: the kernel drops their stores, wgrad reads them
-      hipError_t e = hipMemsetAsync(a.stash + (a.Mp - 32) * a.g.s_rows, 0, (size_t)32 * a.g.s_rows * sizeof(float), st);
-      if (e != hipSuccess) return (int)e;
-    }
+    const hipError_t e = cn_zero_padding_tile_row(a.stash, a.M, a.Mp, a.g.s_rows, st);
+    if (e != hipSuccess) return (int)e;
     if (a.live != nullptr) {
       if (a.g.viewdirs) hipLaunchKernelGGL((mlp_fwd_k<NT, true, true, true>), dim3(grid), dim3(64), 0, st, a);
       else hipLaunchKernelGGL((mlp_fwd_k<NT, false, true, true>), dim3(grid), dim3(64), 0, st, a);

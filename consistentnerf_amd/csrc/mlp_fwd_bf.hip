@@ -486,21 +486,11 @@ __global__ __launch_bounds__(256) void mlp_fwd_bfs_k(BfArgs args_by_value) {
 template <int NT, int MODE, bool TRAIN>
 int launch_bfs(const BfArgs& a, hipStream_t st) {
   const size_t lds = (size_t)4 * Ring<NT, PlaneMode<MODE>::NP>::SLOT + 4 * 16384;
-  static bool attr_set[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return CNERF_E_NODEVICE;
-  if (!attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_fwd_bfs_k<NT, MODE, TRAIN>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-      return (int)hipGetLastError();
-    attr_set[dev] = true;
-  }
+  const int rc = cn_lds_opt_in<mlp_fwd_bfs_k<NT, MODE, TRAIN>>(lds);
+  if (rc) return rc;
   if (TRAIN) {
-    const int64_t Mp = cn_round_up(a.M, 32);
-    if (Mp > a.M) {   // last tile row holds padding points: the kernel drops their stores, wgrad reads them
-      hipError_t e = hipMemsetAsync(a.stash + (Mp - 32) * a.g.s_rows, 0, (size_t)32 * a.g.s_rows * sizeof(float), st);
-      if (e != hipSuccess) return (int)e;
-    }
+    const hipError_t e = cn_zero_padding_tile_row(a.stash, a.M, cn_round_up(a.M, 32), a.g.s_rows, st);
+    if (e != hipSuccess) return (int)e;
   }
   hipLaunchKernelGGL((mlp_fwd_bfs_k<NT, MODE, TRAIN>), dim3((unsigned)cn_div_up(a.M, 128)), dim3(256), lds, st, a);
   CN_CHECK_LAUNCH();

@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include "mlp_bf_common.hpp"
+#include "mlp_bwd_host.hpp"
 
 namespace {
 
@@ -711,8 +712,8 @@ int cn_wgrad_nsplit(int64_t Mp) {
 namespace {
 
 // Appends one network's GEMMs to the job table / reduction table.  Returns false when a shape is outside the envelope.
-bool add_net_jobs(const NetGeom& g, int netidx, const float* stash, const float* G, int64_t Mp, float* partials,
-                  const cnerf_ptrs* grads, WgArgs& a, int& nj, RedArgs& r, int& nr, bool bf3 = false) {
+bool add_net_jobs(const CnBwdNet& n, int netidx, const int* live, WgArgs& a, int& nj, RedArgs& r, int& nr, bool bf3) {
+  const NetGeom& g = n.g;
   cnerf_net net{g.D, g.W, g.L, g.Ld, g.viewdirs, g.out_ch, g.skip};
   WgNet& wn = a.net[netidx];
   const int nt = cnerf_num_tensors(&net);
@@ -723,8 +724,8 @@ bool add_net_jobs(const NetGeom& g, int netidx, const float* stash, const float*
     cnerf_tensor_shape(&net, i, &rr, &cc);
     wn.toff[i] = off;
     r.numel[r0 + i] = rr * cc;
-    r.grad[r0 + i] = grads->p[i];
-    r.part[r0 + i] = partials + off;
+    r.grad[r0 + i] = n.grads->p[i];
+    r.part[r0 + i] = n.partials + off;
     r.nsplit[r0 + i] = 0;
     r.touched[r0 + i] = 0;
     off += cn_round_up(rr * cc, 4);
@@ -777,9 +778,9 @@ bool add_net_jobs(const NetGeom& g, int netidx, const float* stash, const float*
   } else {
     add(g.g_out, g.s_h[D - 1], g.out_ch, W, base + 2, W, 0, base + 3);
   }
-  wn.stash = stash; wn.G = G; wn.partials = partials; wn.Mp = Mp; wn.pstride = pstride;
+  wn.stash = n.stash; wn.G = n.G; wn.partials = n.partials; wn.Mp = n.Mp; wn.pstride = pstride;
   wn.s_rows = g.s_rows; wn.g_rows = g.g_rows;
-  wn.live = nullptr; wn.live_mul = 0; wn.live_sub = 0;
+  wn.live = live; wn.live_mul = live ? n.live_mul : 0; wn.live_sub = live ? n.live_sub : 0;
   return ok;
 }
 
@@ -829,72 +830,65 @@ void order_jobs(const WgJob* job, int nj, const int* ns, const int64_t* slabs, i
   }
 }
 
-}  // namespace
-
-// Weight gradients of one network (n = 1) or of two independent ones in one grid (n = 2; cnerf_mlp_bwd_pair).  `nsplit` is the
-// capacity of each network's partial buffer in slices (cn_wgrad_nsplit).
-int cn_wgrad_launch_n(int n, const NetGeom* const* g, const float* const* stash, const float* const* G, const int64_t* Mp,
-                      float* const* partials, const int* nsplit, const cnerf_ptrs* const* grads, int accumulate,
-                      hipStream_t st, int bf3, const int* live, const int* live_mul, const int* live_sub) {
+// The plan of one launch over nets[0, n): the GEMM jobs, each with its ranges and points per range (WgJob::nsplit, chunk), in
+// grid order — longest workgroups first, jobs back to back (WgJob::first; `grid` blocks in all) — and the reduction table.
+// What is launched and what cnerf_debug_wgrad_plan shows are both this.
+struct WgPlan {
   WgArgs a;
   RedArgs r;
+  int nr, grid;
+};
+
+int make_plan(const CnBwdNet* nets, int n, bool bf3, const int* live, WgPlan& p) {
+  WgArgs a;
+  RedArgs& r = p.r;
   int nj = 0, nr = 0, r0[2] = {0, 0};
-  if (live && (bf3 || !live_mul)) return CNERF_E_UNSUPPORTED;     // (the device-side row count is the exact-fp32 body's)
   for (int i = 0; i < n; ++i) {
     r0[i] = nr;
-    if (!add_net_jobs(*g[i], i, stash[i], G[i], Mp[i], partials[i], grads[i], a, nj, r, nr, bf3 != 0)) return CNERF_E_UNSUPPORTED;
-    a.net[i].live = live;
-    a.net[i].live_mul = live ? live_mul[i] : 0;
-    a.net[i].live_sub = (live && live_sub) ? live_sub[i] : 0;
-    if (live && (live_mul[i] <= 0 || live_mul[i] % TM != 0)) return CNERF_E_ARG;
+    if (!add_net_jobs(nets[i], i, live, a, nj, r, nr, bf3)) return CNERF_E_UNSUPPORTED;
   }
   if (n == 1) a.net[1] = a.net[0];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return CNERF_E_NODEVICE;
-  int ns[MAX_WG_JOBS];
-  {
-    const int cap[2] = {nsplit[0], n > 1 ? nsplit[1] : nsplit[0]};
-    plan_ranges(a, nj, cap, ns);
-  }
+  const int cap[2] = {nets[0].cap, nets[n - 1].cap};
+  int ns[MAX_WG_JOBS], order[MAX_WG_JOBS];
   int64_t slabs[MAX_WG_JOBS];
-  int order[MAX_WG_JOBS];
+  plan_ranges(a, nj, cap, ns);
   for (int i = 0; i < nj; ++i) {
     WgJob& j = a.job[i];
     slabs[i] = a.net[j.net].Mp / TM;
     j.nsplit = ns[i];
     j.chunk = (int)(cn_div_up(slabs[i], (int64_t)ns[i]) * TM);
     // a range's operand rows sit behind one buffer resource each: 32-bit byte offsets
-    const NetGeom& gg = *g[j.net];
+    const NetGeom& gg = nets[j.net].g;
     if ((int64_t)j.chunk * (gg.s_rows > gg.g_rows ? gg.s_rows : gg.g_rows) * 4 >= (int64_t)0x7fffffff) return CNERF_E_UNSUPPORTED;
-    if (j.nsplit > nsplit[j.net]) return CNERF_E_UNSUPPORTED;
+    if (j.nsplit > cap[j.net]) return CNERF_E_UNSUPPORTED;
     r.nsplit[r0[j.net] + j.tensor] = j.nsplit;
     if (j.bias_tensor >= 0) r.nsplit[r0[j.net] + j.bias_tensor] = j.nsplit;
   }
-  // grid order: longest workgroups first, jobs back to back
   order_jobs(a.job, nj, ns, slabs, order);
-  WgArgs b = a;
-  int first = 0;
+  p.a = a;
+  p.grid = 0;
   for (int oi = 0; oi < nj; ++oi) {
-    b.job[oi] = a.job[order[oi]];
-    b.job[oi].first = first;
-    first += b.job[oi].nsplit;
+    p.a.job[oi] = a.job[order[oi]];
+    p.a.job[oi].first = p.grid;
+    p.grid += p.a.job[oi].nsplit;
   }
-  b.nj = nj;
-  const size_t lds_bytes = LDS_BYTES;
-  // the 160 KiB dynamic-LDS opt-in is a per-device function attribute: set it once per device this process launches on
-  // (idempotent, so a race between two host threads only repeats the call)
-  static bool attr_set[2][64] = {};
-  const void* kfn = bf3 ? reinterpret_cast<const void*>(wgrad_mixed_k) : reinterpret_cast<const void*>(wgrad_k);
-  if (!attr_set[bf3 ? 1 : 0][dev]) {
-    if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-      return (int)hipGetLastError();
-    attr_set[bf3 ? 1 : 0][dev] = true;
-  }
-  if (bf3) hipLaunchKernelGGL(wgrad_mixed_k, dim3(first), dim3(64 * NWAVES), lds_bytes, st, b);
-  else hipLaunchKernelGGL(wgrad_k, dim3(first), dim3(64 * NWAVES), lds_bytes, st, b);
+  p.a.nj = nj;
+  p.nr = nr;
+  return CNERF_OK;
+}
+
+}  // namespace
+
+int cn_wgrad_launch(const CnBwdNet* nets, int n, int accumulate, hipStream_t st, int bf3, const int* live) {
+  WgPlan p;
+  int rc = make_plan(nets, n, bf3 != 0, live, p);
+  if (rc) return rc;
+  if ((rc = bf3 ? cn_lds_opt_in<wgrad_mixed_k>(LDS_BYTES) : cn_lds_opt_in<wgrad_k>(LDS_BYTES))) return rc;
+  if (bf3) hipLaunchKernelGGL(wgrad_mixed_k, dim3(p.grid), dim3(64 * NWAVES), LDS_BYTES, st, p.a);
+  else hipLaunchKernelGGL(wgrad_k, dim3(p.grid), dim3(64 * NWAVES), LDS_BYTES, st, p.a);
   CN_CHECK_LAUNCH();
-  r.accumulate = accumulate;
-  hipLaunchKernelGGL(wgrad_reduce_k, dim3(64, nr), dim3(256), 0, st, r);
+  p.r.accumulate = accumulate;
+  hipLaunchKernelGGL(wgrad_reduce_k, dim3(64, p.nr), dim3(256), 0, st, p.r);
   CN_CHECK_LAUNCH();
   return CNERF_OK;
 }
@@ -904,40 +898,26 @@ int cn_wgrad_launch_n(int n, const NetGeom* const* g, const float* const* stash,
 // Returns the number of jobs.  Used by tests/test_host.py and scripts/wgrad_plan.py.
 extern "C" int cnerf_debug_wgrad_plan(const cnerf_net* net0, int64_t Mp0, const cnerf_net* net1, int64_t Mp1, int* out7,
                                       int max_jobs) {
-  NetGeom g[2];
-  const cnerf_net* nets[2] = {net0, net1};
-  const int64_t Mps[2] = {cn_round_up(Mp0, 32), cn_round_up(Mp1, 32)};
+  const cnerf_net* in[2] = {net0, net1};
+  const int64_t Mp[2] = {cn_round_up(Mp0, 32), cn_round_up(Mp1, 32)};
   const int n = net1 ? 2 : 1;
-  WgArgs a;
-  RedArgs r;
-  cnerf_ptrs dummy;
-  memset(&dummy, 0, sizeof(dummy));
-  int nj = 0, nr = 0, cap[2] = {1, 1};
+  cnerf_ptrs no_grads = {};
+  CnBwdNet nets[2] = {};
   for (int i = 0; i < n; ++i) {
-    int rc = cn_make_geom(nets[i], &g[i]);
+    const int rc = cn_make_geom(in[i], &nets[i].g);
     if (rc) return rc < 0 ? rc : -rc;
-    if (!add_net_jobs(g[i], i, nullptr, nullptr, Mps[i], nullptr, &dummy, a, nj, r, nr)) return CNERF_E_UNSUPPORTED;
-    cap[i] = cn_wgrad_nsplit(Mps[i]);
+    nets[i].Mp = Mp[i];
+    nets[i].cap = cn_wgrad_nsplit(Mp[i]);
+    nets[i].grads = &no_grads;
   }
-  if (n == 1) cap[1] = cap[0];
-  if (nj > max_jobs) return CNERF_E_ARG;
-  int ns[MAX_WG_JOBS], order[MAX_WG_JOBS];
-  int64_t slabs[MAX_WG_JOBS];
-  plan_ranges(a, nj, cap, ns);
-  for (int i = 0; i < nj; ++i) slabs[i] = a.net[a.job[i].net].Mp / TM;
-  order_jobs(a.job, nj, ns, slabs, order);
-  for (int oi = 0; oi < nj; ++oi) {
-    const WgJob& j = a.job[order[oi]];
-    int* o = out7 + 7 * oi;
-    o[0] = j.net; o[1] = j.N - j.n_lo; o[2] = j.K; o[3] = j.an * j.ak; o[4] = ns[order[oi]];
-    o[5] = (int)(cn_div_up(slabs[order[oi]], (int64_t)ns[order[oi]]) * TM); o[6] = j.tensor;
+  WgPlan p;
+  const int rc = make_plan(nets, n, false, nullptr, p);
+  if (rc) return rc;
+  if (p.a.nj > max_jobs) return CNERF_E_ARG;
+  for (int i = 0; i < p.a.nj; ++i) {
+    const WgJob& j = p.a.job[i];
+    int* o = out7 + 7 * i;
+    o[0] = j.net; o[1] = j.N - j.n_lo; o[2] = j.K; o[3] = j.an * j.ak; o[4] = j.nsplit; o[5] = j.chunk; o[6] = j.tensor;
   }
-  return nj;
-}
-
-int cn_wgrad_launch(const NetGeom& g, const float* stash, const float* G, int64_t M, int64_t Mp, float* partials,
-                    int nsplit, const cnerf_ptrs* grads, int accumulate, hipStream_t st, int bf3) {
-  (void)M;   // padding points [M, Mp) are stored as zeros by the producers: no masking here
-  const NetGeom* gp = &g;
-  return cn_wgrad_launch_n(1, &gp, &stash, &G, &Mp, &partials, &nsplit, &grads, accumulate, st, bf3, nullptr, nullptr, nullptr);
+  return p.a.nj;
 }

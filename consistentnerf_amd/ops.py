@@ -355,38 +355,53 @@ def mlp_forward_embedded(spec: NetSpec, packed: Tensor, x: Tensor, want_stash: b
     return raw, stash
 
 
+# (pair, live, bf) -> the calls of one backward as (stage, entry point, profile name): the two halves where they exist (bench.py's
+# HIP events bracket each kernel), the combined call otherwise
+_BWD_ENTRY = {
+    (False, False, False): (("dgrad", "cnerf_mlp_dgrad", "mlp_dgrad"), ("wgrad", "cnerf_mlp_wgrad", "mlp_wgrad")),
+    (False, False, True): (("dgrad", "cnerf_mlp_dgrad_bf", "mlp_dgrad_bf3"), ("wgrad", "cnerf_mlp_wgrad_bf", "mlp_wgrad_bf3")),
+    (False, True, False): (("bwd", "cnerf_mlp_bwd_live", "mlp_bwd_live"),),
+    (True, False, False): (("dgrad", "cnerf_mlp_dgrad_pair", "mlp_dgrad"), ("wgrad", "cnerf_mlp_wgrad_pair", "mlp_wgrad")),
+    (True, False, True): (("dgrad", "cnerf_mlp_dgrad_bf_pair", "mlp_dgrad_bf3"), ("wgrad", "cnerf_mlp_wgrad_bf_pair", "mlp_wgrad_bf3")),
+    (True, True, False): (("dgrad", "cnerf_mlp_dgrad_pair_live", "mlp_dgrad"), ("wgrad", "cnerf_mlp_wgrad_pair_live", "mlp_wgrad")),
+}
+
+
+def _mlp_backward(levels, accumulate, bf, live, first=()):
+    """One backward over `levels`, one or two of (spec, packed, d_raw, B, S, stash, grads) with `packed` the buffer of the chosen
+    arithmetic.  `units` of the profile records is the launch CAPACITY (with `live` the point count is on the device: the bench
+    rescales by the step's live rows)."""
+    lib = _lib.load()
+    dgrad, wgrad, units, keep = [], [], 0, []
+    for i, (spec, packed, d_raw, B, S, stash, grads) in enumerate(levels):
+        net, ptrs = spec.c(), _ptrs(grads)
+        d_raw = _chk(d_raw, "d_raw" if len(levels) == 1 else "d_raw%d" % i)
+        ws = torch.empty(lib.cnerf_mlp_bwd_ws_floats(C.byref(net), B * S), device=packed.device, dtype=torch.float32)
+        dgrad.append([C.byref(net), _p(packed), _p(d_raw), B, S, _p(stash), _p(ws)])
+        wgrad.append([C.byref(net), B, S, _p(stash), _p(ws), C.byref(ptrs)])
+        units += B * S
+        keep += [d_raw, ws]      # (alive until the launches are enqueued: a freed workspace would be handed to the next level)
+    tail = ([] if live is None else [_p(live)]) + [int(f) for f in first]
+    args = {"dgrad": [a for lv in dgrad for a in lv] + tail,
+            "wgrad": [a for lv in wgrad for a in lv] + [int(accumulate)] + tail,
+            "bwd": [a for d, w in zip(dgrad, wgrad) for a in d + w[-1:]] + [int(accumulate)] + tail}
+    for stage, name, profile in _BWD_ENTRY[len(levels) == 2, live is not None, bool(bf)]:
+        with _timed(profile, units):
+            _lib.check(getattr(lib, name)(*args[stage], _stream()), name)
+
+
 def mlp_backward(spec: NetSpec, packed: Tensor, d_raw: Tensor, B: int, S: int, stash: Tensor,
                  grads: Optional[List[Tensor]] = None, accumulate: bool = False, packed_bf: Optional[Tensor] = None,
                  live: Optional[Tensor] = None) -> List[Tensor]:
     """packed_bf (the three-plane buffer of pack_weights_bf): the dgrad and wgrad run in the opt-in bf16x3 arithmetic.
     live: the forward ran through mlp_forward(live=...) — the backward stops at the same device-side row count (exact fp32)."""
-    lib, net = _lib.load(), spec.c()
-    d_raw = _chk(d_raw, "d_raw")
-    dev = packed.device
     if grads is None:
-        grads = [torch.empty(s, device=dev, dtype=torch.float32) for s in spec.tensor_shapes()]
+        grads = [torch.empty(s, device=packed.device, dtype=torch.float32) for s in spec.tensor_shapes()]
         accumulate = False
-    ws = torch.empty(lib.cnerf_mlp_bwd_ws_floats(C.byref(net), B * S), device=dev, dtype=torch.float32)
-    ptrs = _ptrs(grads)
-    if live is not None:
-        if packed_bf is not None:
-            raise CnerfError("mlp_backward(live=...) is an exact-fp32 path")
-        with _timed("mlp_bwd_live", B * S):
-            _lib.check(lib.cnerf_mlp_bwd_live(C.byref(net), _p(packed), _p(d_raw), B, S, _p(stash), _p(ws), C.byref(ptrs),
-                                              int(accumulate), _p(live), _stream()), "cnerf_mlp_bwd_live")
-        return grads
     bf = packed_bf is not None
-    if bf:
-        with _timed("mlp_dgrad_bf3", B * S):
-            _lib.check(lib.cnerf_mlp_dgrad_bf(C.byref(net), _p(packed_bf), _p(d_raw), B, S, _p(stash), _p(ws), _stream()),
-                       "cnerf_mlp_dgrad_bf")
-    else:
-        with _timed("mlp_dgrad", B * S):
-            _lib.check(lib.cnerf_mlp_dgrad(C.byref(net), _p(packed), _p(d_raw), B, S, _p(stash), _p(ws), _stream()),
-                       "cnerf_mlp_dgrad")
-    with _timed("mlp_wgrad_bf3" if bf else "mlp_wgrad", B * S):
-        _lib.check((lib.cnerf_mlp_wgrad_bf if bf else lib.cnerf_mlp_wgrad)(C.byref(net), B, S, _p(stash), _p(ws), C.byref(ptrs),
-                                                                             int(accumulate), _stream()), "cnerf_mlp_wgrad")
+    if live is not None and bf:
+        raise CnerfError("mlp_backward(live=...) is an exact-fp32 path")
+    _mlp_backward([(spec, packed_bf if bf else packed, d_raw, B, S, stash, grads)], accumulate, bf, live)
     return grads
 
 
@@ -397,44 +412,14 @@ def mlp_backward_pair(spec0: NetSpec, packed0: Tensor, d_raw0: Tensor, B0: int, 
     """cnerf_mlp_bwd_pair: the backward of two independent networks (coarse / fine) as one dgrad grid, one wgrad grid and
     one reduction; gradients are written (or accumulated) into grads0 / grads1.  packed_bf0 AND packed_bf1: the dgrad and wgrad
     grids run in the opt-in bf16x3 arithmetic.  live: both levels belong to one ray batch whose live row count sits on the device
-    (mlp_forward(live=...)): cnerf_mlp_bwd_pair_live (exact fp32); first0 / first1: that level's first rays carry zero seeds and are
-    left out of its backward."""
-    lib = _lib.load()
-    n0, n1 = spec0.c(), spec1.c()
-    d_raw0, d_raw1 = _chk(d_raw0, "d_raw0"), _chk(d_raw1, "d_raw1")
-    dev = packed0.device
-    ws0 = torch.empty(lib.cnerf_mlp_bwd_ws_floats(C.byref(n0), B0 * S0), device=dev, dtype=torch.float32)
-    ws1 = torch.empty(lib.cnerf_mlp_bwd_ws_floats(C.byref(n1), B1 * S1), device=dev, dtype=torch.float32)
-    p0, p1 = _ptrs(grads0), _ptrs(grads1)
-    if live is not None:
-        if packed_bf0 is not None or packed_bf1 is not None:
-            raise CnerfError("mlp_backward_pair(live=...) is an exact-fp32 path")
-        # (the halves of cnerf_mlp_bwd_pair_live, launched separately so that bench.py's HIP events bracket each kernel; `units` is
-        #  the launch CAPACITY — the live point count is on the device — the bench rescales by the step's live rows)
-        with _timed("mlp_dgrad", B0 * S0 + B1 * S1):
-            _lib.check(lib.cnerf_mlp_dgrad_pair_live(C.byref(n0), _p(packed0), _p(d_raw0), B0, S0, _p(stash0), _p(ws0), C.byref(n1),
-                                                     _p(packed1), _p(d_raw1), B1, S1, _p(stash1), _p(ws1), _p(live), int(first0),
-                                                     int(first1), _stream()), "cnerf_mlp_dgrad_pair_live")
-        with _timed("mlp_wgrad", B0 * S0 + B1 * S1):
-            _lib.check(lib.cnerf_mlp_wgrad_pair_live(C.byref(n0), B0, S0, _p(stash0), _p(ws0), C.byref(p0), C.byref(n1), B1, S1,
-                                                     _p(stash1), _p(ws1), C.byref(p1), int(accumulate), _p(live), int(first0),
-                                                     int(first1), _stream()), "cnerf_mlp_wgrad_pair_live")
-        return
+    (mlp_forward(live=...)): the halves of cnerf_mlp_bwd_pair_live (exact fp32); first0 / first1: that level's first rays carry
+    zero seeds and are left out of its backward."""
+    if live is not None and (packed_bf0 is not None or packed_bf1 is not None):
+        raise CnerfError("mlp_backward_pair(live=...) is an exact-fp32 path")
     bf = packed_bf0 is not None and packed_bf1 is not None
-    if bf:
-        with _timed("mlp_dgrad_bf3", B0 * S0 + B1 * S1):
-            _lib.check(lib.cnerf_mlp_dgrad_bf_pair(C.byref(n0), _p(packed_bf0), _p(d_raw0), B0, S0, _p(stash0), _p(ws0),
-                                                   C.byref(n1), _p(packed_bf1), _p(d_raw1), B1, S1, _p(stash1), _p(ws1), _stream()),
-                       "cnerf_mlp_dgrad_bf_pair")
-    else:
-        with _timed("mlp_dgrad", B0 * S0 + B1 * S1):
-            _lib.check(lib.cnerf_mlp_dgrad_pair(C.byref(n0), _p(packed0), _p(d_raw0), B0, S0, _p(stash0), _p(ws0),
-                                                C.byref(n1), _p(packed1), _p(d_raw1), B1, S1, _p(stash1), _p(ws1), _stream()),
-                       "cnerf_mlp_dgrad_pair")
-    with _timed("mlp_wgrad_bf3" if bf else "mlp_wgrad", B0 * S0 + B1 * S1):
-        _lib.check((lib.cnerf_mlp_wgrad_bf_pair if bf else lib.cnerf_mlp_wgrad_pair)(
-            C.byref(n0), B0, S0, _p(stash0), _p(ws0), C.byref(p0), C.byref(n1), B1, S1, _p(stash1), _p(ws1), C.byref(p1),
-            int(accumulate), _stream()), "cnerf_mlp_wgrad_pair")
+    _mlp_backward([(spec0, packed_bf0 if bf else packed0, d_raw0, B0, S0, stash0, grads0),
+                   (spec1, packed_bf1 if bf else packed1, d_raw1, B1, S1, stash1, grads1)],
+                  accumulate, bf, live, (first0, first1) if live is not None else ())
 
 
 # ------------------------------------------------------------------------------------------ render_rays as one call

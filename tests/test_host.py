@@ -492,6 +492,64 @@ def test_wgrad_range_plan_invariants():
     assert len(wgrad_plan.plan(4096, S=(192,))) == 14
 
 
+def test_backward_forms_reject_bad_arguments_on_the_host(lib):
+    """The 14 forms of the MLP backward (cnerf_mlp_{bwd,dgrad,wgrad} x single / pair / live / bf16x3) share one set of argument
+    rules.  Every call below is an otherwise complete call (real net / gradient-pointer structs, fake non-null device pointers)
+    with ONE thing wrong, and must come back with the exact code from host-side checks alone: nothing here may reach a launch
+    (CNERF_E_NODEVICE, -3, on a machine without a GPU, would mean one did)."""
+    import ctypes as C
+    from consistentnerf_amd import _lib
+    E_ARG, E_UNSUPPORTED, FAKE = -1, -2, 0x10000
+    good, w100 = _lib.Net(2, 128, 10, 4, 1, 4, 4), _lib.Net(2, 100, 10, 4, 1, 4, 4)
+    nt = lib.cnerf_num_tensors(C.byref(good))
+    g0, g1, g1_shared = _lib.Ptrs(), _lib.Ptrs(), _lib.Ptrs()
+    for i in range(nt):
+        g0.p[i], g1.p[i], g1_shared.p[i] = 0x100000 + 4096 * i, 0x900000 + 4096 * i, 0x900000 + 4096 * i
+    g1_shared.p[0] = g0.p[0]
+    forms = ["cnerf_mlp_" + stage + sfx for stage, sfxs in (("bwd", ("", "_pair", "_live", "_pair_live")),
+                                                           ("dgrad", ("", "_pair", "_pair_live", "_bf", "_bf_pair")),
+                                                           ("wgrad", ("", "_pair", "_pair_live", "_bf", "_bf_pair"))) for sfx in sfxs]
+    assert len(forms) == 14 and set(forms) <= set(_lib.SIGNATURES)
+    pair, live = [f for f in forms if "_pair" in f], [f for f in forms if "_live" in f]
+    takes_grads = [f for f in forms if "dgrad" not in f]
+
+    def call(name, **wrong):
+        stage = name.split("_")[2]
+        c = dict(net=[good, good], B=[4, 4], S=[32, 64], grads=[g0, g1], live=FAKE, first=[0, 0])
+        c.update(wrong)
+        args = []
+        for i in range(2 if name in pair else 1):
+            args.append(C.byref(c["net"][i]))
+            if stage != "wgrad":
+                args += [FAKE, FAKE]                                # packed, d_raw
+            args += [c["B"][i], c["S"][i], FAKE, FAKE]              # stash, workspace
+            if stage != "dgrad":
+                args.append(None if c["grads"][i] is None else C.byref(c["grads"][i]))
+        if stage != "dgrad":
+            args.append(0)                                          # accumulate
+        if name in live:
+            args.append(c["live"])
+            if name in pair:
+                args += c["first"]
+        return getattr(lib, name)(*args, None)
+
+    pair_live = [f for f in pair if f in live]
+    assert len(pair_live) == 3 and len(live) == 4 and len(takes_grads) == 9
+    table = [(live, dict(S=[33, 64]), E_ARG), (pair_live, dict(S=[32, 33]), E_ARG)]
+    for bad in (4, -1):
+        table += [(pair_live, dict(first=[bad, 0]), E_ARG), (pair_live, dict(first=[0, bad]), E_ARG)]
+    table += [(pair_live, dict(B=[4, 3]), E_ARG), (pair_live, dict(B=[3, 4]), E_ARG),
+              ([f for f in pair if f in takes_grads], dict(grads=[g0, g1_shared]), E_ARG),
+              (live, dict(live=None), E_ARG),
+              (takes_grads, dict(grads=[None, g1]), E_ARG), ([f for f in pair if f in takes_grads], dict(grads=[g0, None]), E_ARG),
+              (forms, dict(net=[w100, w100]), E_UNSUPPORTED), (forms, dict(net=[w100, good]), E_UNSUPPORTED),
+              # (the second network alone: not on cnerf_mlp_dgrad_bf_pair, which used to launch the first level before it looked)
+              ([f for f in pair if f != "cnerf_mlp_dgrad_bf_pair"], dict(net=[good, w100]), E_UNSUPPORTED)]
+    got = [(name, sorted(wrong.items(), key=str), call(name, **wrong), code) for names, wrong, code in table for name in names]
+    bad = [(name, wrong, rc, code) for name, wrong, rc, code in got if rc != code]
+    assert len(got) >= 80 and not bad, bad
+
+
 def test_rows_of_global_draws_the_whole_batch_and_slices():
     """run_nerf._rows_of_global (strong sharding): with `global_rows = (offset, total)` the random block is drawn for
     the WHOLE batch and sliced, so ranks holding the same generator state reproduce the single-rank stream row for row; without
