@@ -257,19 +257,23 @@ def embed(x: Tensor, L: int) -> Tensor:
     return out.reshape(*lead, 3 + 6 * L)
 
 
+def _mlp_forward_setup(spec: NetSpec, dev, shape, want_stash: bool, pts=None, rays=None, z=None, dirs=None):
+    """The preamble the forward wrappers share -> (lib, net, raw[*shape, raw_ch], stash or None, ray stride, the checked inputs)."""
+    lib, net = _lib.load(), spec.c()
+    pts, rays, z, dirs = _chk(pts, "pts"), _chk(rays, "rays"), _chk(z, "z"), _chk(dirs, "dirs")
+    raw = torch.empty(*shape, spec.raw_ch, device=dev, dtype=torch.float32)
+    stash = None
+    if want_stash:
+        stash = torch.empty(lib.cnerf_mlp_stash_floats(C.byref(net), int(np.prod(shape))), device=dev, dtype=torch.float32)
+    return lib, net, raw, stash, rays.shape[1] if rays is not None else 0, pts, rays, z, dirs
+
+
 def mlp_forward(spec: NetSpec, packed: Tensor, B: int, S: int, *, pts: Optional[Tensor] = None,
                 rays: Optional[Tensor] = None, z: Optional[Tensor] = None, dirs: Optional[Tensor] = None,
                 want_stash: bool = False, live: Optional[Tensor] = None):
     """`live` (device int32 [1], training + rays form only): the batch is padded to the capacity B and only its first live[0] rays
     are real (cnerf_mlp_fwd_live): the launch is sized for B, tiles past the count leave zero raw outputs."""
-    lib, net = _lib.load(), spec.c()
-    pts, rays, z, dirs = _chk(pts, "pts"), _chk(rays, "rays"), _chk(z, "z"), _chk(dirs, "dirs")
-    dev = packed.device
-    raw = torch.empty(B, S, spec.raw_ch, device=dev, dtype=torch.float32)
-    stash = None
-    if want_stash:
-        stash = torch.empty(lib.cnerf_mlp_stash_floats(C.byref(net), B * S), device=dev, dtype=torch.float32)
-    rs = rays.shape[1] if rays is not None else 0
+    lib, net, raw, stash, rs, pts, rays, z, dirs = _mlp_forward_setup(spec, packed.device, (B, S), want_stash, pts, rays, z, dirs)
     if live is not None:
         if not want_stash or rays is None or pts is not None or dirs is not None or live.dtype != torch.int32 or not live.is_cuda:
             raise CnerfError("mlp_forward(live=...) is the training forward on ray rows (no explicit points / directions); "
@@ -314,10 +318,7 @@ def pack_weights_bf(spec: NetSpec, params: Sequence[Tensor], planes: int, out: O
 def mlp_forward_bf(spec: NetSpec, packed_bf: Tensor, planes: int, B: int, S: int, *, pts: Optional[Tensor] = None,
                    rays: Optional[Tensor] = None, z: Optional[Tensor] = None, dirs: Optional[Tensor] = None) -> Tensor:
     """cnerf_mlp_fwd_bf: inference forward on the bf16 / f16 matrix cores (opt-in); `planes` as packed."""
-    lib, net = _lib.load(), spec.c()
-    pts, rays, z, dirs = _chk(pts, "pts"), _chk(rays, "rays"), _chk(z, "z"), _chk(dirs, "dirs")
-    raw = torch.empty(B, S, spec.raw_ch, device=packed_bf.device, dtype=torch.float32)
-    rs = rays.shape[1] if rays is not None else 0
+    lib, net, raw, _, rs, pts, rays, z, dirs = _mlp_forward_setup(spec, packed_bf.device, (B, S), False, pts, rays, z, dirs)
     with _timed(_BF_PROFILE.get(int(planes), "mlp_fwd_bf%d" % planes), B * S):
         _lib.check(lib.cnerf_mlp_fwd_bf(C.byref(net), _p(packed_bf), int(planes), _p(pts), _p(rays), rs, _p(dirs), _p(z), B, S,
                                         _p(raw), _stream()), "cnerf_mlp_fwd_bf")
@@ -328,12 +329,7 @@ def mlp_forward_bf_train(spec: NetSpec, packed_bf: Tensor, B: int, S: int, *, pt
                          rays: Optional[Tensor] = None, z: Optional[Tensor] = None, dirs: Optional[Tensor] = None):
     """cnerf_mlp_fwd_bf_train: the OPT-IN bf16x3 training forward (three bf16 planes per operand, fp32 accumulation) ->
     (raw, stash); the stash is the fp32 kernel's (cnerf_mlp_dgrad / cnerf_mlp_wgrad consume it unchanged)."""
-    lib, net = _lib.load(), spec.c()
-    pts, rays, z, dirs = _chk(pts, "pts"), _chk(rays, "rays"), _chk(z, "z"), _chk(dirs, "dirs")
-    dev = packed_bf.device
-    raw = torch.empty(B, S, spec.raw_ch, device=dev, dtype=torch.float32)
-    stash = torch.empty(lib.cnerf_mlp_stash_floats(C.byref(net), B * S), device=dev, dtype=torch.float32)
-    rs = rays.shape[1] if rays is not None else 0
+    lib, net, raw, stash, rs, pts, rays, z, dirs = _mlp_forward_setup(spec, packed_bf.device, (B, S), True, pts, rays, z, dirs)
     with _timed("mlp_fwd_train_bf3", B * S):
         _lib.check(lib.cnerf_mlp_fwd_bf_train(C.byref(net), _p(packed_bf), _p(pts), _p(rays), rs, _p(dirs), _p(z), B, S,
                                               _p(raw), _p(stash), _stream()), "cnerf_mlp_fwd_bf_train")
@@ -342,13 +338,9 @@ def mlp_forward_bf_train(spec: NetSpec, packed_bf: Tensor, B: int, S: int, *, pt
 
 def mlp_forward_embedded(spec: NetSpec, packed: Tensor, x: Tensor, want_stash: bool = False):
     """NeRF.forward on pre-embedded inputs x[M, in_ch + in_ch_views]."""
-    lib, net = _lib.load(), spec.c()
     x = _chk(x, "x")
     M = x.shape[0]
-    raw = torch.empty(M, spec.raw_ch, device=x.device, dtype=torch.float32)
-    stash = None
-    if want_stash:
-        stash = torch.empty(lib.cnerf_mlp_stash_floats(C.byref(net), M), device=x.device, dtype=torch.float32)
+    lib, net, raw, stash, *_ = _mlp_forward_setup(spec, x.device, (M,), want_stash)
     with _timed("mlp_fwd_train" if want_stash else "mlp_fwd", M):
         _lib.check(lib.cnerf_mlp_fwd_embedded(C.byref(net), _p(packed), _p(x), M, _p(raw), _p(stash), _stream()),
                    "cnerf_mlp_fwd_embedded")

@@ -153,7 +153,7 @@ class FusedAdam:
 
     def bump_epoch(self):
         """The kernel wrote the weights behind autograd's back: invalidate the packed-weight caches keyed on the parameters
-        (run_nerf._packed_gen).  GraphedStep calls this after every replay (the recorded Python of step() ran only once)."""
+        (run_nerf._PanelCache).  GraphedStep calls this after every replay (the recorded Python of step() ran only once)."""
         for p in self.params:
             p._cnerf_epoch = getattr(p, "_cnerf_epoch", 0) + 1
 

@@ -41,84 +41,90 @@ class RayPoints:
         return self.rays[:, None, 0:3] + self.rays[:, None, 3:6] * self.z_vals[..., None]
 
 
-def _pack_state(model):
-    """(kernel tensors, their identity / version key, the cached (key, buffer, generation, [buffer 0, buffer 1]) or None)"""
-    ts = model.kernel_tensors()
-    key = tuple((t.data_ptr(), t._version, getattr(t, "_cnerf_epoch", 0)) for t in ts)
-    return ts, key, model.__dict__.get("_cnerf_packed")
+class _PanelCache:
+    """The kernel-layout copy of one model's weights, one object per model and kind (NeRF.invalidate_packed drops both): the fp32
+    panels (`planes` None) and the bf16- / fp16-plane panels of the opt-in reduced-precision forward and the bf16x3 training kernels
+    (`planes` = the mode's value in ops.PRECISION_PLANES, distinct per mode).  Re-packed only when a parameter changed (optimizer
+    step / load) or the mode did.  Two buffers alternate, so the copy a forward pass used stays intact for its backward without a
+    per-step clone (forward A, step, forward B, backward A is legal): it is overwritten by the SECOND re-pack after it — two
+    parameter updates between a forward and its backward, where the reference itself fails (autograd's version check)."""
+    __slots__ = ("key", "bufs", "gen", "buf", "planes")
+    SLOT = {False: "_cnerf_packed", True: "_cnerf_packed_bf"}       # where a model keeps it, by `planes is not None`
 
+    def __init__(self):
+        self.key, self.bufs, self.gen, self.buf, self.planes = None, [None, None], -1, None, None
 
-def _packed_gen(model):
-    """Kernel-layout weights of `model`, re-packed only when a parameter changed (optimizer step / load).  Two buffers
-    alternate, so the copy a forward pass used stays intact for its backward without a per-step clone: it is overwritten
-    by the SECOND re-pack after it — two parameter updates between a forward and its backward, where the reference
-    itself fails (autograd's version check on the modified weights).  Returns (buffer, generation)."""
-    ts, key, cache = _pack_state(model)
-    if cache is None or cache[0] != key:
-        gen = 0 if cache is None else cache[2] + 1
-        bufs = [None, None] if cache is None else cache[3]
-        with torch.no_grad():
-            bufs[gen & 1] = ops.pack_weights(model.spec(), ts, bufs[gen & 1])
-        cache = (key, bufs[gen & 1], gen, bufs)
-        model.__dict__["_cnerf_packed"] = cache
-    return cache[1], cache[2]
+    @staticmethod
+    def probe(model, planes=None):
+        """(the model's cache of this kind or None, its kernel tensors, their identity / version key now)"""
+        ts = model.kernel_tensors()
+        key = tuple((t.data_ptr(), t._version, getattr(t, "_cnerf_epoch", 0)) for t in ts)
+        return model.__dict__.get(_PanelCache.SLOT[planes is not None]), ts, key if planes is None else (planes,) + key
+
+    def next_out(self, planes=None):
+        """The buffer the next re-pack overwrites (None: the packer allocates it; always after a change of `planes`)."""
+        return self.bufs[(self.gen + 1) & 1] if planes == self.planes else None
+
+    def commit(self, model, key, buf, planes=None):
+        """`buf` holds the panels of `key`: the next generation (monotonic also across a change of `planes`, which drops both buffers)."""
+        if planes != self.planes:
+            self.bufs, self.planes = [None, None], planes
+        self.gen += 1
+        self.bufs[self.gen & 1] = self.buf = buf
+        self.key = key
+        model.__dict__[self.SLOT[planes is not None]] = self
+
+    @staticmethod
+    def get(model, planes=None):
+        """-> (buffer, generation) of the current panels of `model`, re-packed first when stale."""
+        c, ts, key = _PanelCache.probe(model, planes)
+        if c is None or c.key != key:
+            c = _PanelCache() if c is None else c
+            out = c.next_out(planes)
+            with torch.no_grad():
+                buf = ops.pack_weights(model.spec(), ts, out) if planes is None else ops.pack_weights_bf(model.spec(), ts, planes, out)
+            c.commit(model, key, buf, planes)
+        return c.buf, c.gen
+
+    def still_valid(self, gen, buf):
+        """May a backward still read `buf`, packed as generation `gen`?  Not after a second re-pack.  The plane panels also insist on
+        `buf` being one of the two buffers: after invalidate_packed() + a new forward they refuse, the fp32 panels accept."""
+        return self.gen - gen <= 1 and (self.planes is None or any(b is buf for b in self.bufs))
 
 
 def _packed(model):
-    return _packed_gen(model)[0]
+    return _PanelCache.get(model)[0]
+
+
+def _packed_bf(model, planes):
+    return _PanelCache.get(model, planes)[0]
+
+
+def _still_valid(model, gen, buf, planes=None):
+    c = model.__dict__.get(_PanelCache.SLOT[planes is not None])
+    return c is not None and c.still_valid(gen, buf)
 
 
 def _prepack_pair(model_a, model_b):
     """render_rays is about to query both networks: when BOTH kernel-layout copies are stale (every training step: the optimizer
-    just wrote both) re-pack them with one launch instead of one each.  Same cache protocol as _packed_gen."""
+    just wrote both) re-pack them with one launch instead of one each."""
     if model_a is None or model_b is None or model_a is model_b:
         return
     st = []
     for m in (model_a, model_b):
         if not hasattr(m, "kernel_tensors"):
             return
-        ts, key, cache = _pack_state(m)
-        if cache is not None and cache[0] == key:
+        c, ts, key = _PanelCache.probe(m)
+        if c is not None and c.key == key:
             return                               # (at most one is stale: its own query re-packs it)
-        gen = 0 if cache is None else cache[2] + 1
-        bufs = [None, None] if cache is None else cache[3]
-        st.append((m, ts, key, gen, bufs))
-    if st[0][1][0].device != st[1][1][0].device or not st[0][1][0].is_cuda:
+        st.append((m, ts, key, _PanelCache() if c is None else c))
+    (ma, tsa, ka, ca), (mb, tsb, kb, cb) = st
+    if tsa[0].device != tsb[0].device or not tsa[0].is_cuda:
         return
-    (ma, tsa, ka, ga, ba), (mb, tsb, kb, gb, bb) = st
     with torch.no_grad():
-        ba[ga & 1], bb[gb & 1] = ops.pack_weights_pair(ma.spec(), tsa, ba[ga & 1], mb.spec(), tsb, bb[gb & 1])
-    ma.__dict__["_cnerf_packed"] = (ka, ba[ga & 1], ga, ba)
-    mb.__dict__["_cnerf_packed"] = (kb, bb[gb & 1], gb, bb)
-
-
-def _packed_bf_gen(model, planes):
-    """bf16- / fp16-plane panels of `model` (opt-in reduced-precision forward / the bf16x3 training kernels; `planes` = the mode's
-    value in ops.PRECISION_PLANES, distinct per mode), re-packed when a parameter or the mode
-    changed.  Same two-buffer / generation protocol as _packed_gen: the copy a training forward used survives ONE optimizer step
-    before its backward (forward A, step, forward B, backward A is legal with the fp32 panels, so it is here); a second re-pack
-    overwrites it and the backward refuses (_packed_bf_still_valid).  Returns (buffer, generation)."""
-    ts = model.kernel_tensors()
-    key = (planes,) + tuple((t.data_ptr(), t._version, getattr(t, "_cnerf_epoch", 0)) for t in ts)
-    cache = model.__dict__.get("_cnerf_packed_bf")
-    if cache is None or cache[0] != key:
-        same_planes = cache is not None and cache[0][0] == planes
-        gen = cache[2] + 1 if cache is not None else 0          # (monotonic also across a change of plane count)
-        bufs = cache[3] if same_planes else [None, None]
-        with torch.no_grad():
-            bufs[gen & 1] = ops.pack_weights_bf(model.spec(), ts, planes, bufs[gen & 1])
-        cache = (key, bufs[gen & 1], gen, bufs)
-        model.__dict__["_cnerf_packed_bf"] = cache
-    return cache[1], cache[2]
-
-
-def _packed_bf(model, planes):
-    return _packed_bf_gen(model, planes)[0]
-
-
-def _packed_bf_still_valid(model, gen, buf):
-    cache = model.__dict__.get("_cnerf_packed_bf")
-    return cache is not None and cache[2] - gen <= 1 and any(b is buf for b in cache[3])
+        pa, pb = ops.pack_weights_pair(ma.spec(), tsa, ca.next_out(), mb.spec(), tsb, cb.next_out())
+    ca.commit(ma, ka, pa)
+    cb.commit(mb, kb, pb)
 
 
 # Training arithmetic: "fp32" (default: exact fp32 MFMA, the arithmetic every parity statement and the headline bench line are
@@ -142,11 +148,6 @@ def training_precision(model):
     if prec not in ("fp32", "bf16x3"):
         raise ValueError("training_precision must be 'fp32' or 'bf16x3'")
     return prec
-
-
-def _packed_still_valid(model, gen):
-    cache = model.__dict__.get("_cnerf_packed")
-    return cache is not None and cache[2] - gen <= 1
 
 
 def _probe_engine_query():
@@ -216,9 +217,20 @@ def _engine_accumulates(p):
 MERGE_BWD = os.environ.get("CNERF_MERGE_BWD", "1") != "0"
 
 
+class _LevelJob:
+    """What the MLP backward of one level launches with, taken from its node (`ctx`) and the gradient of its output.  `d_raw` is
+    made contiguous here: when the fine node parks, in ITS backward."""
+    __slots__ = ("spec", "packed", "packed_bf", "d_raw", "B", "S", "stash", "params", "model", "live", "skip")
+
+    def __init__(self, ctx, g_raw):
+        self.spec, self.packed, self.packed_bf, self.d_raw = ctx.spec, ctx.packed, ctx.packed_bf, g_raw.contiguous()
+        self.B, self.S, self.stash, self.params, self.model = ctx.B, ctx.S, ctx.stash, ctx.params, ctx.model
+        self.live, self.skip = ctx.live, ctx.skip
+
+
 class _LevelPair:
     """Links the coarse and the fine _MlpFn node of one render_rays call.  The fine node runs first in the backward pass
-    (it was created last); if the engine is going to run the coarse node too, it parks its inputs here and the coarse node
+    (it was created last); if the engine is going to run the coarse node too, it parks its _LevelJob here and the coarse node
     launches both."""
     __slots__ = ("coarse", "fine", "parked")
 
@@ -256,22 +268,15 @@ def _take_dropped(*param_lists):
     return fresh
 
 
-def _report_ready(model, direct):
-    """One backward node of `model` has accumulated into the flat gradient: tell the GradReducer when it was the last."""
-    if hasattr(model, "_cnerf_pending"):
-        model._cnerf_pending -= 1
-        if direct and model._cnerf_pending <= 0:
-            model._cnerf_reducer.network_ready(model)
-
-
-def _report_ready_pair(model_a, model_b):
-    """The merged backward finished BOTH networks at once: report them together, so that a reducer that owns both sends their
-    (adjacent) slices of the flat gradient as ONE message instead of two back-to-back ones."""
+def _report_ready(models, direct):
+    """One backward node of each of `models` has run: on the direct route (it accumulated into the flat gradient) tell the
+    GradReducer of those it was the last node of.  The merged backward finishes BOTH networks at once: reported together, so that a
+    reducer that owns both sends their (adjacent) slices of the flat gradient as ONE message instead of two back-to-back ones."""
     ready = []
-    for m in (model_a, model_b):
+    for m in models:
         if hasattr(m, "_cnerf_pending"):
             m._cnerf_pending -= 1
-            if m._cnerf_pending <= 0:
+            if direct and m._cnerf_pending <= 0:
                 ready.append(m)
     if len(ready) == 2 and ready[0]._cnerf_reducer is ready[1]._cnerf_reducer:
         ready[0]._cnerf_reducer.networks_ready(ready)
@@ -280,49 +285,70 @@ def _report_ready_pair(model_a, model_b):
             m._cnerf_reducer.network_ready(m)
 
 
+def _run_single(job, direct):
+    """One level on its own -> its gradients (on the direct route: the parameters' views of the flat gradient, written in place)."""
+    out = [p.grad for p in job.params] if direct else None
+    grads = ops.mlp_backward(job.spec, job.packed, job.d_raw, job.B, job.S, job.stash, grads=out,
+                             accumulate=direct and not _take_dropped(job.params), packed_bf=job.packed_bf, live=job.live)
+    _report_ready([job.model], direct)
+    return grads
+
+
+def _run_pair(fine, coarse):
+    """Both levels as one launch, on the direct route (bf16x3 only when both carry a plane buffer: ops.mlp_backward_pair)."""
+    live = coarse.live
+    ops.mlp_backward_pair(fine.spec, fine.packed, fine.d_raw, fine.B, fine.S, fine.stash, [p.grad for p in fine.params],
+                          coarse.spec, coarse.packed, coarse.d_raw, coarse.B, coarse.S, coarse.stash, [p.grad for p in coarse.params],
+                          accumulate=not _take_dropped(fine.params, coarse.params), packed_bf0=fine.packed_bf,
+                          packed_bf1=coarse.packed_bf, live=live, first0=fine.skip if live is not None else 0,
+                          first1=coarse.skip if live is not None else 0)
+    _report_ready([fine.model, coarse.model], True)
+
+
 class _MlpFn(torch.autograd.Function):
     """Fused gamma(x), gamma(d) + MLP (replaces R:37-52 + H:44-45 + H:107-130 and their autograd)."""
 
     @staticmethod
     def forward(ctx, model, B, S, pts, rays, z, dirs, emb, live, skip, *params):
         spec = model.spec()
-        packed, gen = _packed_gen(model)
+        packed, gen = _PanelCache.get(model)
         if any(ctx.needs_input_grad[3:8]):
             # fail loudly rather than return silently-missing gradients: the reference never differentiates through the
             # sample positions (z is detached at R:397, rays come from the data), and the dgrad kernel stops at layer 0
             raise ops.CnerfError("gradients w.r.t. sample positions / rays / view directions / pre-embedded inputs are "
                                  "not implemented (only w.r.t. the network parameters)")
         train = any(ctx.needs_input_grad[10:])
+        packed_bf = bf_gen = use_live = None
         if emb is not None:      # NeRF.forward(x) on pre-embedded inputs
             raw, stash = ops.mlp_forward_embedded(spec, packed, emb, want_stash=train)
         elif train and training_precision(model) == "bf16x3":
             # OPT-IN second training arithmetic (never the default): the forward GEMMs on the bf16 matrix cores at three planes
             # per operand; same stash, so the backward below is unchanged.  `packed` (fp32 panels) still feeds the dgrad.
-            ctx.packed_bf, ctx.packed_bf_gen = _packed_bf_gen(model, 3)
-            raw, stash = ops.mlp_forward_bf_train(spec, ctx.packed_bf, B, S, pts=pts, rays=rays, z=z, dirs=dirs)
+            packed_bf, bf_gen = _PanelCache.get(model, 3)
+            raw, stash = ops.mlp_forward_bf_train(spec, packed_bf, B, S, pts=pts, rays=rays, z=z, dirs=dirs)
         else:
             # `live` (device int32 [1]; RayPoints.live): the batch is padded to its capacity B and only the first live[0] rays are
             # real — the training kernels stop there (run_nerf_view.ss_step_loss: the one-render in-loop consistency step).  Every
             # other route simply processes the padding rays too (they are valid rays whose loss weight is 0: same result, more work).
             use_live = live if (train and pts is None and dirs is None and S % 32 == 0) else None
             raw, stash = ops.mlp_forward(spec, packed, B, S, pts=pts, rays=rays, z=z, dirs=dirs, want_stash=train, live=use_live)
-            ctx.live = use_live
-            # `skip` (with live): this level's first `skip` rays will get zero seeds — the merged backward leaves them out
-            ctx.skip = int(skip) if (use_live is not None and skip) else 0
         if train:
             ctx.spec, ctx.B, ctx.S, ctx.stash, ctx.packed, ctx.packed_gen = spec, B, S, stash, packed, gen
             ctx.params, ctx.model = params, model
+            ctx.packed_bf, ctx.packed_bf_gen, ctx.live, ctx.pair = packed_bf, bf_gen, use_live, None    # (pair: _link_levels sets it)
+            # `skip` (with live): this level's first `skip` rays will get zero seeds — the merged backward leaves them out
+            ctx.skip = int(skip) if (use_live is not None and skip) else 0
             if hasattr(model, "_cnerf_pending"):     # distributed.GradReducer counts this network's backward nodes
                 model._cnerf_pending += 1
         return raw
 
     @staticmethod
     def backward(ctx, g_raw):
-        params = ctx.params
-        if not _packed_still_valid(ctx.model, ctx.packed_gen):
+        params, pair = ctx.params, ctx.pair
+        if not _still_valid(ctx.model, ctx.packed_gen, ctx.packed):
             raise ops.CnerfError("the network's weights were updated twice between this forward pass and its backward "
                                  "(the kernel-layout copy it used has been re-packed)")
-        if getattr(ctx, "packed_bf", None) is not None and not _packed_bf_still_valid(ctx.model, ctx.packed_bf_gen, ctx.packed_bf):
+        if ctx.packed_bf is not None and not _still_valid(ctx.model, ctx.packed_bf_gen, ctx.packed_bf, planes=3):
             raise ops.CnerfError("the network's weights were updated twice between this bf16x3 forward pass and its backward "
                                  "(the bf16-plane copy it used has been re-packed)")
         # Parameters owned by FusedAdam carry their .grad as a view into the flat gradient buffer: under loss.backward()
@@ -331,39 +357,25 @@ class _MlpFn(torch.autograd.Function):
         # torch.autograd.grad() on FusedAdam-owned ones, where the engine captures gradients instead of accumulating them
         # — takes the tensor route and leaves the flat buffer untouched.
         direct = _direct_ok(ctx.needs_input_grad[10:], params) and _engine_accumulates(params[0])
-        pair = getattr(ctx, "pair", None)
         nret = (None,) * (10 + len(params))
-        live = getattr(ctx, "live", None)
+        job = _LevelJob(ctx, g_raw)
+        parked = grads = None
         if direct and pair is not None and pair.fine() is ctx and pair.parked is None:
             c = pair.coarse()
             # park only when the coarse node is certain to run in this very pass, on the direct route as well
             if (c is not None and c.stash is not None and _direct_ok(c.needs_input_grad[10:], c.params)
                     and _ENGINE_QUERY(c)):
-                pair.parked = (ctx.spec, ctx.packed, g_raw.contiguous(), ctx.B, ctx.S, ctx.stash, [p.grad for p in params],
-                               ctx.model, getattr(ctx, "packed_bf", None), params, live, getattr(ctx, "skip", 0))
+                pair.parked = job
                 ctx.stash = ctx.packed = ctx.params = ctx.model = None
                 return nret
-        parked = None
         if pair is not None and pair.coarse() is ctx and pair.parked is not None:
             parked, pair.parked = pair.parked, None
-        if parked is not None and direct and parked[10] is live and (live is None or parked[3] == ctx.B):
-            fs, fp, fg, fB, fS, fst, fgr, fmodel, fbf, fparams, _flive, fskip = parked
-            ops.mlp_backward_pair(fs, fp, fg, fB, fS, fst, fgr, ctx.spec, ctx.packed, g_raw.contiguous(), ctx.B, ctx.S,
-                                  ctx.stash, [p.grad for p in params], accumulate=not _take_dropped(fparams, params), packed_bf0=fbf,
-                                  packed_bf1=getattr(ctx, "packed_bf", None), live=live, first0=fskip if live is not None else 0,
-                                  first1=getattr(ctx, "skip", 0) if live is not None else 0)
-            _report_ready_pair(fmodel, ctx.model)
-            ctx.stash = ctx.packed = ctx.params = ctx.model = None
-            return nret
-        if parked is not None:        # (cannot happen — the fine node checked this node's route — but never drop a gradient)
-            fs, fp, fg, fB, fS, fst, fgr, fmodel, fbf, fparams, flive, _fskip = parked
-            ops.mlp_backward(fs, fp, fg, fB, fS, fst, grads=fgr, accumulate=not _take_dropped(fparams), packed_bf=fbf, live=flive)
-            _report_ready(fmodel, True)
-        out = [p.grad for p in params] if direct else None
-        grads = ops.mlp_backward(ctx.spec, ctx.packed, g_raw.contiguous(), ctx.B, ctx.S, ctx.stash, grads=out,
-                                 accumulate=direct and not _take_dropped(params), packed_bf=getattr(ctx, "packed_bf", None),
-                                 live=live)
-        _report_ready(ctx.model, direct)
+        if parked is not None and direct and parked.live is job.live and (job.live is None or parked.B == job.B):
+            _run_pair(parked, job)
+        else:
+            if parked is not None:    # (cannot happen — the fine node checked this node's route — but never drop a gradient)
+                _run_single(parked, True)
+            grads = _run_single(job, direct)
         ctx.stash = ctx.packed = ctx.params = ctx.model = None
         return nret if direct else (None,) * 10 + tuple(grads)
 

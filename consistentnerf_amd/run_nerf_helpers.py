@@ -146,7 +146,7 @@ class NeRF(nn.Module):
     inference_precision = "fp32"
 
     def invalidate_packed(self):
-        """Forget the kernel-layout copy of the weights.  The cache key (run_nerf._packed) sees optimizer steps,
+        """Forget the kernel-layout copy of the weights.  The cache key (run_nerf._PanelCache) sees optimizer steps,
         load_state_dict() and every autograd-visible in-place edit, but NOT writes through `p.data` (manual EMA /
         re-initialisation code: `p.data.mul_()`, `p.data.copy_()`), which bump no version counter — call this after such
         an edit."""

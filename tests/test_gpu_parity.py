@@ -2681,6 +2681,57 @@ def test_packed_weights_double_buffer(dev):
         l.backward()
 
 
+def test_packed_weights_repack_launches(dev, monkeypatch):
+    """How often render_rays re-packs the kernel-layout weights: one PAIR launch when an optimizer step left both networks' copies
+    stale, one single launch when only one network changed, none when nothing did — and what the cache then holds is bit for bit
+    what ops.pack_weights makes of the same parameters."""
+    from consistentnerf_amd import ops, run_nerf as R
+    from consistentnerf_amd.optim import FusedAdam
+    coarse, _ = make_model(4, 128, True, 5, 95, dev)
+    fine, _ = make_model(4, 128, True, 5, 96, dev)
+    kw = _kwargs(coarse, fine, 16, 16, 0.0, False, 0.0, False)
+    rays, tgt = T(I.ray_batch(40, seed=6), dev), torch.rand(40, 3, device=dev)
+    opt_c, opt_f = FusedAdam(list(coarse.parameters()), lr=1e-2), FusedAdam(list(fine.parameters()), lr=1e-2)
+    pack, pack_pair, n = ops.pack_weights, ops.pack_weights_pair, {"single": 0, "pair": 0}
+
+    def counted(kind, fn):
+        def call(*a, **k):
+            n[kind] += 1
+            return fn(*a, **k)
+        return call
+    monkeypatch.setattr(ops, "pack_weights", counted("single", pack))
+    monkeypatch.setattr(ops, "pack_weights_pair", counted("pair", pack_pair))
+
+    def packs_of(render):
+        n.update(single=0, pair=0)
+        render()
+        got = (n["single"], n["pair"])
+        for m in (coarse, fine):
+            # (every region of the layout is padded to 64 floats and no pack writes the padding: the reference pack goes into a
+            # copy of the cached buffer, so the comparison covers exactly the words a pack writes)
+            have = R._packed(m)
+            assert torch.equal(have, pack(m.spec(), m.kernel_tensors(), have.clone()))
+        assert (n["single"], n["pair"]) == got          # (reading the cache packed nothing)
+        return got
+
+    def fwd():
+        o = R.render_rays(rays, **kw)
+        return R.img2mse(o["rgb_map"], tgt) + (R.img2mse(o["rgb0"], tgt) if o["rgb0"].requires_grad else 0.0)
+    fwd().backward()
+    opt_c.step()
+    opt_f.step()
+    assert packs_of(fwd) == (0, 1)
+    assert packs_of(fwd) == (0, 0)
+    coarse.requires_grad_(False)                      # from here on only the fine network changes
+    for p in coarse.parameters():
+        p.grad = None
+    opt_f.zero_grad()
+    fwd().backward()
+    opt_f.step()
+    assert packs_of(fwd) == (1, 0)
+    assert packs_of(fwd) == (0, 0)
+
+
 # ------------------------------------------------------------------------------------------------
 # round 2: BASELINE configs[4] (C5) and configs[2] (C3) at FULL size, through size-independent properties
 def test_c5_full_frame_properties(dev):

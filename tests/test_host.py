@@ -167,8 +167,8 @@ for mean in (True, False):
     opt.flat_grad.copy_(mine)
     mods[1]._cnerf_pending = 2                     # a network with two backward nodes reports after the second one
     import consistentnerf_amd.run_nerf as RN
-    RN._report_ready(mods[1], True); assert not red._done
-    RN._report_ready(mods[1], True); assert red._done == {id(mods[1])}     # fine-first order; mods[0] never reports
+    RN._report_ready([mods[1]], True); assert not red._done
+    RN._report_ready([mods[1]], True); assert red._done == {id(mods[1])}     # fine-first order; mods[0] never reports
     red.finish()
     want = torch.arange(28, dtype=torch.float32) * sum(r + 1 for r in range(world)) * ((1.0 / world) if mean else 1.0)
     assert torch.allclose(opt.flat_grad, want), (opt.flat_grad, want)
@@ -177,7 +177,7 @@ for mean in (True, False):
 red = D.GradReducer(opt, mods, mean=False)
 opt.flat_grad.copy_(torch.arange(28, dtype=torch.float32) * (rank + 1))
 mods[0]._cnerf_pending = mods[1]._cnerf_pending = 1
-RN._report_ready_pair(mods[1], mods[0])
+RN._report_ready([mods[1], mods[0]], True)
 assert red.messages == 1 and red._done == {id(mods[0]), id(mods[1])}
 red.finish()
 assert red.messages == 1 and red.steps == 1
@@ -185,7 +185,7 @@ assert torch.allclose(opt.flat_grad, torch.arange(28, dtype=torch.float32) * sum
 # a network evaluated twice (two pending nodes) next to one evaluated once: the pair report only releases what is final
 opt.flat_grad.zero_()
 mods[0]._cnerf_pending, mods[1]._cnerf_pending = 2, 1
-RN._report_ready_pair(mods[1], mods[0])
+RN._report_ready([mods[1], mods[0]], True)
 assert red._done == {id(mods[1])} and red.messages == 2
 red.finish()
 assert red.messages == 3
@@ -790,3 +790,101 @@ def test_bench_dump_outputs_stays_within_its_limit_with_a_fixed_sample(tmp_path)
     s = got["big"]
     assert s.ndim == 1 and 0.3e6 < s.size == written["big"] < 3e6 and np.all(np.diff(s) > 0) and float(s.max()) < 3e6
     assert np.array_equal(np.load(tmp_path / "b" / "big.npy"), s + 1)
+
+
+def _panel_cache_api():
+    """run_nerf's packed-weight cache as (get(model, planes) -> (buffer, generation), valid(model, generation, buffer, planes))."""
+    from consistentnerf_amd import run_nerf as R
+    return R._PanelCache.get, R._still_valid
+
+
+# One row per step of a sequence on one model: (action, argument, expectation).  Actions: "get" (argument: planes, None for the fp32
+# panels) expects (packs so far, buffer, generation, the `out` its pack was given); "edit" is an in-place parameter edit under
+# no_grad, "epoch" a FusedAdam.bump_epoch-style `_cnerf_epoch` increment without a version change, "drop" invalidate_packed().  Every
+# row then lists which earlier rows' (generation, buffer) a backward may still use: {row: expected} — a (fp32, planes) pair where
+# the two kinds differ.  Buffers are named by letter: a new letter must be a new tensor, a known one that very tensor object.
+_PANEL_COMMON = [            # (run once on the fp32 panels and once with every `planes` set to 3)
+    ("get", None, (1, "A", 0, None), {0: True}),
+    ("get", None, (1, "A", 0, None), {0: True, 1: True}),                      # no change: no pack, same buffer
+    ("edit", None, None, {}),
+    ("get", None, (2, "B", 1, None), {0: True, 3: True}),                      # the other slot; one re-pack later the first is intact
+    ("edit", None, None, {}),
+    ("get", None, (3, "A", 2, "A"), {0: False, 3: True, 5: True}),             # back into the first slot, reused as `out`
+    ("epoch", None, None, {}),
+    ("get", None, (4, "B", 3, "B"), {0: False, 3: False, 5: True, 7: True}),
+    ("drop", None, None, {0: False, 5: False, 7: False}),                      # invalidate_packed(), no new forward: both refuse
+    ("get", None, (5, "C", 0, None), {0: (True, False), 5: (True, False), 7: (True, False), 9: True}),   # ... a new forward: they differ
+    ("edit", None, None, {}),
+    ("get", None, (6, "D", 1, None), {7: (True, False), 9: True, 11: True}),
+]
+_PANEL_PLANES = [
+    ("get", 3, (1, "A", 0, None), {0: True}),
+    ("get", 2, (2, "B", 1, None), {0: False, 1: True}),                        # another mode: re-pack, both buffers dropped, count goes on
+    ("get", 2, (2, "B", 1, None), {1: True}),
+    ("get", 3, (3, "C", 2, None), {0: False, 1: False, 3: True}),              # and back: again
+    ("edit", None, None, {}),
+    ("get", 3, (4, "D", 3, None), {3: True, 5: True}),
+    ("edit", None, None, {}),
+    ("get", 3, (5, "C", 4, "C"), {3: False, 5: True, 7: True}),
+]
+
+
+def test_packed_weight_cache_protocol(monkeypatch):
+    """The cache of kernel-layout weights behind every forward (run_nerf._PanelCache), on CPU modules with stand-in packers: when it
+    re-packs, into which of its two buffers, how generations count, and which copies a backward may still read — the fp32 and the
+    plane panels alike, except after invalidate_packed() followed by a new forward, where the fp32 panels accept an old copy
+    (generation distance alone) and the plane panels refuse it (buffer identity).  The tables were written from, and pass against,
+    the three separate functions this class replaced."""
+    from consistentnerf_amd import ops, run_nerf as R
+    from consistentnerf_amd.run_nerf_helpers import NeRF
+    get, valid = _panel_cache_api()
+    calls = []                   # the `out` argument of every pack
+
+    def pack(spec, params, out=None):
+        calls.append(out)
+        return out if out is not None else torch.zeros(4)
+
+    def pack_bf(spec, params, planes, out=None):
+        calls.append(out)
+        return out if out is not None else torch.zeros(4, dtype=torch.uint8)
+    monkeypatch.setattr(ops, "pack_weights", pack)
+    monkeypatch.setattr(ops, "pack_weights_bf", pack_bf)
+    monkeypatch.setattr(ops, "pack_weights_pair", lambda *a: 1 / 0)
+    for vd in (True, False):
+        for table, planes_all in ((_PANEL_COMMON, None), (_PANEL_COMMON, 3), (_PANEL_PLANES, None)):
+            m = NeRF(D=2, W=16, input_ch=63, output_ch=4 if vd else 5, skips=[4], input_ch_views=27 if vd else 0, use_viewdirs=vd)
+            del calls[:]
+            named, handles = {}, {}
+            for row, (action, arg, expect, validity) in enumerate(table):
+                where = (vd, planes_all, row)
+                planes = arg if planes_all is None else planes_all
+                if action == "get":
+                    buf, gen = get(m, planes)
+                    n, name, want_gen, out = expect
+                    assert (len(calls), gen) == (n, want_gen), where
+                    assert named.setdefault(name, buf) is buf and sum(b is buf for b in named.values()) == 1, where
+                    assert calls[-1] is (None if out is None else named[out]), where
+                    handles[row] = (gen, buf, planes)
+                elif action == "edit":
+                    with torch.no_grad():
+                        m.kernel_tensors()[2].add_(1.0)
+                elif action == "epoch":
+                    t = m.kernel_tensors()[1]
+                    v = t._version
+                    t._cnerf_epoch = getattr(t, "_cnerf_epoch", 0) + 1
+                    assert t._version == v
+                else:
+                    m.invalidate_packed()
+                for r, want in validity.items():
+                    gen, buf, pl = handles[r]
+                    want = want[pl is not None] if isinstance(want, tuple) else want
+                    assert valid(m, gen, buf, pl) is want, where + (r,)
+            # the module-level names other code imports return the current buffer and do not pack again
+            n = len(calls)
+            last = handles[max(handles)]
+            assert (R._packed(m) if last[2] is None else R._packed_bf(m, last[2])) is last[1] and len(calls) == n
+    # the pair form leaves everything to the single form when it cannot apply (here: no model, one model twice, not on a GPU)
+    a, b = (NeRF(D=2, W=16, input_ch=63, output_ch=4, skips=[4], input_ch_views=27, use_viewdirs=True) for _ in range(2))
+    for pair in ((None, a), (a, None), (a, a), (a, object()), (a, b)):
+        R._prepack_pair(*pair)
+    assert "_cnerf_packed" not in a.__dict__ and "_cnerf_packed" not in b.__dict__
