@@ -67,6 +67,12 @@ class ClossTail(C.Structure):
                 ("P", C.c_int32), ("n", C.c_int32)]
 
 
+class LossForm(C.Structure):
+    """struct cnerf_lossform"""
+    _fields_ = [("rgb_form", C.c_int32), ("depth_form", C.c_int32), ("lp_coef", C.c_float), ("temp_rgb", C.c_void_p),
+                ("temp_depth", C.c_void_p)]
+
+
 class SsWarp(C.Structure):
     """struct cnerf_ss_warp"""
     _fields_ = [("ref", RayGen), ("w2c", C.c_float * 12), ("flip", C.c_int32), ("image_ch", C.c_int32), ("thr0", C.c_float)]
@@ -83,6 +89,7 @@ class PixelBatch(C.Structure):
 
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _ClossP = C.POINTER(Closs)
+_FormP = C.POINTER(LossForm)
 _RngP = C.POINTER(Rng)
 _NetP, _PtrsP = C.POINTER(Net), C.POINTER(Ptrs)
 
@@ -167,6 +174,12 @@ SIGNATURES = {
     "cnerf_closs_finish_ssim": (_i, [C.POINTER(ClossTail), _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cnerf_composite_bwd_closs_ssim": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i64, _i, _i, _ClossP, _vp, _vp, _vp, _vp, _f, _f, _f, _vp,
                                             _i64, _f, _vp, _i64, _vp, _vp]),
+    "cnerf_lossform_ws_floats": (_i64, [_i64]),
+    "cnerf_composite_fwd_lossform": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i64, _i, _i, _ClossP, _FormP, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cnerf_lossform_finish": (_i, [C.POINTER(ClossTail), _FormP, _FormP, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cnerf_composite_bwd_lossform": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i64, _i, _i, _ClossP, _FormP, _vp, _vp, _vp, _vp, _f, _f, _f, _f,
+                                          _vp, _i64, _f, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "cnerf_softmask_loss": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "cnerf_ssim_ws_floats": (_i64, [_i64, _i64, _i64, _i64, _i]),
     "cnerf_ssim_fwd": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "cnerf_ssim_bwd_ws_floats": (_i64, [_i64, _i64, _i64, _i64, _i]),

@@ -41,12 +41,36 @@ struct MseBwd {
 // depth maps) sums them in index order, normalises by the (possibly global) counts and leaves the three seed weights the backward
 // uses.  Backward: seed_rgb = (w_m (rgb - target)) * g_rgb, seed_depth = (w_d (depth / far - prior / far)) * g_depth (+ the patch
 // term's d_depth * g_patch on the patch rays) — the operations of masked_loss_k / patch_depth_loss_k and autograd's `d * g`.
+// The other live loss forms of V / VC (cnerf_lossform, include/cnerf.h): what the FORMS instantiations of the two kernels add.  The
+// new depth forms divide by far as ATen divides a tensor by a scalar, x * (1 / far): their literal lines run on ATen.
+struct LossForm {
+  int rgb_form = CNERF_RGB_HARDMASK, depth_form = CNERF_DEPTH_HARDMASK;
+  float lp_coef = 0.f, coef = 0.f;   // (coef = hardmask_coef: the backward's weight of the mask == 0 depth seeds)
+  const float* temp_rgb = nullptr;
+  const float* temp_depth = nullptr;
+};
+// weight and weighted powers of one residual under a soft form: softlp (V:58) w = |d|^coef + 1; softmask (V:50) w = exp(d^2 / t)
+__device__ __forceinline__ void soft_sums(bool softmask, float d, float coef, float t, double& sw, double& swd2, double& swd4) {
+  const float d2 = d * d;
+  const float w = softmask ? expf(d2 / t) : powf(fabsf(d), coef) + 1.f;
+  sw += (double)w;
+  swd2 += (double)(w * d2);
+  if (softmask) swd4 += (double)(w * (d2 * d2));
+}
+// d loss / d residual of the same, times inv = 1 / sum(w): soft_lp_k's / softmask_k's expression (loss.hip)
+__device__ __forceinline__ float soft_seed(bool softmask, float d, float coef, float t, float inv) {
+  if (softmask) return (expf((d * d) / t) * (2.f * d + 2.f * ((d * d) * d) / t)) * inv;
+  const float p = powf(fabsf(d), coef);
+  return (d * (coef * p + 2.f * (p + 1.f))) * inv;
+}
+
 struct ClossFwd {
   const float* tgt;      // [B,3]
   const float* mask;     // [B] or nullptr (every ray in the m == 1 set)
   const float* prior;    // [B] or nullptr (no depth term)
   float far;
-  double* part;          // [5][gridDim.x]
+  double* part;          // [5][gridDim.x]; the FORMS kernels: [CNERF_LOSSFORM_SLOTS][gridDim.x]
+  LossForm form;         // the FORMS kernels only
 };
 struct ClossBwd {
   const float* rgb;      // forward rgb_map [B,3]
@@ -63,6 +87,9 @@ struct ClossBwd {
   const float* ssim_d;   // [n_ssim * 3] d ssim_level / d rgb of this level (cnerf_closs_finish_ssim), or nullptr
   int64_t n_ssim;
   float ssim_w;
+  LossForm form;         // the FORMS kernel only: stats = the level's 8 floats of cnerf_lossform_finish
+  const float* d_temp;   // [2] the level's (rgb_w dL_rgb / dt, depth_w dL_depth / dt), or nullptr
+  float* g_temp;         // [2] <- d_temp * g
 };
 
 struct Sample {
@@ -192,7 +219,7 @@ __device__ __forceinline__ double composite_ray(const float* __restrict__ raw, i
 }
 
 // WV = rays (waves) per workgroup: WAVES for the plain form; MSE_WAVES for the loss form (fewer, fatter partials and tickets)
-template <int C, int WV>
+template <int C, int WV, bool FORMS = false>
 __global__ __launch_bounds__(WV * 64) void composite_fwd_k(const float* __restrict__ raw, int ch,
                                                               const float* __restrict__ z,
                                                               const float* __restrict__ rays, int rs,
@@ -204,6 +231,69 @@ __global__ __launch_bounds__(WV * 64) void composite_fwd_k(const float* __restri
   const int lane = threadIdx.x & 63;
   const int64_t b = (int64_t)blockIdx.x * WV + (threadIdx.x >> 6);
   float o4[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (FORMS) {
+    // the v6 masked-loss variant below with a form per kind of term: CNERF_LOSSFORM_SLOTS partials per workgroup (cnerf.h)
+    constexpr int NS = CNERF_LOSSFORM_SLOTS;
+    __shared__ double sq[WV][NS];
+    double t[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) t[k] = 0.0;
+    if (b < B) {
+      composite_ray<C>(raw, ch, z, rays, rs, noise, b, S, white, rgb, disp, acc, depth, weights, cam, nullptr, o4);
+      if (lane == 0) {
+        const LossForm& f = cl.form;
+        const float m = cl.mask ? cl.mask[b] : 1.f;
+        if (m == 1.f) t[3] = 1.0;
+        if (m == 0.f) t[4] = 1.0;
+        if (f.rgb_form == CNERF_RGB_HARDMASK) {
+          float e = 0.f;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const float d = o4[c] - cl.tgt[b * 3 + c];
+            e += d * d;
+          }
+          if (m == 1.f) t[0] = (double)e;
+          if (m == 0.f) t[1] = (double)e;
+        } else {
+          const bool sm = f.rgb_form == CNERF_RGB_SOFTMASK;
+          const float tr = sm ? f.temp_rgb[0] : 1.f;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) soft_sums(sm, o4[c] - cl.tgt[b * 3 + c], f.lp_coef, tr, t[7], t[8], t[9]);
+        }
+        if (cl.prior) {
+          const float inv = 1.f / cl.far, p = cl.prior[b];
+          if (f.depth_form == CNERF_DEPTH_HARDMASK) {
+            const float d = o4[3] / cl.far - p / cl.far;
+            if (m == 1.f) t[2] = (double)(d * d);
+          } else if (f.depth_form == CNERF_DEPTH_HARDMASK_COEF) {
+            const float d = o4[3] * inv - p * inv;
+            if (m == 1.f) t[2] = (double)(d * d);
+            if (m == 0.f) t[5] = (double)(d * d);
+          } else if (f.depth_form == CNERF_DEPTH_NORM) {
+            const float d = o4[3] * inv - (m == 0.f ? 0.f : p) * inv;
+            t[2] = (double)(d * d);
+          } else if (f.depth_form == CNERF_DEPTH_PLAIN) {
+            const float d = o4[3] - (m == 0.f ? 0.f : p);
+            t[2] = (double)(d * d);
+          } else {
+            const bool sm = f.depth_form == CNERF_DEPTH_SOFTMASK;
+            soft_sums(sm, o4[3] * inv - p * inv, f.lp_coef, sm ? f.temp_depth[0] : 1.f, t[5], t[6], t[2]);
+          }
+        }
+      }
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < NS; ++k) sq[threadIdx.x >> 6][k] = t[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < NS) {
+      double s = 0.0;
+      for (int w = 0; w < WV; ++w) s += sq[w][threadIdx.x];
+      cl.part[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = s;
+    }
+    return;
+  }
   if (cl.tgt != nullptr) {
     // masked-loss variant: per-ray terms in lane 0 (the arithmetic of masked_loss_k: e = d0^2 + d1^2 + d2^2 in fp32, sums in
     // fp64), five partials per workgroup summed over its waves in wave order; no tickets (see ClossFwd)
@@ -304,7 +394,7 @@ __global__ __launch_bounds__(WV * 64) void composite_fwd_k(const float* __restri
   composite_ray<C>(raw, ch, z, rays, rs, noise, b, S, white, rgb, disp, acc, depth, weights, cam, nullptr, o4);
 }
 
-template <int C>
+template <int C, bool FORMS = false>
 __global__ __launch_bounds__(WAVES * 64) void composite_bwd_k(const float* __restrict__ raw, int ch,
                                                               const float* __restrict__ z,
                                                               const float* __restrict__ rays, int rs,
@@ -337,10 +427,43 @@ __global__ __launch_bounds__(WAVES * 64) void composite_bwd_k(const float* __res
     const float* const st = cl.stats + ((cl.seg_row > 0 && b >= cl.seg_row) ? 4 : 0);
     const float w = m == 1.f ? st[0] : (m == 0.f ? st[1] : 0.f);
     const float g_rgb_l = cl.rgb_w * g0;
-    gr += (w * (cl.rgb[b * 3 + 0] - cl.tgt[b * 3 + 0])) * g_rgb_l;
-    gg += (w * (cl.rgb[b * 3 + 1] - cl.tgt[b * 3 + 1])) * g_rgb_l;
-    gb += (w * (cl.rgb[b * 3 + 2] - cl.tgt[b * 3 + 2])) * g_rgb_l;
-    if (cl.prior) {
+    bool v6_rgb = true, v6_depth = true;
+    if constexpr (FORMS) {
+      // the form's seeds: the operations of the literal lines' backward (mse_k / soft_lp_k / softmask_k's d_x, autograd's `d_x * g`,
+      // then the `* (1 / far)` of ATen's tensor / scalar), see LossForm
+      const LossForm& f = cl.form;
+      if (b == 0 && lane == 0 && cl.g_temp) { cl.g_temp[0] = cl.d_temp[0] * g0; cl.g_temp[1] = cl.d_temp[1] * g0; }
+      if (f.rgb_form != CNERF_RGB_HARDMASK) {
+        v6_rgb = false;
+        const bool sm = f.rgb_form == CNERF_RGB_SOFTMASK;
+        const float tr = sm ? f.temp_rgb[0] : 1.f;
+        gr += soft_seed(sm, cl.rgb[b * 3 + 0] - cl.tgt[b * 3 + 0], f.lp_coef, tr, st[4]) * g_rgb_l;
+        gg += soft_seed(sm, cl.rgb[b * 3 + 1] - cl.tgt[b * 3 + 1], f.lp_coef, tr, st[4]) * g_rgb_l;
+        gb += soft_seed(sm, cl.rgb[b * 3 + 2] - cl.tgt[b * 3 + 2], f.lp_coef, tr, st[4]) * g_rgb_l;
+      }
+      if (cl.prior && f.depth_form != CNERF_DEPTH_HARDMASK) {
+        v6_depth = false;
+        const float inv = 1.f / cl.far, p = cl.prior[b], g_d = cl.depth_w * g0;
+        if (f.depth_form == CNERF_DEPTH_HARDMASK_COEF) {
+          const float x = cl.depth[b] * inv - p * inv;
+          if (m == 1.f) gd += ((st[2] * x) * g_d) * inv;
+          if (m == 0.f) gd += ((st[3] * x) * (g_d * f.coef)) * inv;
+        } else if (f.depth_form == CNERF_DEPTH_NORM) {
+          gd += ((st[2] * (cl.depth[b] * inv - (m == 0.f ? 0.f : p) * inv)) * g_d) * inv;
+        } else if (f.depth_form == CNERF_DEPTH_PLAIN) {
+          gd += (st[2] * (cl.depth[b] - (m == 0.f ? 0.f : p))) * g_d;
+        } else {
+          const bool sm = f.depth_form == CNERF_DEPTH_SOFTMASK;
+          gd += (soft_seed(sm, cl.depth[b] * inv - p * inv, f.lp_coef, sm ? f.temp_depth[0] : 1.f, st[2]) * g_d) * inv;
+        }
+      }
+    }
+    if (v6_rgb) {
+      gr += (w * (cl.rgb[b * 3 + 0] - cl.tgt[b * 3 + 0])) * g_rgb_l;
+      gg += (w * (cl.rgb[b * 3 + 1] - cl.tgt[b * 3 + 1])) * g_rgb_l;
+      gb += (w * (cl.rgb[b * 3 + 2] - cl.tgt[b * 3 + 2])) * g_rgb_l;
+    }
+    if (cl.prior && v6_depth) {
       const float dd = m == 1.f ? st[2] * (cl.depth[b] / cl.far - cl.prior[b] / cl.far) : 0.f;
       gd += dd * (cl.depth_w * g0);
     }
@@ -513,33 +636,77 @@ extern "C" int cnerf_composite_bwd_mse(const float* raw, int raw_ch, const float
 // ---- compositing with ConsistentNeRF's masked rgb / depth losses folded in (V:1645-1865): see ClossFwd / ClossBwd above ----------
 extern "C" int64_t cnerf_closs_ws_floats(int64_t B) { return B <= 0 ? 0 : 10 * cn_div_up(B, MSE_WAVES); }
 
-extern "C" int cnerf_composite_fwd_closs(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
-                                         const float* noise, int64_t B, int S, int white_bkgd, const cnerf_closs* L, float* rgb,
-                                         float* disp, float* acc, float* depth, float* weights, float* workspace, void* stream) {
+namespace {
+// cnerf_lossform -> LossForm, or false: a form out of range, a softmask form without its temperature, a softlp form without its
+// exponent (with_depth: the depth form matters only next to a prior)
+bool make_form(const cnerf_lossform* F, bool with_depth, LossForm* f) {
+  if (!F || F->rgb_form < CNERF_RGB_HARDMASK || F->rgb_form > CNERF_RGB_SOFTMASK || F->depth_form < CNERF_DEPTH_HARDMASK ||
+      F->depth_form > CNERF_DEPTH_SOFTMASK)
+    return false;
+  const bool lp = F->rgb_form == CNERF_RGB_SOFTLP || (with_depth && F->depth_form == CNERF_DEPTH_SOFTLP);
+  if ((lp && !(F->lp_coef > 0.f)) || (F->rgb_form == CNERF_RGB_SOFTMASK && !F->temp_rgb) ||
+      (with_depth && F->depth_form == CNERF_DEPTH_SOFTMASK && !F->temp_depth))
+    return false;
+  f->rgb_form = F->rgb_form; f->depth_form = F->depth_form; f->lp_coef = F->lp_coef; f->temp_rgb = F->temp_rgb;
+  f->temp_depth = F->temp_depth;
+  return true;
+}
+
+template <bool FORMS>
+int composite_fwd_closs_impl(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride, const float* noise,
+                             int64_t B, int S, int white_bkgd, const cnerf_closs* L, const cnerf_lossform* F, float* rgb, float* disp,
+                             float* acc, float* depth, float* weights, float* workspace, void* stream) {
   if (!raw || !z || !rays || !L || !L->target || !rgb || !workspace || B <= 0 || S <= 0 || raw_ch < 4 || ray_stride < 6 ||
       ((uintptr_t)workspace & 7) != 0 || (L->prior && (!depth || !(L->far > 0.f))))
     return CNERF_E_ARG;
   ClossFwd c;
   c.tgt = L->target; c.mask = L->mask; c.prior = L->prior; c.far = L->far; c.part = reinterpret_cast<double*>(workspace);
+  if (FORMS && (L->seg_row != 0 || !make_form(F, L->prior != nullptr, &c.form))) return CNERF_E_ARG;
   return dispatch_c(S, [&](auto cc) -> int {
     constexpr int C = decltype(cc)::value;
-    hipLaunchKernelGGL((composite_fwd_k<C, MSE_WAVES>), dim3((unsigned)cn_div_up(B, MSE_WAVES)), dim3(MSE_WAVES * 64), 0,
+    hipLaunchKernelGGL((composite_fwd_k<C, MSE_WAVES, FORMS>), dim3((unsigned)cn_div_up(B, MSE_WAVES)), dim3(MSE_WAVES * 64), 0,
                        cn_stream(stream), raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, rgb, disp, acc, depth, weights,
                        cn_no_raygen(), MseFwd{}, c);
     CN_CHECK_LAUNCH();
     return CNERF_OK;
   });
 }
+}  // namespace
+
+extern "C" int cnerf_composite_fwd_closs(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
+                                         const float* noise, int64_t B, int S, int white_bkgd, const cnerf_closs* L, float* rgb,
+                                         float* disp, float* acc, float* depth, float* weights, float* workspace, void* stream) {
+  return composite_fwd_closs_impl<false>(raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, L, nullptr, rgb, disp, acc, depth,
+                                         weights, workspace, stream);
+}
+
+// ---- the same with a form per kind of term (cnerf_lossform: the other live loss branches of V / VC) ------------------------------
+extern "C" int64_t cnerf_lossform_ws_floats(int64_t B) { return B <= 0 ? 0 : 2 * CNERF_LOSSFORM_SLOTS * cn_div_up(B, MSE_WAVES); }
+
+extern "C" int cnerf_composite_fwd_lossform(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
+                                            const float* noise, int64_t B, int S, int white_bkgd, const cnerf_closs* L,
+                                            const cnerf_lossform* F, float* rgb, float* disp, float* acc, float* depth, float* weights,
+                                            float* workspace, void* stream) {
+  return composite_fwd_closs_impl<true>(raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, L, F, rgb, disp, acc, depth,
+                                        weights, workspace, stream);
+}
 
 namespace {
+template <bool FORMS = false>
 int composite_bwd_closs_impl(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride, const float* noise,
                              int64_t B, int S, int white_bkgd, const cnerf_closs* L, const float* rgb, const float* depth,
                              const float* stats, const float* g_loss, float rgb_w, float depth_w, float patch_w, const float* patch_d,
-                             int64_t n_patch_rays, float ssim_w, const float* ssim_d, int64_t n_ssim_rays, float* d_raw, void* stream) {
+                             int64_t n_patch_rays, float ssim_w, const float* ssim_d, int64_t n_ssim_rays, float* d_raw, void* stream,
+                             const cnerf_lossform* F = nullptr, float coef = 0.f, const float* d_temp = nullptr,
+                             float* g_temp = nullptr) {
   if (!raw || !z || !rays || !L || !L->target || !rgb || !stats || !d_raw || B <= 0 || S <= 0 || raw_ch < 4 || ray_stride < 6 ||
       (L->prior && (!depth || !(L->far > 0.f))) || n_patch_rays < 0 || n_patch_rays > B || n_ssim_rays < 0 || n_ssim_rays > B)
     return CNERF_E_ARG;
   ClossBwd c;
+  c.d_temp = d_temp; c.g_temp = g_temp;
+  if (FORMS && (L->seg_row != 0 || !make_form(F, L->prior != nullptr, &c.form) || (d_temp == nullptr) != (g_temp == nullptr)))
+    return CNERF_E_ARG;
+  c.form.coef = coef;
   c.ssim_d = n_ssim_rays > 0 ? ssim_d : nullptr; c.n_ssim = n_ssim_rays; c.ssim_w = ssim_w;
   c.rgb = rgb; c.depth = depth; c.tgt = L->target; c.mask = L->mask; c.prior = L->prior; c.stats = stats; c.g = g_loss;
   c.seg_row = L->seg_row > 0 && L->seg_row < B ? L->seg_row : 0;
@@ -547,8 +714,8 @@ int composite_bwd_closs_impl(const float* raw, int raw_ch, const float* z, const
   c.patch_w = patch_w;
   return dispatch_c(S, [&](auto cc) -> int {
     constexpr int C = decltype(cc)::value;
-    hipLaunchKernelGGL((composite_bwd_k<C>), dim3((unsigned)cn_div_up(B, WAVES)), dim3(WAVES * 64), 0, cn_stream(stream), raw, raw_ch,
-                       z, rays, ray_stride, noise, B, S, white_bkgd, (const float*)nullptr, (const float*)nullptr,
+    hipLaunchKernelGGL((composite_bwd_k<C, FORMS>), dim3((unsigned)cn_div_up(B, WAVES)), dim3(WAVES * 64), 0, cn_stream(stream), raw,
+                       raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, (const float*)nullptr, (const float*)nullptr,
                        (const float*)nullptr, (const float*)nullptr, d_raw, MseBwd{}, c);
     CN_CHECK_LAUNCH();
     return CNERF_OK;
@@ -572,4 +739,16 @@ extern "C" int cnerf_composite_bwd_closs_ssim(const float* raw, int raw_ch, cons
   if (!ssim_d || n_ssim_rays <= 0) return CNERF_E_ARG;
   return composite_bwd_closs_impl(raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, L, rgb, depth, stats, g_loss, rgb_w,
                                   depth_w, patch_w, patch_d, n_patch_rays, ssim_w, ssim_d, n_ssim_rays, d_raw, stream);
+}
+
+extern "C" int cnerf_composite_bwd_lossform(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
+                                            const float* noise, int64_t B, int S, int white_bkgd, const cnerf_closs* L,
+                                            const cnerf_lossform* F, const float* rgb, const float* depth, const float* stats8,
+                                            const float* g_loss, float rgb_w, float depth_w, float patch_w, float coef,
+                                            const float* patch_d, int64_t n_patch_rays, float ssim_w, const float* ssim_d,
+                                            int64_t n_ssim_rays, const float* d_temp2, float* g_temp2, float* d_raw, void* stream) {
+  if (n_ssim_rays > 0 && !ssim_d) return CNERF_E_ARG;
+  return composite_bwd_closs_impl<true>(raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, L, rgb, depth, stats8, g_loss,
+                                        rgb_w, depth_w, patch_w, patch_d, n_patch_rays, ssim_w, ssim_d, n_ssim_rays, d_raw, stream, F,
+                                        coef, d_temp2, g_temp2);
 }

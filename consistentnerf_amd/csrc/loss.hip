@@ -205,16 +205,24 @@ struct ClossTail {
   const float* rgb[2];       // colour maps of the levels [B, 3]
   const float* tgt;          // [B, 3]
   float* ssim_d[2];          // [sP * 768] d ssim_level / d rgb per level, or nullptr
+  // the FORMS tail only (cnerf_lossform_finish): a form per kind of term and level, CNERF_LOSSFORM_SLOTS partials per workgroup
+  int rgb_form[2], depth_form[2];
+  const float* temp_rgb[2];
+  const float* temp_depth[2];
+  float* d_temp;             // [2][2]: per level (rgb_w dL_rgb / dt, depth_w dL_depth / dt)
+  double B;                  // rays of the batch: the denominator of the norm / plain depth means without global counts
 };
 
+template <bool FORMS>
 __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
+  constexpr int NS = FORMS ? CNERF_LOSSFORM_SLOTS : 5;
   __shared__ double sh[T / 64];
   __shared__ float pshare[2][8];
-  __shared__ double tot[2][5];
+  __shared__ double tot[2][NS];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int levels = a.part[1] ? 2 : 1;
   for (int lv = 0; lv < levels; ++lv)
-    for (int k = 0; k < 5; ++k) {
+    for (int k = 0; k < NS; ++k) {
       double s = 0.0;
       for (int i = threadIdx.x; i < a.nparts; i += T) s += a.part[lv][(int64_t)k * a.nparts + i];
       s = block_sum(s, sh);
@@ -234,7 +242,7 @@ __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
                                            lane);
     if (lane == 0) sshare[lv][p] = share;
   }
-  if (a.ss == 2) {
+  if (!FORMS && a.ss == 2) {
     // The one-render form of the whole `--ss_loss` step (VT:899-969): rays [0, 8 nparts1) are the primary batch (mask = sel, prior =
     // depth_cas_s), rays from there on the second render's warped rays (mask = 1 on the live rows, 0 on the padding; target / prior =
     // the reference view's colours / depth prior at the snapped pixels).  Segment sums in index order, like the sums above.
@@ -308,7 +316,7 @@ __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
   }
   __syncthreads();
   if (threadIdx.x != 0) return;
-  if (a.ss) {
+  if (!FORMS && a.ss) {
     // VT:941-969 — the primary render's terms under `--ss_loss`, mask = the rays `[mask_bound][mask]` selects (cnerf_ss_ref_rays'
     // `sel`), each term behind its own random.randint(0, 1) coin:
     //   img_loss  = coin ? img2mse(rgb[sel], target[sel])      : img2mse(rgb, target)                       (:942)
@@ -354,7 +362,36 @@ __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
     const double N0 = a.counts ? (double)a.counts[1] : tot[lv][4];
     float il = (float)(s1 / (3.0 * N1));
     if (N0 > 0) il += a.coef * (float)(s0 / (3.0 * N0));
-    const float dl = a.has_depth ? (float)(sd / N1) : 0.f;
+    float dl = a.has_depth ? (float)(sd / N1) : 0.f;
+    float wd = (float)(2.0 / N1) / a.far, wd0 = 0.f, inv_rgb = 0.f;
+    if constexpr (FORMS) {
+      // L = N / Dn with N = sum(w d^2), Dn = sum(w) (detached in d, not in t); softmask: dL / dt = -(sum(w d^4) / Dn - L^2) / t^2
+      auto d_temp = [](double s4, double Dn, double N, double t) { const double L = N / Dn; return -(s4 / Dn - L * L) / (t * t); };
+      float dt_rgb = 0.f, dt_depth = 0.f;
+      if (a.rgb_form[lv] != CNERF_RGB_HARDMASK) {
+        const double Dn = tot[lv][7], N = tot[lv][8];
+        il = (float)(N / Dn);
+        inv_rgb = (float)(1.0 / Dn);
+        if (a.rgb_form[lv] == CNERF_RGB_SOFTMASK) dt_rgb = a.rgb_w * (float)d_temp(tot[lv][9], Dn, N, (double)a.temp_rgb[lv][0]);
+      }
+      if (a.has_depth && a.depth_form[lv] != CNERF_DEPTH_HARDMASK) {
+        const int df = a.depth_form[lv];
+        if (df == CNERF_DEPTH_HARDMASK_COEF) {
+          if (N0 > 0) { dl += a.coef * (float)(tot[lv][5] / N0); wd0 = (float)(2.0 / N0); }
+          wd = (float)(2.0 / N1);
+        } else if (df == CNERF_DEPTH_NORM || df == CNERF_DEPTH_PLAIN) {
+          const double Nall = a.counts ? (double)a.counts[0] + (double)a.counts[1] : a.B;
+          dl = (float)(sd / Nall);
+          wd = (float)(2.0 / Nall);
+        } else {
+          const double Dn = tot[lv][5], N = tot[lv][6];
+          dl = (float)(N / Dn);
+          wd = (float)(1.0 / Dn);
+          if (df == CNERF_DEPTH_SOFTMASK) dt_depth = a.depth_w * (float)d_temp(sd, Dn, N, (double)a.temp_depth[lv][0]);
+        }
+      }
+      a.d_temp[2 * lv + 0] = dt_rgb; a.d_temp[2 * lv + 1] = dt_depth;
+    }
     float pl = 0.f;
     for (int k = 0; k < a.P; ++k) pl += pshare[lv][k];
     loss += a.rgb_w * il;
@@ -368,11 +405,18 @@ __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
     }
     if (a.has_depth) loss = loss + a.depth_w * dl;
     a.terms[1 + 3 * lv] = il; a.terms[2 + 3 * lv] = dl; a.terms[3 + 3 * lv] = pl;
-    a.stats[4 * lv + 0] = (float)(2.0 / (3.0 * N1));
-    a.stats[4 * lv + 1] = N0 > 0 ? a.coef * (float)(2.0 / (3.0 * N0)) : 0.f;
-    a.stats[4 * lv + 2] = (float)(2.0 / N1) / a.far;
-    a.stats[4 * lv + 3] = 0.f;
+    float* st = a.stats + (FORMS ? 8 : 4) * lv;
+    st[0] = (float)(2.0 / (3.0 * N1));
+    st[1] = N0 > 0 ? a.coef * (float)(2.0 / (3.0 * N0)) : 0.f;
+    st[2] = wd;
+    st[3] = wd0;
+    if constexpr (FORMS) { st[4] = inv_rgb; st[5] = st[6] = st[7] = 0.f; }
   }
+  if (FORMS && levels == 1) {
+    for (int k = 8; k < 16; ++k) a.stats[k] = 0.f;
+    a.d_temp[2] = a.d_temp[3] = 0.f;
+  }
+  if (FORMS && a.sP == 0) a.terms[8] = a.terms[9] = 0.f;
   if (levels == 1) { a.terms[4] = a.terms[5] = a.terms[6] = 0.f; }
   if (a.sP > 0 && levels == 1) a.terms[9] = 0.f;
   a.terms[0] = loss;
@@ -597,8 +641,14 @@ struct ClossSsim {            // cnerf_closs_finish_ssim's additions (sP = 0: no
   float* ssim_d = nullptr;
 };
 
+struct ClossForms {           // cnerf_lossform_finish's additions
+  const cnerf_lossform* F[2];
+  float* d_temp;
+};
+
 int closs_finish_impl(const cnerf_closs_sum* t, const int32_t* ss_coins, float* terms, float* stats, float* patch_d, void* stream,
-                      int64_t seg_row = 0, const float* counts3 = nullptr, const ClossSsim& sm = ClossSsim()) {
+                      int64_t seg_row = 0, const float* counts3 = nullptr, const ClossSsim& sm = ClossSsim(),
+                      const ClossForms* fm = nullptr) {
   if (!t || !terms || !stats || !t->ws_last || t->B <= 0 || t->P < 0 || t->P > 8 || (t->P > 0 && (t->n <= 0 || !t->mono || !t->depth_last)) ||
       (t->P > 0 && t->ws_coarse && !t->depth_coarse) || (t->has_depth && !(t->far > 0.f)) || (int64_t)t->P * t->n > t->B ||
       ((uintptr_t)t->ws_last & 7) != 0 || ((uintptr_t)t->ws_coarse & 7) != 0)
@@ -620,7 +670,25 @@ int closs_finish_impl(const cnerf_closs_sum* t, const int32_t* ss_coins, float* 
   a.sP = sm.sP; a.ssim_w = sm.ssim_w; a.rgb[0] = sm.rgb_last; a.rgb[1] = t->ws_coarse ? sm.rgb_coarse : nullptr; a.tgt = sm.target;
   a.ssim_d[0] = sm.ssim_d;
   a.ssim_d[1] = (sm.ssim_d && t->ws_coarse) ? sm.ssim_d + (int64_t)sm.sP * CN_PATCH_SSIM_RAYS * 3 : nullptr;
-  hipLaunchKernelGGL(closs_tail_k, dim3(1), dim3(T), 0, cn_stream(stream), a);
+  if (fm) {
+    // (no in-loop consistency segments here; a softlp / softmask normaliser is a sum of weights, which no caller all-reduces: no
+    // global counts with those forms)
+    if (ss_coins || seg_row != 0 || !fm->d_temp) return CNERF_E_ARG;
+    for (int lv = 0; lv < (t->ws_coarse ? 2 : 1); ++lv) {
+      const cnerf_lossform* F = fm->F[lv];
+      if (!F || F->rgb_form < CNERF_RGB_HARDMASK || F->rgb_form > CNERF_RGB_SOFTMASK || F->depth_form < CNERF_DEPTH_HARDMASK ||
+          F->depth_form > CNERF_DEPTH_SOFTMASK || (F->rgb_form == CNERF_RGB_SOFTMASK && !F->temp_rgb) ||
+          (t->has_depth && F->depth_form == CNERF_DEPTH_SOFTMASK && !F->temp_depth))
+        return CNERF_E_ARG;
+      const bool soft = F->rgb_form != CNERF_RGB_HARDMASK || (t->has_depth && F->depth_form >= CNERF_DEPTH_SOFTLP);
+      if (soft && t->counts) return CNERF_E_ARG;
+      a.rgb_form[lv] = F->rgb_form; a.depth_form[lv] = F->depth_form; a.temp_rgb[lv] = F->temp_rgb; a.temp_depth[lv] = F->temp_depth;
+    }
+    a.d_temp = fm->d_temp; a.B = (double)t->B;
+    hipLaunchKernelGGL(closs_tail_k<true>, dim3(1), dim3(T), 0, cn_stream(stream), a);
+  } else {
+    hipLaunchKernelGGL(closs_tail_k<false>, dim3(1), dim3(T), 0, cn_stream(stream), a);
+  }
   CN_CHECK_LAUNCH();
   return CNERF_OK;
 }
@@ -653,4 +721,64 @@ extern "C" int cnerf_closs_finish_ssim(const cnerf_closs_sum* t, int ssim_P, flo
   ClossSsim sm;
   sm.sP = ssim_P; sm.ssim_w = ssim_w; sm.rgb_last = rgb_last; sm.rgb_coarse = rgb_coarse; sm.target = target; sm.ssim_d = ssim_d;
   return closs_finish_impl(t, nullptr, terms10, stats, patch_d, stream, 0, nullptr, sm);
+}
+
+extern "C" int cnerf_lossform_finish(const cnerf_closs_sum* t, const cnerf_lossform* F_last, const cnerf_lossform* F_coarse, int ssim_P,
+                                     float ssim_w, const float* rgb_last, const float* rgb_coarse, const float* target, float* terms10,
+                                     float* stats16, float* patch_d, float* ssim_d, float* d_temp4, void* stream) {
+  if (!t || !F_last || !terms10 || !stats16 || !d_temp4 || t->B <= 0 || (t->ws_coarse && !F_coarse) || ssim_P < 0 || ssim_P > 8) return CNERF_E_ARG;
+  ClossSsim sm;
+  if (ssim_P > 0) {
+    if (!rgb_last || !target || (int64_t)ssim_P * CN_PATCH_SSIM_RAYS > t->B || (t->ws_coarse && !rgb_coarse)) return CNERF_E_ARG;
+    sm.sP = ssim_P; sm.ssim_w = ssim_w; sm.rgb_last = rgb_last; sm.rgb_coarse = rgb_coarse; sm.target = target; sm.ssim_d = ssim_d;
+  }
+  const ClossForms fm = {{F_last, F_coarse}, d_temp4};
+  return closs_finish_impl(t, nullptr, terms10, stats16, patch_d, stream, 0, nullptr, sm, &fm);
+}
+
+// img2mse_softmask / img2mse_depth_softmask (V:50 / V:55; the `--softmask` branch of the loss, VC:1526-1528 / VC:1564-1572): every
+// squared residual weighted by w = exp(d^2 / t), normalised by the sum of the weights, which is detached in d but NOT in the
+// temperature:  L = N / Dn, N = sum(w d^2), Dn = sum(w);  dL / dd = w (2 d + 2 d^3 / t) / Dn;  dL / dt = -(sum(w d^4) / Dn - L^2) / t^2.
+// One workgroup, two sweeps (sums in fp64, fixed order), like soft_lp_k.
+namespace {
+__global__ __launch_bounds__(T) void softmask_k(const float* __restrict__ x, const float* __restrict__ y, int64_t n,
+                                                const float* __restrict__ temp, float* __restrict__ loss, float* __restrict__ d_x,
+                                                float* __restrict__ d_temp) {
+  __shared__ double sh[T / 64];
+  __shared__ double tot[1];
+  const float t = temp[0];
+  double num = 0, den = 0, s4 = 0;
+  for (int64_t i = threadIdx.x; i < n; i += T) {
+    const float d = x[i] - y[i];
+    const float d2 = d * d;
+    const float w = expf(d2 / t);
+    den += (double)w;
+    num += (double)(w * d2);
+    s4 += (double)(w * (d2 * d2));
+  }
+  num = block_sum(num, sh);
+  den = block_sum(den, sh);
+  s4 = block_sum(s4, sh);
+  if (threadIdx.x == 0) {
+    const double L = num / den;
+    tot[0] = den;
+    loss[0] = (float)L;
+    if (d_temp) d_temp[0] = (float)(-(s4 / den - L * L) / ((double)t * (double)t));
+  }
+  __syncthreads();
+  if (!d_x) return;
+  const float inv = (float)(1.0 / tot[0]);
+  for (int64_t i = threadIdx.x; i < n; i += T) {
+    const float d = x[i] - y[i];
+    d_x[i] = (expf((d * d) / t) * (2.f * d + 2.f * ((d * d) * d) / t)) * inv;
+  }
+}
+}  // namespace
+
+extern "C" int cnerf_softmask_loss(const float* x, const float* y, int64_t n, const float* temp, float* loss, float* d_x, float* d_temp,
+                                   void* stream) {
+  if (!x || !y || !temp || !loss || n <= 0) return CNERF_E_ARG;
+  hipLaunchKernelGGL(softmask_k, dim3(1), dim3(T), 0, cn_stream(stream), x, y, n, temp, loss, d_x, d_temp);
+  CN_CHECK_LAUNCH();
+  return CNERF_OK;
 }

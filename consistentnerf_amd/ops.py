@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Closs, ClossTail, CnerfError, Net, PixelBatch, Ptrs, RayGen, RenderCfg, RenderGrads, RenderOut, Rng, SsWarp
+from ._lib import Closs, ClossTail, CnerfError, LossForm, Net, PixelBatch, Ptrs, RayGen, RenderCfg, RenderGrads, RenderOut, Rng, SsWarp
 
 Tensor = torch.Tensor
 
@@ -598,6 +598,10 @@ def composite_backward_mse(raw, z, rays, noise, white_bkgd, rgb, target, g_loss)
     return d_raw
 
 
+RGB_FORMS = ("hardmask", "softlp", "softmask")                                            # CNERF_RGB_*
+DEPTH_FORMS = ("hardmask", "hardmask_coef", "norm", "plain", "softlp", "softmask")        # CNERF_DEPTH_*
+
+
 # ---- the ConsistentNeRF losses folded into compositing (cnerf_composite_fwd_closs / cnerf_closs_finish / cnerf_composite_bwd_closs)
 @dataclass
 class ClossSpec:
@@ -621,6 +625,20 @@ class ClossSpec:
     counts3: Optional[Tensor] = None      # (with seg_row) GLOBAL (selected, primary, warped) ray counts of a batch sharded over ranks
     ssim_w: float = 0.0                   # V's patch SSIM term (loss -= ssim_w ssim_level per level; 0 = none) over the first
     ssim_P: int = 0                       # ssim_P patches of 16 x 16 rays (cnerf_closs_finish_ssim)
+    rgb_form: int = 0                     # RGB_FORMS / DEPTH_FORMS index (cnerf_lossform): any non-zero one takes the *_lossform
+    depth_form: int = 0                   # entry points
+    lp_coef: float = 0.0                  # the exponent of a softlp form (args.Lp_coef)
+    temps: Optional[tuple] = None         # 0-d device tensors (temp_rgb, temp_depth, temp_rgb coarse, temp_depth coarse) or None each
+
+    @property
+    def forms(self) -> bool:
+        return bool(self.rgb_form or self.depth_form)
+
+    def form_c(self, level: int) -> LossForm:
+        """struct cnerf_lossform of a level (0 = the last / fine one, 1 = coarse)."""
+        t = self.temps or (None,) * 4
+        a = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        return LossForm(int(self.rgb_form), int(self.depth_form), float(self.lp_coef), a(t[2 * level]), a(t[2 * level + 1]))
 
     def c(self) -> Closs:
         return Closs(self.target.data_ptr(), None if self.mask is None else self.mask.data_ptr(),
@@ -649,13 +667,28 @@ class ClossSpec:
         if sP > 0 and (sP > 8 or sP * PATCH_SSIM_RAYS > B or coins is not None):
             raise CnerfError(f"closs: the patch SSIM term needs ssim_P <= 8 patches of {PATCH_SSIM_RAYS} rays inside the batch and no "
                              f"ss_coins (ssim_P={sP}, B={B})")
+        rf, df = int(self.rgb_form), int(self.depth_form) if pr is not None else 0
+        temps = None
+        if rf or df:
+            if not (0 <= rf < len(RGB_FORMS) and 0 <= df < len(DEPTH_FORMS)):
+                raise CnerfError(f"closs: unknown loss form ({rf}, {df})")
+            if coins is not None or (self.counts is not None and (rf or df >= DEPTH_FORMS.index("softlp"))):
+                raise CnerfError("closs: a loss form takes no ss_coins, and no global counts with a softlp / softmask form")
+            if (rf == RGB_FORMS.index("softlp") or df == DEPTH_FORMS.index("softlp")) and not float(self.lp_coef) > 0:
+                raise CnerfError("closs: a softlp form needs lp_coef > 0")
+            temps = tuple(None if x is None else _chk(x.reshape(1), "temp") for x in (self.temps or (None,) * 4))
+            need = [k for k in (0, 2) if rf == RGB_FORMS.index("softmask")] + [k for k in (1, 3) if df == DEPTH_FORMS.index("softmask")]
+            if len(temps) != 4 or any(temps[k] is None for k in need):
+                raise CnerfError("closs: a softmask form needs its temperature of both levels as device tensors")
         return ClossSpec(t, m, pr, float(self.far), float(self.coef), float(self.rgb_w), float(self.depth_w), float(self.patch_w),
                          mono, P, int(self.n), _chk(self.counts, "counts"), coins, seg, _chk(self.counts3, "counts3") if seg else None,
-                         float(self.ssim_w) if sP else 0.0, sP)
+                         float(self.ssim_w) if sP else 0.0, sP, rf, df, float(self.lp_coef), temps)
 
 
-def composite_forward_closs(raw: Tensor, z: Tensor, rays: Tensor, noise: Optional[Tensor], white_bkgd: bool, L: ClossSpec):
-    """-> (rgb, disp, acc, weights, depth, ws): raw2outputs + the level's five masked-loss partial sums per workgroup in `ws`."""
+def composite_forward_closs(raw: Tensor, z: Tensor, rays: Tensor, noise: Optional[Tensor], white_bkgd: bool, L: ClossSpec,
+                            level: int = 0):
+    """-> (rgb, disp, acc, weights, depth, ws): raw2outputs + the level's five masked-loss partial sums per workgroup in `ws` (with
+    a loss form, L.forms: cnerf_composite_fwd_lossform's ten; level 0 = the last level, 1 = coarse: whose temperatures to read)."""
     raw, z, rays, noise = _chk(raw, "raw"), _chk(z, "z"), _chk(rays, "rays"), _chk(noise, "noise")
     B, S = z.shape
     dev = raw.device
@@ -663,8 +696,15 @@ def composite_forward_closs(raw: Tensor, z: Tensor, rays: Tensor, noise: Optiona
     disp, acc, depth = torch.empty(B, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev)
     weights = torch.empty(B, S, device=dev)
     lib = _lib.load()
-    ws = torch.empty(lib.cnerf_closs_ws_floats(B) // 2, device=dev, dtype=torch.float64)
     c = L.c()
+    if L.forms:
+        ws = torch.empty(lib.cnerf_lossform_ws_floats(B) // 2, device=dev, dtype=torch.float64)
+        f = L.form_c(level)
+        _lib.check(lib.cnerf_composite_fwd_lossform(_p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S,
+                                                    int(white_bkgd), C.byref(c), C.byref(f), _p(rgb), _p(disp), _p(acc), _p(depth),
+                                                    _p(weights), _p(ws), _stream()), "cnerf_composite_fwd_lossform")
+        return rgb, disp, acc, weights, depth, ws
+    ws = torch.empty(lib.cnerf_closs_ws_floats(B) // 2, device=dev, dtype=torch.float64)
     _lib.check(lib.cnerf_composite_fwd_closs(_p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S,
                                              int(white_bkgd), C.byref(c), _p(rgb), _p(disp), _p(acc), _p(depth), _p(weights),
                                              _p(ws), _stream()), "cnerf_composite_fwd_closs")
@@ -715,11 +755,41 @@ def closs_finish_ssim(L: ClossSpec, B: int, ws_last: Tensor, ws_coarse: Optional
     return terms, stats, patch_d, ssim_d
 
 
-def composite_backward_closs(raw, z, rays, noise, white_bkgd, L: ClossSpec, rgb, depth, stats4, g_loss, patch_d, ssim_d=None) -> Tensor:
+def lossform_finish(L: ClossSpec, B: int, ws_last: Tensor, ws_coarse: Optional[Tensor], depth_last: Optional[Tensor],
+                    depth_coarse: Optional[Tensor], rgb_last: Tensor, rgb_coarse: Optional[Tensor], want_grad: bool = True):
+    """cnerf_lossform_finish (L.forms) -> (terms[10], stats[16] = per level 8, patch_d | None, ssim_d | None, d_temp[4] = per level
+    (rgb_w dL_rgb / d temp_rgb, depth_w dL_depth / d temp_depth))."""
+    dev = ws_last.device
+    terms, stats, d_temp = torch.empty(10, device=dev), torch.empty(16, device=dev), torch.empty(4, device=dev)
+    levels = 2 if ws_coarse is not None else 1
+    patch_d = torch.empty(levels, L.P * L.n, device=dev) if (L.P > 0 and want_grad) else None
+    ssim_d = torch.empty(levels, L.ssim_P * PATCH_SSIM_RAYS * 3, device=dev) if (L.ssim_P > 0 and want_grad) else None
+    a = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    t = ClossTail(a(ws_last), a(ws_coarse), int(B), a(L.counts), L.coef, L.far, L.rgb_w, L.depth_w, L.patch_w,
+                  int(L.prior is not None), a(depth_last) if L.P > 0 else None,
+                  a(depth_coarse) if (L.P > 0 and levels == 2) else None, a(L.mono) if L.P > 0 else None, L.P, L.n)
+    f0, f1 = L.form_c(0), L.form_c(1)
+    rgb_last, rgb_coarse = _chk(rgb_last, "rgb"), _chk(rgb_coarse, "rgb0") if levels == 2 else None
+    _lib.check(_lib.load().cnerf_lossform_finish(C.byref(t), C.byref(f0), C.byref(f1), int(L.ssim_P), float(L.ssim_w), _p(rgb_last),
+                                                 _p(rgb_coarse), _p(L.target), _p(terms), _p(stats), _p(patch_d), _p(ssim_d),
+                                                 _p(d_temp), _stream()), "cnerf_lossform_finish")
+    return terms, stats, patch_d, ssim_d, d_temp
+
+
+def composite_backward_closs(raw, z, rays, noise, white_bkgd, L: ClossSpec, rgb, depth, stats4, g_loss, patch_d, ssim_d=None,
+                             level: int = 0, d_temp2=None, g_temp2=None) -> Tensor:
     raw, z, rays, noise = _chk(raw, "raw"), _chk(z, "z"), _chk(rays, "rays"), _chk(noise, "noise")
     B, S = z.shape
     d_raw = torch.empty_like(raw)
     c = L.c()
+    if L.forms:                 # the form's seeds (cnerf_composite_bwd_lossform); stats4 = the level's 8 floats
+        f = L.form_c(level)
+        _lib.check(_lib.load().cnerf_composite_bwd_lossform(
+            _p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S, int(white_bkgd), C.byref(c), C.byref(f), _p(rgb),
+            _p(depth), _p(stats4), _p(g_loss), L.rgb_w, L.depth_w, L.patch_w, L.coef, _p(patch_d),
+            L.P * L.n if patch_d is not None else 0, float(L.ssim_w), _p(ssim_d), 0 if ssim_d is None else ssim_d.numel() // 3,
+            _p(d_temp2), _p(g_temp2), _p(d_raw), _stream()), "cnerf_composite_bwd_lossform")
+        return d_raw
     if ssim_d is not None:      # + V's patch SSIM seeds (cnerf_composite_bwd_closs_ssim)
         _lib.check(_lib.load().cnerf_composite_bwd_closs_ssim(
             _p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S, int(white_bkgd), C.byref(c), _p(rgb), _p(depth),
@@ -989,6 +1059,20 @@ def soft_lp_loss(x: Tensor, y: Tensor, coef: float, want_grad: bool = True):
     d_x = torch.empty_like(x) if want_grad else None
     _lib.check(_lib.load().cnerf_soft_lp_loss(_p(x), _p(y), x.numel(), float(coef), _p(loss), _p(d_x), _stream()), "cnerf_soft_lp_loss")
     return loss[0], d_x
+
+
+def softmask_loss(x: Tensor, y: Tensor, temp: Tensor, want_grad: bool = True):
+    """cnerf_softmask_loss (V:50 / V:55): (sum(w d^2) / sum(w) with w = exp(d^2 / temp), the denominator detached in d but not in
+    temp; d loss / d x | None; d loss / d temp [1] | None).  temp: a device tensor of one element."""
+    x, y, temp = _chk(x, "x"), _chk(y, "y"), _chk(temp.reshape(1), "temp")
+    if x.shape != y.shape or x.numel() == 0:
+        raise CnerfError("softmask_loss: x and y must be non-empty tensors of one shape")
+    loss = torch.empty(1, device=x.device)
+    d_x = torch.empty_like(x) if want_grad else None
+    d_t = torch.empty(1, device=x.device) if want_grad else None
+    _lib.check(_lib.load().cnerf_softmask_loss(_p(x), _p(y), x.numel(), _p(temp), _p(loss), _p(d_x), _p(d_t), _stream()),
+               "cnerf_softmask_loss")
+    return loss[0], d_x, d_t
 
 
 def patch_depth_loss(depth_pred: Tensor, mono: Tensor, P: int, n: int, g_scale: float = 1.0, want_grad: bool = True):

@@ -437,40 +437,64 @@ class _RenderClossFn(torch.autograd.Function):
     from (raw, raw_coarse) to the scalar.  Forward: the last level's compositing launch leaves its masked-loss partial sums (the
     coarse level's launch left its own, render_rays), cnerf_closs_finish sums both, evaluates the patch term of both levels and
     assembles the loss; backward: the two compositing-backward launches form their rgb / depth / patch seeds in registers.  Gone from
-    the step: 2 masked-loss + 2 patch-term launches and the ~25 ATen kernels between them (adds, muls, index copies, fills)."""
+    the step: 2 masked-loss + 2 patch-term launches and the ~25 ATen kernels between them (adds, muls, index copies, fills).
+    With a loss form (L.forms: the other live branches of V / VC, cnerf_lossform) the same three kinds of launch through the *_lossform
+    entry points; `temps` = L.temps as autograd inputs: the softmask temperatures (temp_rgb, temp_depth, coarse temp_rgb, coarse
+    temp_depth; None each), whose gradients the compositing-backward launches leave next to d_raw."""
 
     @staticmethod
-    def forward(ctx, raw, raw_c, z, z_c, rays, noise, noise_c, white, L, rgb_c, depth_c, ws_c):
+    def forward(ctx, raw, raw_c, z, z_c, rays, noise, noise_c, white, L, rgb_c, depth_c, ws_c, *temps):
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
             raise ops.CnerfError("render_loss: gradients w.r.t. z_vals / rays are not implemented (only w.r.t. raw)")
         rgb, disp, acc, weights, depth, ws = ops.composite_forward_closs(raw, z, rays, noise, white, L)
         want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        if L.ssim_P > 0:    # + V's patch SSIM term of every level (loss -= ssim_w ssim_level)
+        d_temp = None
+        ctx.n_temps = len(temps)
+        if L.forms:
+            want = want or any(ctx.needs_input_grad[12:])
+            terms, stats, patch_d, ssim_d, d_temp = ops.lossform_finish(L, z.shape[0], ws, ws_c, depth, depth_c, rgb, rgb_c, want_grad=want)
+        elif L.ssim_P > 0:    # + V's patch SSIM term of every level (loss -= ssim_w ssim_level)
             terms, stats, patch_d, ssim_d = ops.closs_finish_ssim(L, z.shape[0], ws, ws_c, depth, depth_c, rgb, rgb_c, want_grad=want)
         else:
             terms, stats, patch_d = ops.closs_finish(L, z.shape[0], ws, ws_c, depth, depth_c, want_grad=want)
             ssim_d = None
-        ctx.save_for_backward(raw, raw_c, z, z_c, rays, rgb, rgb_c, depth, depth_c, stats, patch_d, ssim_d)
+        ctx.save_for_backward(raw, raw_c, z, z_c, rays, rgb, rgb_c, depth, depth_c, stats, patch_d, ssim_d, d_temp)
         ctx.noise, ctx.noise_c, ctx.white, ctx.L = noise, noise_c, white, L
+        ctx.temp_shapes = [None if t is None else t.shape for t in temps]
         ctx.mark_non_differentiable(terms, rgb, disp, acc, weights, depth)
         ctx.set_materialize_grads(False)
         return terms[0], terms, rgb, disp, acc, weights, depth
 
     @staticmethod
     def backward(ctx, g_loss, *_rest):
-        raw, raw_c, z, z_c, rays, rgb, rgb_c, depth, depth_c, stats, patch_d, ssim_d = ctx.saved_tensors
+        raw, raw_c, z, z_c, rays, rgb, rgb_c, depth, depth_c, stats, patch_d, ssim_d, d_temp = ctx.saved_tensors
         d_raw = d_raw_c = None
+        g_temps = (None,) * ctx.n_temps
         if g_loss is not None:
             L = ctx.L
-            w = 8 if L.seg_row else 4       # (two segments: per level [2][4] seed weights, cnerf_closs_finish_ss2)
+            w = 8 if (L.seg_row or L.forms) else 4   # (two segments: per level [2][4] seed weights, cnerf_closs_finish_ss2; forms: [8])
+            want_t = L.forms and any(ctx.needs_input_grad[12:])
+            g_temp = torch.empty(4, device=raw.device) if want_t else None   # written by the levels' backward launches
+            tk = lambda lv: {} if not L.forms else dict(level=lv, d_temp2=d_temp[2 * lv:2 * lv + 2] if want_t else None,  # noqa: E731
+                                                        g_temp2=g_temp[2 * lv:2 * lv + 2] if want_t else None)
+            ran = [False, False]
             if ctx.needs_input_grad[0]:
                 d_raw = ops.composite_backward_closs(raw, z, rays, ctx.noise, ctx.white, L, rgb, depth, stats[0:w], g_loss,
-                                                     None if patch_d is None else patch_d[0], None if ssim_d is None else ssim_d[0])
+                                                     None if patch_d is None else patch_d[0], None if ssim_d is None else ssim_d[0],
+                                                     **tk(0))
+                ran[0] = True
             if raw_c is not None and ctx.needs_input_grad[1]:
                 d_raw_c = ops.composite_backward_closs(raw_c, z_c, rays, ctx.noise_c, ctx.white, L, rgb_c, depth_c, stats[w:2 * w],
                                                        g_loss, None if patch_d is None else patch_d[1],
-                                                       None if ssim_d is None else ssim_d[1])
-        return (d_raw, d_raw_c) + (None,) * 10
+                                                       None if ssim_d is None else ssim_d[1], **tk(1))
+                ran[1] = True
+            if want_t:
+                for lv in (0, 1):       # (a level whose raw takes no gradient had no launch to ride in)
+                    if not ran[lv]:
+                        g_temp[2 * lv:2 * lv + 2] = d_temp[2 * lv:2 * lv + 2] * g_loss
+                g_temps = tuple(g_temp[k].reshape(ctx.temp_shapes[k]) if ctx.needs_input_grad[12 + k] else None
+                                for k in range(ctx.n_temps))
+        return (d_raw, d_raw_c) + (None,) * 10 + g_temps
 
 
 _ONES = {}
@@ -962,13 +986,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     if _target is None:
         rgb_map, disp_map, acc_map, weights, depth_map = _CompositeFn.apply(raw, z_vals, rays, noise, bool(white_bkgd))
     elif isinstance(_target, ops.ClossSpec):
-        _target = _target.checked(N_rays)
+        _form_temps = (_target.temps or ()) if _target.forms else ()    # autograd inputs: checked() below detaches nothing, but
+        _target = _target.checked(N_rays)                              # the node must see the caller's own tensors
         if N_importance > 0:  # coarse level of two: its partial sums ride in its compositing launch; the autograd node comes below
             rgb_map, disp_map, acc_map, weights, depth_map, ws_c = ops.composite_forward_closs(raw, z_vals, rays, noise,
-                                                                                               bool(white_bkgd), _target)
+                                                                                               bool(white_bkgd), _target, level=1)
         else:
             loss, terms, rgb_map, disp_map, acc_map, weights, depth_map = _RenderClossFn.apply(
-                raw, None, z_vals, None, rays, noise, None, bool(white_bkgd), _target, None, None, None)
+                raw, None, z_vals, None, rays, noise, None, bool(white_bkgd), _target, None, None, None, *_form_temps)
     elif N_importance > 0:    # coarse level of two: its loss term rides in its compositing launch; the autograd node comes below
         rgb_map, disp_map, acc_map, weights, depth_map, loss_c = ops.composite_forward_mse(raw, z_vals, rays, noise, bool(white_bkgd),
                                                                                           _target)
@@ -1006,7 +1031,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                 # one-render form of the step, seg_row > 0: the second render's coarse terms always reach the coarse network.)
                 rc = raw_coarse.detach()
             loss, terms, rgb_map, disp_map, acc_map, weights, depth_map = _RenderClossFn.apply(
-                raw, rc, z_vals, z_coarse, rays, noise, noise_coarse, bool(white_bkgd), _target, rgb_map_0, depth_map_0, ws_c)
+                raw, rc, z_vals, z_coarse, rays, noise, noise_coarse, bool(white_bkgd), _target, rgb_map_0, depth_map_0, ws_c,
+                *_form_temps)
         else:
             loss, rgb_map, disp_map, acc_map, weights, depth_map = _RenderLossFn.apply(
                 raw, raw_coarse, z_vals, z_coarse, rays, noise, noise_coarse, bool(white_bkgd), _target, rgb_map_0, loss_c)

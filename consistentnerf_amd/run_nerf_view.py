@@ -4,6 +4,9 @@
   render_rays V:441-551 | raw2outputs V:392-438 | get_rays_ref V:553 | get_ref_rays V:576 |
   get_test_label V:630 | the hard-mask precompute of train() V:994-1046 (`compute_hard_masks`) |
   the masked RGB / depth losses V:1645-1648, V:1737, V:1786-1788, V:1865 (`hardmask_losses`) |
+  the other live loss branches of V and of run_nerf_view_cal_correspondance.py (VC): `--softLpmask` V:58, `--softmask` V:50 / V:55
+  (`img2mse_softLpmask`, `img2mse_softmask`, `img2mse_depth_softmask`), the depth forms V:1762-1771 and VC:1550-1551
+  (`render_loss(rgb_form=, depth_form=)`) |
   the in-loop consistency block of run_nerf_view_test.py: VT:905-938 (`ss_consistency`) and its consumers VT:941-969
   (`ss_primary_losses`)
 
@@ -208,6 +211,77 @@ def img2mse_softLpmask(x, y, coef):
     return torch.sum(w * d ** 2) / torch.sum(w).detach()
 
 
+class _SoftmaskFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, temp):
+        need = any(ctx.needs_input_grad)
+        loss, d_x, d_t = ops.softmask_loss(x, y, temp, need)
+        if need:
+            ctx.save_for_backward(d_x, d_t)
+        ctx.temp_shape = temp.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        d_x, d_t = ctx.saved_tensors
+        gx = d_x * g if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) else None
+        return ((gx if ctx.needs_input_grad[0] else None), (-gx if ctx.needs_input_grad[1] else None),
+                ((d_t * g).reshape(ctx.temp_shape) if ctx.needs_input_grad[2] else None))
+
+
+def img2mse_softmask(x, y, temp):
+    """V:50, the `--softmask` branch of the colour loss (VC:1526-1528; dead in V, where `if args.hardmask or args.softmask` wins):
+    every squared residual weighted by exp((x - y)^2 / temp), normalised by the sum of the weights with the RESIDUAL detached —
+    the temperature is not: it receives a gradient through both sums.  temp = F.softplus(net.temp_rgb), the softplus left to
+    autograd.  One launch (value, d / dx, d / dtemp) for same-shape fp32 GPU tensors and a one-element GPU temperature; the
+    reference's expression on ATen otherwise."""
+    if (torch.is_tensor(x) and torch.is_tensor(y) and torch.is_tensor(temp) and x.is_cuda and y.is_cuda and temp.is_cuda
+            and x.shape == y.shape and x.numel() > 0 and temp.numel() == 1 and x.dtype == torch.float32 and y.dtype == torch.float32
+            and temp.dtype == torch.float32):
+        return _SoftmaskFn.apply(x.contiguous(), y.contiguous(), temp)
+    return torch.sum((torch.exp((x - y) ** 2 / temp)) * (x - y) ** 2) / torch.sum(torch.exp((x - y).detach() ** 2 / temp))
+
+
+def img2mse_depth_softmask(x, y, temp):
+    """V:55, the `--softmask` branch of the depth loss (VC:1564-1572 on depth / far, prior / far with F.softplus(net.temp_depth)): the
+    expression of img2mse_softmask, under the reference's second name."""
+    return img2mse_softmask(x, y, temp)
+
+
+RGB_FORMS, DEPTH_FORMS = ops.RGB_FORMS, ops.DEPTH_FORMS
+
+
+def _form_depth_lines(d, prior, m, far, coef, form, lp_coef, temp, counts):
+    """The depth term of one level under a loss form other than "hardmask", as the reference writes it (m: [B] floats or None)."""
+    if form == "hardmask_coef":                                                                     # VC:1550-1551
+        if m is None:
+            return img2mse(d / far, prior / far)
+        m1, m0 = m == 1, m == 0
+        if counts is not None:
+            dl = torch.sum((d[m1] / far - prior[m1] / far) ** 2) / counts[0]
+            return dl + coef * torch.sum((d[m0] / far - prior[m0] / far) ** 2) / counts[1] if bool(counts[1] > 0) else dl
+        dl = img2mse(d[m1] / far, prior[m1] / far)
+        if bool(m0.any()):                   # `mask_cas_s.squeeze().sum() != N_rand`
+            dl = dl + coef * img2mse(d[m0] / far, prior[m0] / far)
+        return dl
+    if form in ("norm", "plain"):                                                                    # V:1762-1764, V:1770-1771
+        # `depth_cas_s[mask_cas_s.squeeze() == 0] = 0` on a copy: the reference writes into its batch slice, this does not
+        p2 = prior if m is None else torch.where(m == 0, torch.zeros_like(prior), prior)
+        a, b = (d / far, p2 / far) if form == "norm" else (d, p2)
+        return img2mse(a, b) if counts is None else torch.sum((a - b) ** 2) / (counts[0] + counts[1])
+    if form == "softlp":                                                                             # V:1760-1761
+        return img2mse_softLpmask(d / far, prior / far, lp_coef)
+    return img2mse_depth_softmask(d / far, prior / far, temp)                                        # VC:1572
+
+
+def _temps4(temp_rgb, temp_depth):
+    """(temp_rgb, temp_depth) as render_loss takes them — each None, one 0-d tensor for both levels, or a (fine, coarse) pair —
+    -> (temp_rgb, temp_depth, coarse temp_rgb, coarse temp_depth)."""
+    pair = lambda t: tuple(t) if isinstance(t, (tuple, list)) else (t, t)  # noqa: E731
+    (rf, rc), (df, dc) = pair(temp_rgb), pair(temp_depth)
+    return rf, df, rc, dc
+
+
 class Temp_Scheduler:
     """V:80-100 — the linear schedule of the pseudo-label noise level (`std_scheduler = Temp_Scheduler(total_iters, 0.2, 0.05,
     temp_min=0.05)`, V:1420): step() -> (1 - epoch / total) (base - min) + min, floored at min; epoch counts the calls (the
@@ -277,10 +351,11 @@ _TERM_NAMES = ("loss", "img_loss", "depth_loss", "patch_loss", "img_loss0", "dep
 
 
 def _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, coef, far, rgb_w, depth_w, mono, P, ps, patch_w, counts,
-                       kwargs, ssim_w=0.0, ssim_patches=4):
+                       kwargs, ssim_w=0.0, ssim_patches=4, rgb_form="hardmask", depth_form="hardmask", lp_coef=0.0, temps=None):
     """The reference's own sequence (V:1645-1865) on render()'s maps: what render_loss computes, launch by launch.  ssim_w != 0:
     + V's patch SSIM term of every level over the first ssim_patches 16 x 16 patches (loss -= ssim_w ssim_level, after the
-    level's monocular term)."""
+    level's monocular term).  rgb_form / depth_form: the other branches of V / VC as their own lines (render_loss's docstring);
+    temps = (temp_rgb, temp_depth, coarse temp_rgb, coarse temp_depth)."""
     if ssim_w != 0 and int(ps) != 16:
         raise ValueError(f"render_loss: the patch SSIM term needs 16 x 16 patches (V:1699), got patch_size {ps}")
     rgb, disp, acc, depth, extras = render(H, W, K, chunk=chunk, rays=rays, **kwargs)
@@ -288,8 +363,24 @@ def _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, coef, 
     with_depth = depth_prior is not None
     terms = {}
 
+    forms = rgb_form != "hardmask" or depth_form != "hardmask"
+    temps = temps or (None,) * 4
+    m = None if mask is None else mask.reshape(-1).to(torch.float32)
+
     def level(c, d, suffix):
-        il, dl = hardmask_losses(c, tgt, mask, coef, d if with_depth else None, depth_prior, far, counts)
+        if not forms:
+            il, dl = hardmask_losses(c, tgt, mask, coef, d if with_depth else None, depth_prior, far, counts)
+        else:
+            lv = 1 if suffix else 0
+            hard_d = with_depth and depth_form == "hardmask"
+            il, dl = hardmask_losses(c, tgt, mask, coef, d if hard_d else None, depth_prior if hard_d else None, far, counts) \
+                if (rgb_form == "hardmask" or hard_d) else (None, None)
+            if rgb_form == "softlp":
+                il = img2mse_softLpmask(c, tgt, lp_coef)                                             # V:1663-1664
+            elif rgb_form == "softmask":
+                il = img2mse_softmask(c, tgt, temps[2 * lv])                                         # VC:1526-1528
+            if with_depth and not hard_d:
+                dl = _form_depth_lines(d, depth_prior.reshape(-1), m, far, coef, depth_form, lp_coef, temps[2 * lv + 1], counts)
         part = rgb_w * il
         terms["img_loss" + suffix] = il.detach()
         if mono is not None and P > 0:
@@ -314,7 +405,7 @@ def _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, coef, 
 
 def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32, rays=None, hardmask_coef=0.2, depth_far=None,
                 rgb_w=1.0, depth_w=1.0, mono=None, patch_num=4, patch_size=16, patch_w=0.001, counts=None, ssim_w=0.0, _ss_coins=None,
-                **kwargs):
+                rgb_form="hardmask", depth_form="hardmask", lp_coef=0.0, temp_rgb=None, temp_depth=None, **kwargs):
     """The loss of one run_nerf_view.train() step as ONE call (V:1636-1865 with the terms this package builds):
 
         rgb, disp, acc, depth_pred, extras = render(H, W, K, chunk=, rays=batch_rays, retraw=True, **render_kwargs_train)
@@ -332,7 +423,48 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
     loss.backward() bit for bit.  Batches beyond one chunk, more than 8 patches, CPU tensors: the lines above, literally.
     ssim_w (0 = off, the call without the term; 0.005 = V): V's patch SSIM term on the first patch_num 16 x 16 patches of the
     batch (whether or not `mono` is given), folded into the same launches; terms gain `ssim` / `ssim0`, the level values.  LPIPS
-    stays with the caller: loss + 0.005 * lpips(...) on the returned maps, by autograd."""
+    stays with the caller: loss + 0.005 * lpips(...) on the returned maps, by autograd.
+
+    rgb_form / depth_form: the other live branches of the reference's two drivers, folded the same way (same launches, no host
+    synchronisation; the patch term, the SSIM term and the three weights compose with every form):
+        rgb_form    "hardmask" (default)  the lines above (plain img2mse when mask is None)
+                    "softlp"              img2mse_softLpmask(rgb, target_s, lp_coef)                             V:58, V:1663-1664
+                    "softmask"            img2mse_softmask(rgb, target_s, temp_rgb)                              V:50, VC:1526-1528
+        depth_form  "hardmask" (default)  V:1737
+                    "hardmask_coef"       V:1737 + hardmask_coef * img2mse(depth[m == 0] / far, prior[m == 0] / far), the second term
+                                          iff some ray has m == 0                                                VC:1550-1551
+                    "norm"                img2mse(depth / far, prior' / far) over ALL rays, prior' = 0 where m == 0     V:1762-1764
+                    "plain"               img2mse(depth, prior')                                                 V:1770-1771
+                    "softlp"              img2mse_softLpmask(depth / far, prior / far, lp_coef)                  V:1760-1761
+                    "softmask"            img2mse_depth_softmask(depth / far, prior / far, temp_depth)           V:55, VC:1572
+    "norm" / "plain": the reference ZEROES its batch slice in place (`depth_cas_s[mask_cas_s.squeeze() == 0] = 0`, so the coarse
+    level and anything later see the zeroed prior too); here the caller's depth_prior tensor is NOT modified — the zeros exist in
+    registers only.  lp_coef = args.Lp_coef.  temp_rgb / temp_depth: 0-d device tensors, ALREADY F.softplus(net.temp_rgb) /
+    F.softplus(net.temp_depth) so that the softplus stays in autograd, required by the softmask forms; loss.backward() delivers
+    their gradients.  VC takes the fine level's temperature from network_fine and the coarse level's from network_fn (VC:1527 / 1602,
+    VC:1570 / 1633): pass what VC passes, a pair (softplus(network_fine.temp_x), softplus(network_fn.temp_x)); ONE tensor = both
+    levels read it and its gradient is the sum over the levels.  Gradients: the MSE-type forms (hardmask_coef, norm, plain) bit for
+    bit equal to their lines; softlp / softmask to rounding (powf / expf against ATen's pow / exp).  counts with "norm" / "plain":
+    the mean's denominator becomes counts[0] + counts[1]; with "hardmask_coef": (n1, n0) as for the colour term; with a softlp /
+    softmask form: refused (their normaliser is a global sum of weights, which nothing all-reduces), as is _ss_coins with any
+    form."""
+    if rgb_form not in RGB_FORMS or depth_form not in DEPTH_FORMS:
+        raise ValueError(f"render_loss: unknown loss form rgb_form={rgb_form!r} / depth_form={depth_form!r}: rgb_form is one of "
+                         f"{RGB_FORMS}, depth_form one of {DEPTH_FORMS}")
+    forms = rgb_form != "hardmask" or depth_form != "hardmask"
+    soft = {rgb_form, depth_form} & {"softlp", "softmask"}
+    temps = _temps4(temp_rgb, temp_depth)
+    if forms and _ss_coins is not None:
+        raise ValueError("render_loss: the in-loop consistency step (_ss_coins, VT:941-969) has only the default loss forms")
+    if soft and counts is not None:
+        raise ValueError(f"render_loss: counts (a sharded batch) with a {sorted(soft)} form: its normaliser is a global sum of weights, "
+                         "which is not all-reduced")
+    if "softlp" in soft and not float(lp_coef) > 0:
+        raise ValueError("render_loss: a softlp form needs lp_coef > 0 (args.Lp_coef)")
+    for name, form, pair in (("temp_rgb", rgb_form, temps[0::2]), ("temp_depth", depth_form, temps[1::2])):
+        if form == "softmask" and not all(torch.is_tensor(t) and t.numel() == 1 for t in pair):
+            raise ValueError(f"render_loss: the softmask form needs {name} = F.softplus(net.{name}) as a 0-d tensor (or a (fine, coarse) "
+                             "pair of them)")
     ssim_w = float(ssim_w)
     far = float(kwargs.get('far', 1.)) if depth_far is None else float(depth_far)
     n = rays[0].reshape(-1, 3).shape[0] if rays is not None else 0
@@ -342,6 +474,7 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
     ok = (rays is not None and 0 < n <= chunk and tgt is not None and tgt.is_cuda and tgt.dtype == torch.float32 and tgt.shape[0] == n
           and kwargs.get('c2w') is None and P <= 8 and P * ps2 <= n and not torch.is_tensor(kwargs.get('near'))
           and not torch.is_tensor(kwargs.get('far')))
+    ok = ok and all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in temps)
     sP = int(patch_num) if ssim_w != 0 else 0
     if _ss_coins is not None and ssim_w != 0:
         raise ValueError("render_loss: the in-loop consistency step (VT) has no SSIM term; ssim_w must be 0 with _ss_coins")
@@ -361,9 +494,11 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
         return loss, {k: t[i] for i, k in enumerate(_TERM_NAMES)}, rgb, disp, acc, depth, extras
     if not ok:
         return _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, hardmask_coef, far, rgb_w, depth_w, mono, P,
-                                  patch_size, patch_w, counts, kwargs, ssim_w=ssim_w, ssim_patches=int(patch_num))
+                                  patch_size, patch_w, counts, kwargs, ssim_w=ssim_w, ssim_patches=int(patch_num), rgb_form=rgb_form,
+                                  depth_form=depth_form, lp_coef=lp_coef, temps=temps)
     spec = ops.ClossSpec(tgt, mask, depth_prior, far, hardmask_coef, rgb_w, depth_w, patch_w, mono, P, ps2, counts, ssim_w=ssim_w,
-                         ssim_P=sP)
+                         ssim_P=sP, rgb_form=RGB_FORMS.index(rgb_form), depth_form=DEPTH_FORMS.index(depth_form), lp_coef=float(lp_coef),
+                         temps=temps if forms else None)
     rgb, disp, acc, depth, extras = render(H, W, K, chunk=chunk, rays=rays, _target=spec, **kwargs)
     loss, t = extras.pop('loss'), extras.pop('loss_terms')
     terms = {k: t[i] for i, k in enumerate(_TERM_NAMES)}

@@ -21,7 +21,10 @@
 extern "C" {
 #endif
 
-#define CNERF_ABI_VERSION 6   /* 6 (additions since, every earlier symbol unchanged): SSIM / MS-SSIM (the ssim section below: cnerf_ssim_fwd,
+#define CNERF_ABI_VERSION 6   /* 6 (additions since, every earlier symbol, struct layout and workspace size unchanged — the number stays 6, as it did
+                                * for SSIM: nothing a v6 caller uses moved): the other live loss forms of V / VC folded into the C3 step
+                                * (cnerf_lossform, cnerf_lossform_ws_floats, cnerf_composite_fwd_lossform, cnerf_lossform_finish,
+                                * cnerf_composite_bwd_lossform) and the stand-alone cnerf_softmask_loss;  SSIM / MS-SSIM (the ssim section below: cnerf_ssim_fwd,
                                 * cnerf_ssim_bwd, cnerf_avg_pool2, cnerf_patch_ssim_loss and their workspace queries) and V's patch SSIM term
                                 * folded into the C3 step (cnerf_closs_finish_ssim, cnerf_composite_bwd_closs_ssim).
                                 * 6: + the in-loop consistency step as ONE render whose row count lives on the device: cnerf_ss_batch (the combined
@@ -339,6 +342,63 @@ int cnerf_composite_bwd_closs_ssim(const float* raw, int raw_ch, const float* z,
                                    const float* patch_d, int64_t n_patch_rays, float ssim_w, const float* ssim_d, int64_t n_ssim_rays,
                                    float* d_raw, void* stream);
 
+/* The other live loss forms of the reference's drivers folded the same way (V = run_nerf_view.py, VC =
+ * run_nerf_view_cal_correspondance.py): the three launches above with a FORM per kind of term.  d = the residual of one element.
+ *   rgb_form    CNERF_RGB_HARDMASK    V:1645-1648, as cnerf_composite_fwd_closs (mask NULL = plain img2mse)
+ *               CNERF_RGB_SOFTLP      V:58 on the 3 B colours: sum(w d^2) / sum(w), w = |d|^lp_coef + 1 (cnerf_soft_lp_loss's rules)
+ *               CNERF_RGB_SOFTMASK    V:50 on the 3 B colours: sum(w d^2) / sum(w), w = exp(d^2 / temp_rgb[0])
+ *   depth_form  CNERF_DEPTH_HARDMASK  V:1737, as cnerf_composite_fwd_closs
+ *               CNERF_DEPTH_HARDMASK_COEF  VC:1550-1551: mean over mask == 1 + coef * mean over mask == 0 (iff some mask == 0) of
+ *                                     (depth / far - prior / far)^2
+ *               CNERF_DEPTH_NORM      V:1762-1764: mean over ALL B rays of (depth / far - prior' / far)^2, prior' = 0 where mask == 0
+ *               CNERF_DEPTH_PLAIN     V:1770-1771: the same without / far
+ *               CNERF_DEPTH_SOFTLP    V:1760-1761: V:58 on depth / far, prior / far
+ *               CNERF_DEPTH_SOFTMASK  V:55 / VC:1572: V:50 on depth / far, prior / far with temp_depth[0]
+ *   x / far of the new depth forms is x * (1 / far), as ATen divides a tensor by a scalar.  The temperatures are DEVICE scalars
+ *   (already softplus'ed): nothing is read back, a captured graph sees each replay's value.
+ * forward, per level: cnerf_composite_fwd_lossform = cnerf_composite_fwd_closs with CNERF_LOSSFORM_SLOTS (10) fp64 partials per
+ *   workgroup of 8 rays in `workspace` (cnerf_lossform_ws_floats(B) floats, 8-byte aligned), fixed order, no atomics: slots 0-4 as
+ *   v6 (slot 2 = the depth form's main sum: squared residuals, or sum(w d^4) for softmask), 5-6 = the depth form's second set
+ *   (mask == 0 squares | sum(w), sum(w d^2)), 7-9 = the colour form's sum(w), sum(w d^2), sum(w d^4).
+ * cnerf_lossform_finish (ONE workgroup) = cnerf_closs_finish[_ssim] (ssim_P = 0: no SSIM term) for the forms: with L = N / Dn,
+ *   N = sum(w d^2), Dn = sum(w) (detached in d): dL/dd_i = w_i (2 d_i + 2 d_i^3 / t) / Dn and dL/dt = -(sum(w d^4) / Dn - L^2) / t^2
+ *   for softmask.  stats16 = per level 8 floats: v6's (w1, w0, wd, -) with wd = the depth form's main seed weight, [3] = the
+ *   mask == 0 depth weight (hardmask_coef), [4] = 1 / Dn of the colour form; d_temp4 = per level (rgb_w dL_rgb/dt, depth_w
+ *   dL_depth/dt), 0 where the form has no temperature.  counts (global n1, n0): hardmask / hardmask_coef as v6, norm / plain divide
+ *   by n1 + n0; refused (CNERF_E_ARG) with a softlp / softmask form, whose normaliser would need a global sum of weights.
+ * backward, per level: cnerf_composite_bwd_lossform = cnerf_composite_bwd_closs_ssim (n_ssim_rays = 0: none) with the form's seeds
+ *   formed in registers; d_temp2 / g_temp2 (nullable together) = the level's pair of cnerf_lossform_finish's d_temp4 and where to
+ *   leave it times g_loss[0]: the gradients of the level's two temperatures. */
+#define CNERF_RGB_HARDMASK 0
+#define CNERF_RGB_SOFTLP 1
+#define CNERF_RGB_SOFTMASK 2
+#define CNERF_DEPTH_HARDMASK 0
+#define CNERF_DEPTH_HARDMASK_COEF 1
+#define CNERF_DEPTH_NORM 2
+#define CNERF_DEPTH_PLAIN 3
+#define CNERF_DEPTH_SOFTLP 4
+#define CNERF_DEPTH_SOFTMASK 5
+#define CNERF_LOSSFORM_SLOTS 10
+typedef struct cnerf_lossform {
+  int32_t rgb_form, depth_form;
+  float lp_coef;             /* > 0 with a softlp form */
+  const float* temp_rgb;     /* device [1], > 0: required by CNERF_RGB_SOFTMASK */
+  const float* temp_depth;   /* device [1], > 0: required by CNERF_DEPTH_SOFTMASK */
+} cnerf_lossform;
+int64_t cnerf_lossform_ws_floats(int64_t B);
+int cnerf_composite_fwd_lossform(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride, const float* noise,
+                                 int64_t B, int S, int white_bkgd, const cnerf_closs* L, const cnerf_lossform* F, float* rgb,
+                                 float* disp, float* acc, float* depth, float* weights, float* workspace, void* stream);
+int cnerf_lossform_finish(const cnerf_closs_sum* t, const cnerf_lossform* F_last, const cnerf_lossform* F_coarse, int ssim_P,
+                          float ssim_w, const float* rgb_last, const float* rgb_coarse, const float* target, float* terms10,
+                          float* stats16, float* patch_d, float* ssim_d, float* d_temp4, void* stream);
+int cnerf_composite_bwd_lossform(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride, const float* noise,
+                                 int64_t B, int S, int white_bkgd, const cnerf_closs* L, const cnerf_lossform* F, const float* rgb,
+                                 const float* depth, const float* stats8, const float* g_loss, float rgb_w, float depth_w,
+                                 float patch_w, float coef, const float* patch_d, int64_t n_patch_rays, float ssim_w,
+                                 const float* ssim_d, int64_t n_ssim_rays, const float* d_temp2, float* g_temp2, float* d_raw,
+                                 void* stream);
+
 /* ---- a8: inverse-CDF sampling  (sample_pdf H:206-250) ------------------------------------------ */
 /* bins[B,Nb], weights[B,Nb-1], u[B,Nf] (u_row_stride 0 broadcasts one row) -> samples[B,Nf];
  * inds[B,Nf] int64 (searchsorted right=True result, the bit-exact parity target) optional.
@@ -534,6 +594,12 @@ int64_t cnerf_mse_ws_floats(int64_t n);
  * d = x - y, w = |d|^coef + 1 with the denominator detached; d_x (nullable) = the gradient w.r.t. x.  One launch, fixed order. */
 int cnerf_soft_lp_loss(const float* x, const float* y, int64_t n, float coef, float* loss, float* d_x, void* stream);
 int cnerf_mse_ws(const float* x, const float* y, int64_t n, float* loss, float* d_x, float* workspace, void* stream);
+/* img2mse_softmask / img2mse_depth_softmask (run_nerf_view.py:50 / :55; the `--softmask` loss branch, VC:1526-1528, VC:1564-1572):
+ * loss[0] = sum(w d^2) / sum(w), d = x - y, w = exp(d^2 / temp[0]), the denominator detached in d but NOT in the temperature (a
+ * DEVICE scalar > 0);  d_x (nullable) = w (2 d + 2 d^3 / t) / sum(w),  d_temp[0] (nullable) = -(sum(w d^4) / sum(w) - loss^2) / t^2.
+ * One launch, fixed order. */
+int cnerf_softmask_loss(const float* x, const float* y, int64_t n, const float* temp, float* loss, float* d_x, float* d_temp,
+                        void* stream);
 
 /* ---- a14: masked photometric / depth losses  (V:1645-1648, V:1737, V:1786-1788, V:1865) --------- */
 /* loss[0] = mean_{m==1}(rgb-t)^2 + coef*mean_{m==0}(rgb-t)^2 (second term only if some m==0);
