@@ -126,3 +126,65 @@ def analytic_scene(H, W, K, c2w, sphere_r=1.0, plane_z=-1.5):
     P = ro + t[..., None] * rd
     rgb = 0.5 + 0.5 * np.sin(3.0 * P + np.array([0.0, 1.0, 2.0]))
     return t.astype(np.float32), rgb.astype(np.float32)
+
+
+# ---- the sample-count envelope of the compositing and resampling kernels (tests/test_gpu_sample_envelope.py) -------------------
+# every dispatch of composite.hip (C = ceil(S / 64) in {1, 2, 3, 4, 8, 16}), both sides of each boundary, the padded counts between
+ENVELOPE_S = (1, 2, 63, 64, 65, 127, 129, 193, 256, 257, 300, 512, 513, 777, 1024)
+ENVELOPE_FAMILIES = ("mild", "surface")
+# (Nc, Nf): weight rows Nc - 2 on both sides of 8 and of 64 / 128 / 192 (the chunk counts of build_cdf) up to the maximum 255,
+# Nc + Nf on both sides of 256 (register bitonic sort / rank sort) up to the maximum 1024
+RESAMPLE_SHAPES = ((3, 1), (4, 5), (9, 64), (10, 63), (17, 128), (33, 223), (34, 222), (64, 192), (64, 193), (65, 191), (66, 256),
+                   (67, 128), (128, 128), (129, 128), (130, 65), (194, 300), (200, 824), (257, 767), (257, 1))
+
+
+def composite_envelope_inputs(family, S, B=9, near=2.0, far=6.0):
+    """Seeded per (family, S): raw [B,S,4], z [B,S], rays_d [B,3], density noise [B,S] in [0,1) (used with a white background),
+    and the four upstream gradients g_rgb [B,3], g_disp / g_acc / g_depth [B] ~ N(0,1).
+      mild     raw ~ 3 N(0,1), z sorted uniform in [near, far], rays_d ~ N(0,1)  (raw2outputs_inputs), one density per ray made
+               positive so that a ray of one or two samples is not empty
+      surface  what a trained network produces: empty space (sigma = -5|N(0,1)| - 0.1) around ONE opaque run per ray of random
+               start and length 1 .. max(2, S/4) with sigma = 10^U(0, 3.5) (alpha == 1 in fp32, so the transmittance factor is the
+               bare 1e-10), and a zero-width interval z[S/2] == z[S/2 - 1] (what resampling at a CDF tie creates) for S > 3
+    Ray 0 has negative density everywhere, noise included: acc == 0 and disp is NaN (R:302); g_disp[0] = 0."""
+    assert family in ENVELOPE_FAMILIES
+    rs = np.random.RandomState(1000 * (1 + ENVELOPE_FAMILIES.index(family)) + S)
+    raw = rs.normal(size=(B, S, 4)) * 3.0
+    z = np.sort(rs.uniform(near, far, size=(B, S)), -1)
+    d = rs.normal(size=(B, 3))
+    if family == "surface":
+        raw[..., 3] = -5.0 * np.abs(rs.normal(size=(B, S))) - 0.1
+        for b in range(1, B):
+            start, length = rs.randint(0, S), rs.randint(1, max(2, S // 4) + 1)
+            raw[b, start:start + length, 3] = 10.0 ** rs.uniform(0.0, 3.5, size=raw[b, start:start + length, 3].shape)
+        if S > 3:
+            z[:, S // 2] = z[:, S // 2 - 1]
+    else:
+        for b in range(1, B):          # no ray but ray 0 is empty, at any S
+            raw[b, b % S, 3] = np.abs(raw[b, b % S, 3]) + 0.1
+    raw[0, :, 3] = -np.abs(raw[0, :, 3]) - 1.1
+    noise = rs.uniform(size=(B, S))
+    g = [rs.normal(size=(B, 3))] + [rs.normal(size=(B,)) for _ in range(3)]
+    g[1][0] = 0.0
+    return tuple(a.astype(np.float32) for a in [raw, z, d, noise] + g)
+
+
+def resample_envelope_inputs(Nc, B=13, near=2.0, far=6.0):
+    """z [B,Nc] sorted uniform in [near, far] and coarse weights [B,Nc] = uniform^8 (peaky), seeded per Nc; the resampler reads
+    weights[:, 1:-1] over the Nc - 1 midpoints of z.  Row 0 is all zero (a uniform pdf through the 1e-5 floor), row 1 is zero on
+    [1, Nc//2): a flat run of the CDF whose every entry ties with its neighbour's."""
+    rs = np.random.RandomState(5000 + Nc)
+    z = np.sort(rs.uniform(near, far, size=(B, Nc)), -1).astype(np.float32)
+    w = (rs.uniform(size=(B, Nc)) ** 8).astype(np.float32)
+    w[0] = 0.0
+    w[1, 1:Nc // 2] = 0.0
+    return z, w
+
+
+def resample_envelope_u(tag, B, Nf):
+    """The two streams of the reference's sample_pdf(..., pytest=True): det = linspace(0, 1, Nf) in float64 cast to fp32 (H:224-226,
+    u = 1 ties with the last CDF entry on every row), rand = np.random.seed(0); np.random.rand(B, Nf) (H:227-229)."""
+    if tag == "det":
+        return np.broadcast_to(np.linspace(0., 1., Nf), (B, Nf)).astype(np.float32).copy()
+    np.random.seed(0)
+    return np.random.rand(B, Nf).astype(np.float32)

@@ -131,6 +131,18 @@ def test_composite_with_the_loss_folded_in(dev, B, S, white):
     """cnerf_composite_fwd_mse / _bwd_mse vs cnerf_composite_fwd + cnerf_mse + `d_x * g` + cnerf_composite_bwd: the maps and d_raw
     bit for bit; the loss to fp64-association round-off (a different, fixed, order of the same fp64 sum) — and identical across
     repeated launches (fixed-order second stage by whichever workgroup finishes last; the ticket counter re-arms itself)."""
+    _composite_with_the_loss_folded_in(dev, B, S, white)
+
+
+@pytest.mark.parametrize("B", [5, 257])
+@pytest.mark.parametrize("S,white", [(300, False), (1024, True)])
+def test_composite_with_the_loss_folded_in_large_sample_counts(dev, B, S, white):
+    """The same at 8 and 16 samples per lane (C = ceil(S / 64) of composite.hip's dispatch): the MSE-form instantiations
+    composite_fwd_k<8 | 16, MSE_WAVES> and composite_bwd_k<8 | 16> with the seed formed in-kernel against the plain ones."""
+    _composite_with_the_loss_folded_in(dev, B, S, white)
+
+
+def _composite_with_the_loss_folded_in(dev, B, S, white):
     from consistentnerf_amd import ops
     g = torch.Generator(device=dev).manual_seed(B * 7 + S)
     raw = torch.randn(B, S, 4, device=dev, generator=g) * 2

@@ -144,10 +144,10 @@ def _dist(a, ref):
     return float((a.double() - ref.double()).abs().max())
 
 
-def kernel_batch(dev, b, mask_kind):
+def kernel_batch(dev, b, mask_kind, s=S):
     g = torch.Generator(device="cpu").manual_seed(100 + b)
-    raw = (torch.randn(b, S, 4, generator=g) * 3).to(dev)
-    z = torch.sort(torch.rand(b, S, generator=g) * (FAR - NEAR) + NEAR, -1).values.to(dev)
+    raw = (torch.randn(b, s, 4, generator=g) * 3).to(dev)
+    z = torch.sort(torch.rand(b, s, generator=g) * (FAR - NEAR) + NEAR, -1).values.to(dev)
     rays = T(I.ray_batch(b, seed=b, near=NEAR, far=FAR), dev)
     tgt = torch.rand(b, 3, generator=g).to(dev)
     prior = (torch.rand(b, generator=g) * (FAR - NEAR) + NEAR).to(dev)
@@ -192,8 +192,18 @@ def test_lossform_kernels_vs_float64_lines(dev, b, mask_kind, rf, df):
     gradients 1e-5 (a difference of two such sums, sum(w d^4) / Dn - L^2, which cancels to about a tenth of its terms), and d_raw
     against cnerf_composite_bwd fed with the float64 seeds, 2e-6 of its largest element (the softlp bound of the issue; each seed is
     <= 6 fp32 operations from its float64 value)."""
+    _lossform_kernels_vs_float64_lines(dev, b, mask_kind, rf, df, S)
+
+
+def test_lossform_kernels_vs_float64_lines_at_300_samples(dev):
+    """The same at S = 300: the FORMS instantiations of 8 samples per lane (composite_fwd_k<8, MSE_WAVES, true>,
+    composite_bwd_k<8, true>), lanes 38 ... 63 of every ray dead."""
+    _lossform_kernels_vs_float64_lines(dev, 13, "mixed", "softmask", "softmask", 300)
+
+
+def _lossform_kernels_vs_float64_lines(dev, b, mask_kind, rf, df, s):
     from consistentnerf_amd import ops
-    raw, z, rays, tgt, prior, mask = kernel_batch(dev, b, mask_kind)
+    raw, z, rays, tgt, prior, mask = kernel_batch(dev, b, mask_kind, s)
     temps = (torch.tensor([0.40318605], device=dev), torch.tensor([0.3], device=dev))
     L = ops.ClossSpec(tgt, mask, prior, FAR, 0.2, 1.0, 0.1, 0.0, rgb_form=ops.RGB_FORMS.index(rf), depth_form=ops.DEPTH_FORMS.index(df),
                       lp_coef=0.5, temps=temps + temps).checked(b)

@@ -15,6 +15,10 @@ Stated tolerances (fp32 path, v_mfma_f32_32x32x2_f32 + OCML sin/cos/exp vs ATen/
   end to end (fine level)  |d rgb| <= 5e-3, PSNR-equivalent >= 50 dB vs the capture (conditioning of the
                            2^9-frequency encoding, see test_render_rays_golden); 2e-5 when the oracle is evaluated at
                            the kernel's own sample depths
+Sample counts: the tests of this file stay at Nc <= 64, Nf <= 192 except test_render_rays_large_sample_counts_vs_oracle (Nc up to 200,
+Nc + Nf up to 1024, same tolerances).  The kernels' whole envelope — compositing at S = 1 ... 1024 against float64 (maps 2e-5, d_raw
+1e-5 max|g|), resampling at Nc = 3 ... 257 and Nc + Nf <= 1024 (indices bit-exact INCLUDING ties against the reference, merged depths
+bit-exact against torch.sort, z_std 4 ulp), the limits beyond — is tests/test_gpu_sample_envelope.py.
 """
 import os
 
@@ -541,6 +545,50 @@ def test_random_render_rays_vs_oracle(dev, D, W, Nc, Nf, perturb, white, noise, 
     of anything, single rays, both backgrounds, density noise and inverse-depth spacing: the coarse level against the oracle at
     2e-5 (its depths are bit-exact), the fine level and the parameter gradients against the oracle evaluated at the kernel's own
     fine depths on the kernel's ReLU branch (2e-5 / 1e-5 max per tensor)."""
+    _render_rays_vs_oracle(dev, D, W, Nc, Nf, perturb, white, noise, lindisp, B, wseed)
+
+
+LARGE_RR = [(2, 64, 128, 256, 1.0, False, 0.0, False, 5), (2, 64, 64, 960, 0.0, True, 1.0, False, 3),
+            (4, 128, 200, 100, 1.0, False, 0.0, True, 5)]
+
+
+@pytest.mark.parametrize("D,W,Nc,Nf,perturb,white,noise,lindisp,B", LARGE_RR)
+def test_render_rays_large_sample_counts_vs_oracle(dev, D, W, Nc, Nf, perturb, white, noise, lindisp, B):
+    """a3 past the C2 corner, at the sweep's tolerances: 2, 3 and 4 CDF chunks per lane (Nc = 128, 200), the rank sort (Nc + Nf >
+    256), 8 and 16 samples per lane in the compositing of the fine level (384, 300 and the maximum 1024 samples per ray)."""
+    _render_rays_vs_oracle(dev, D, W, Nc, Nf, perturb, white, noise, lindisp, B, 400 + Nc)
+
+
+@fp32_only
+def test_render_fwd_bwd_single_call_at_1024_samples(dev):
+    """cnerf_render_fwd / cnerf_render_bwd at Nc + Nf = 64 + 960 (white background): every map and every parameter gradient bit for
+    bit against the Python surface, as test_render_fwd_bwd_single_call_equals_python_surface."""
+    from consistentnerf_amd import ops, run_nerf as R
+    from consistentnerf_amd.run_nerf_helpers import pytest_uniform, sample_u
+    D, W, Nc, Nf, perturb, white, noise, lindisp, B = LARGE_RR[1]
+    coarse, _ = make_model(D, W, True, 5, 51, dev)
+    fine, _ = make_model(D, W, True, 5, 52, dev)
+    rays = T(I.ray_batch(B, seed=9), dev)
+    ret = R.render_rays(rays, retraw=True, pytest=True, _with_depth=True, **_kwargs(coarse, fine, Nc, Nf, perturb, white, noise, lindisp))
+    keys = ["rgb_map", "disp_map", "acc_map", "depth_map", "rgb0", "disp0", "acc0", "depth0"]
+    rs = np.random.RandomState(4)
+    gin = {k: T(rs.normal(size=tuple(ret[k].shape)).astype(np.float32), dev) for k in keys}
+    sum((ret[k] * gin[k]).sum() for k in keys).backward()
+    out, st = ops.render_forward(coarse.spec(), R._packed(coarse), fine.spec(), R._packed(fine), rays, Nc, Nf, t_rand=None,
+                                 u=sample_u(B, Nf, True, True, dev), noise0=pytest_uniform((B, Nc), dev) * noise,
+                                 noise1=pytest_uniform((B, Nc + Nf), dev) * noise, white_bkgd=white, train=True, retraw=True)
+    for k in keys + ["raw", "z_std"]:
+        assert torch.equal(out[k], ret[k]) or (k.startswith("disp") and np.array_equal(
+            out[k].cpu().numpy(), ret[k].detach().cpu().numpy(), equal_nan=True)), k
+    gc = [torch.empty_like(p) for p in coarse.kernel_tensors()]
+    gf = [torch.empty_like(p) for p in fine.kernel_tensors()]
+    ops.render_backward(st, gin, gc, gf)
+    for gs, model in ((gc, coarse), (gf, fine)):
+        for got, p in zip(gs, model.kernel_tensors()):   # tensors the network does not use get zeros / no .grad
+            assert torch.equal(got, p.grad) if p.grad is not None else not got.any()
+
+
+def _render_rays_vs_oracle(dev, D, W, Nc, Nf, perturb, white, noise, lindisp, B, wseed):
     from consistentnerf_amd import run_nerf_view as V
     far = 6.0
     coarse, sdc_np = make_model(D, W, True, 5, wseed, dev)

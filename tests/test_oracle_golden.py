@@ -98,6 +98,58 @@ def test_sample_pdf(tag):
         eq(O.pytest_uniform((256, 128)), g["u"], "u stream")
 
 
+@pytest.mark.parametrize("tag", ["det", "rand"])
+def test_sample_pdf_lengths(tag):
+    """The reference's sample_pdf on 19 (Nc, Nf) shapes (CDF rows of 1 ... 255 weights, up to 1024 merged depths; an all-zero row
+    and a row with a flat CDF run in each; tests/golden/make_golden_sample_lengths.py): the oracle reproduces every index, ties
+    included, and every sample."""
+    g = golden("sample_pdf_lengths")
+    for Nc, Nf in I.RESAMPLE_SHAPES:
+        z, w = I.resample_envelope_inputs(Nc)
+        zt = T(z)
+        samples, inds = O.sample_pdf(0.5 * (zt[:, 1:] + zt[:, :-1]), T(w)[:, 1:-1], T(I.resample_envelope_u(tag, z.shape[0], Nf)))
+        eq(inds, g[f"{Nc}_{Nf}_{tag}_inds"].astype(np.int64), f"inds {Nc} {Nf}")
+        eq(samples, g[f"{Nc}_{Nf}_{tag}_samples"], f"samples {Nc} {Nf}")
+    eq(O.pytest_uniform((13, 824)), I.resample_envelope_u("rand", 13, 824), "u stream")
+
+
+def aten_row_sum_np(x):
+    """sampling.hip::aten_row_sum restated in numpy, rows in parallel: x [R, n] fp32 -> [R] fp32.  8-float vectors (scalars for
+    n < 8), vector i of a group of four to accumulator i & 3, leftover vectors to accumulator 0, acc0 += acc1, acc2, acc3, then the
+    n % 8 tail summed from zero and the 8 lanes added to it in lane order."""
+    R, n = x.shape
+    V = 8 if n >= 8 else 1
+    nv = n // V
+    ilp = nv >> 2
+    xv = x[:, :nv * V].reshape(R, nv, V)
+    p = np.zeros((4, R, V), np.float32)
+    for i in range(ilp):
+        for k in range(4):
+            p[k] += xv[:, 4 * i + k]
+    for i in range(4 * ilp, nv):
+        p[0] += xv[:, i]
+    p0 = p[0] + p[1]
+    p0 = p0 + p[2]
+    p0 = p0 + p[3]
+    acc = np.zeros(R, np.float32)
+    for k in range(nv * V, n):
+        acc = acc + x[:, k]
+    for lane in range(V):
+        acc = acc + p0[:, lane]
+    return acc
+
+
+def test_aten_row_sum_restatement_equals_torch_sum():
+    """The association sampling.hip claims for torch.sum(x, -1) on the CPU, for every row length the resampler admits (1 ... 255
+    weights) and for batches of 300 and of 1 ... 3 rows: bit for bit.  One ulp of this sum decides the index at a CDF tie."""
+    rs = np.random.RandomState(62)
+    for n in range(1, 256):
+        for R in (300, 1, 2, 3):
+            x = (rs.uniform(size=(R, n)) ** 8).astype(np.float32) + np.float32(1e-5)
+            got, want = aten_row_sum_np(x), torch.sum(T(x), -1).numpy()
+            assert np.array_equal(got, want), (n, R, int((got != want).sum()))
+
+
 def _bulk_u(tag, B=4096, Nf=128):
     """the u of the reference's call: linspace(0, 1, Nf) broadcast (det, H:224-226) or its pytest stream (H:227-229)"""
     if tag == "det":
