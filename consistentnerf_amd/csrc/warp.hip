@@ -54,12 +54,14 @@ __global__ void warp_points_k(const float* __restrict__ P, int64_t N, Mat34 w2c,
 
 constexpr int KMAX = 300;   // thr0 * 2^k overflows to +inf long before this: every finite |diff| passes
 
-// smallest k >= 0 with diff < thr0 * 2^k (thr doubled in fp32 exactly like V:1026-1029)
+// smallest k >= 0 with diff < thr0 * 2^k (thr doubled in fp32 exactly like V:1026-1029).  A NaN or +inf diff (a non-finite depth
+// prior) passes no rung, not even thr = +inf — the reference doubles forever there — and gets KMAX + 1, the level of a pixel that
+// is out of bounds: it never enters a mask, and a chunk with no other in-bounds pixel is a chunk without one (thr = NaN).
 __device__ __forceinline__ int pass_level(float diff, float thr0) {
   float thr = thr0;
   int k = 0;
   while (!(diff < thr) && k < KMAX) { thr = 2.f * thr; ++k; }
-  return k;
+  return diff < thr ? k : KMAX + 1;
 }
 
 __global__ __launch_bounds__(256) void hard_mask_k(int H, int W, float fx, float fy, float cx, float cy, Mat34 c2w_t,
@@ -303,8 +305,8 @@ __global__ __launch_bounds__(1024) void ss_ref_rays_k(SsDev a, const float* __re
 extern "C" int cnerf_warp_points(const float* P, int64_t N, const float* w2c_host, float fx, float fy, float cx,
                                  float cy, int H, int W, int flip, float* Xc, float* px, float* py, uint8_t* inb,
                                  void* stream) {
-  if (!P || !w2c_host || N < 0 || H < 2 || W < 2) return CNERF_E_ARG;
-  if (N == 0) return CNERF_OK;
+  if (!w2c_host || N < 0 || (N > 0 && !P) || H < 2 || W < 2) return CNERF_E_ARG;
+  if (N == 0) return CNERF_OK;   // (an empty tensor's pointer is null)
   hipLaunchKernelGGL(warp_points_k, dim3((unsigned)cn_div_up(N, 256)), dim3(256), 0, cn_stream(stream), P, N,
                      load34(w2c_host), fx, fy, cx, cy, H, W, flip, Xc, px, py, inb);
   CN_CHECK_LAUNCH();

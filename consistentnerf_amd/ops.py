@@ -1003,7 +1003,18 @@ def ss_batch(rays_o: Tensor, rays_d: Tensor, depth: Tensor, target_s: Tensor, w2
 
 def hard_mask_pair(H, W, K, c2w_tgt, w2c_ref, depth_tgt: Tensor, depth_ref: Tensor, thr0: float, chunk: int,
                    mask: Tensor, want_thr: bool = False):
+    """cnerf_hard_mask_pair: ORs into mask (uint8 [H * W], in place) the pixels of the target view that pass against ONE reference
+    view -> the per-chunk thresholds (NaN: no pixel of the chunk can pass) with want_thr, else None.  The kernel indexes all three
+    buffers by pixel: their sizes are checked here."""
     depth_tgt, depth_ref = _chk(depth_tgt, "depth_tgt"), _chk(depth_ref, "depth_ref")
+    H, W, chunk = int(H), int(W), int(chunk)
+    if chunk <= 0:
+        raise CnerfError(f"hard_mask_pair: chunk must be positive (got {chunk})")
+    if depth_tgt.numel() != H * W or depth_ref.numel() != H * W or mask.numel() != H * W:
+        raise CnerfError(f"hard_mask_pair: depth_tgt, depth_ref and mask must hold H * W = {H * W} elements "
+                         f"(got {depth_tgt.numel()}, {depth_ref.numel()}, {mask.numel()})")
+    if mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.device != depth_tgt.device or depth_ref.device != depth_tgt.device:
+        raise CnerfError("hard_mask_pair: mask must be a contiguous uint8 tensor on the device of the depths (it is written in place)")
     nchunks = (H * W + chunk - 1) // chunk
     thr = torch.empty(nchunks, device=mask.device) if want_thr else None
     _lib.check(_lib.load().cnerf_hard_mask_pair(H, W, float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]),

@@ -188,3 +188,271 @@ def resample_envelope_u(tag, B, Nf):
         return np.broadcast_to(np.linspace(0., 1., Nf), (B, Nf)).astype(np.float32).copy()
     np.random.seed(0)
     return np.random.rand(B, Nf).astype(np.float32)
+
+
+# ---- the input range of the warp, hard-mask and encoding kernels (tests/test_gpu_geometry_envelope.py, test_geometry_inputs.py) --
+# (H, W, focal): the smallest scenes with several workgroups per pair, ragged last chunks and chunks without an in-bounds pixel
+GEOMETRY_SCENES = ((24, 32, 36.0), (37, 53, 58.0), (48, 64, 70.0))
+GEOMETRY_TRAIN = (0, 1, 2)            # view 3 is held out: its mask stays zero
+# every threshold ladder the tests climb: the default, a fine one, one that stops every chunk at level 0, one that needs more than
+# 64 doublings (2^-80 * 2^k reaches the differences of these scenes at k = 68 ... 89, pixel by pixel)
+GEOMETRY_THR0 = (0.1, 1e-6, 1e3, 2.0 ** -80)
+KMAX = 300                            # warp.hip: the ladder ends there (thr0 * 2^k is +inf in fp32 long before)
+NO_LEVEL = KMAX + 1                   # the level of a pixel that is out of bounds or whose |z - D_ref| is not finite
+U32 = 2.0 ** -24                      # unit round-off of fp32
+
+
+def geometry_poses():
+    """Four c2w [3,4]: three close views and one 75 degrees round, from which most target pixels project outside the image."""
+    return np.stack([camera_pose(0.0, -15.0, 4.0), camera_pose(13.0, -11.0, 4.1), camera_pose(75.0, -14.0, 3.9),
+                     camera_pose(-17.0, -19.0, 4.0)])
+
+
+def geometry_scene(H, W, focal, poses=None, bias_view=1, bias=0.35, fy_ratio=1.07, c_off=(1.37, -0.81)):
+    """analytic_scene seen through a camera with fy != fx and a principal point off the centre by a non-integer amount; the depth
+    prior of `bias_view` is biased (make_golden.fx_hardmask's trick) so that chunks need threshold doublings.
+    -> K [3,3] fp32, poses [N,3,4] fp32, depths [N,H,W] fp32."""
+    poses = geometry_poses() if poses is None else np.asarray(poses, np.float32)
+    K = np.array([[focal, 0, 0.5 * W + c_off[0]], [0, focal * fy_ratio, 0.5 * H + c_off[1]], [0, 0, 1]], np.float32)
+    depths = np.stack([analytic_scene(H, W, K.astype(np.float64), p)[0] for p in poses])
+    depths[bias_view] = depths[bias_view] + np.float32(bias)
+    return K, poses, depths
+
+
+def ladder(thr0):
+    """thr0 * 2^k for k = 0 .. KMAX, doubled in fp32 as warp.hip and the reference (V:1026-1029) form them -> float64 [KMAX + 1]."""
+    r = np.empty(KMAX + 1, np.float32)
+    t = np.float32(thr0)
+    with np.errstate(over="ignore"):
+        for k in range(KMAX + 1):
+            r[k] = t
+            t = np.float32(2.0) * t
+    return r.astype(np.float64)
+
+
+def ladder_level(diff, thr0):
+    """smallest k with diff < thr0 * 2^k; NO_LEVEL where diff is NaN or +inf (no rung, not even +inf, lets it pass)."""
+    return np.searchsorted(ladder(thr0), diff, side="right")      # NaN sorts behind +inf
+
+
+def _w2c64(c2w):
+    m = np.eye(4)
+    m[:3, :4] = np.asarray(c2w, np.float64)[:3, :4]
+    return np.linalg.inv(m)
+
+
+def project_f64(P, w2c, K, H, W, flip=True):
+    """The warp (oracle.warp_points, warp.hip `project`) in float64 -> dict: Xc [N,3], px, py (BEFORE rounding), x, y (rounded
+    half to even), inb (strict bounds on the rounded pixel), and err: a first-order bound on the distance of an fp32 evaluation of
+    px / py from these (4 roundings per camera coordinate, 3 for K's row, one for the division), used to decide which rows two
+    fp32 evaluations may round differently."""
+    P, w2c, K = np.asarray(P, np.float64), np.asarray(w2c, np.float64), np.asarray(K, np.float64)
+    R, t = w2c[:3, :3], w2c[:3, 3]
+    Xc = P @ R.T + t
+    S = np.abs(P) @ np.abs(R).T + np.abs(t)                      # sum of |terms| per camera coordinate
+    if flip:
+        Xc = Xc * np.array([1.0, -1.0, -1.0])
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    with np.errstate(all="ignore"):
+        zc = Xc[:, 2]
+        px, py = (Xc[:, 0] * fx + zc * cx) / zc, (Xc[:, 1] * fy + zc * cy) / zc
+        ex = (4 * (fx * S[:, 0] + abs(cx) * S[:, 2]) + 2 * (np.abs(Xc[:, 0]) * fx + np.abs(zc * cx))) / np.abs(zc) \
+            + np.abs(px) * (4 * S[:, 2] / np.abs(zc) + 2)
+        ey = (4 * (fy * S[:, 1] + abs(cy) * S[:, 2]) + 2 * (np.abs(Xc[:, 1]) * fy + np.abs(zc * cy))) / np.abs(zc) \
+            + np.abs(py) * (4 * S[:, 2] / np.abs(zc) + 2)
+        x, y = np.rint(px), np.rint(py)
+        inb = (x > 0) & (x < W - 1) & (y > 0) & (y < H - 1)
+    return dict(Xc=Xc, S=S, px=px, py=py, x=x, y=y, inb=inb, err=U32 * np.maximum(ex, ey))
+
+
+def pixel_margin(px, py, H, W):
+    """Distance in pixels of (px, py) from the nearest rounding tie (x.5) and from the strict border (0.5, W - 1.5, 0.5, H - 1.5)."""
+    with np.errstate(all="ignore"):
+        tie = np.minimum(np.abs(px - np.floor(px) - 0.5), np.abs(py - np.floor(py) - 0.5))
+        edge = np.minimum(np.minimum(np.abs(px - 0.5), np.abs(px - (W - 1.5))), np.minimum(np.abs(py - 0.5), np.abs(py - (H - 1.5))))
+    return np.minimum(tie, edge)
+
+
+def hard_mask_pair_f64(H, W, K, c2w_tgt, c2w_ref, depth_tgt, depth_ref, thr0):
+    """The hard-mask rule (V:1008-1041) for ONE (target, reference) pair in float64, per target pixel in row-major order -> dict:
+    px, py (projected pixel before rounding), inb, diff = |z - D_ref| (NaN where out of bounds), level (ladder_level, NO_LEVEL
+    where out of bounds or not finite) and margin (pixel_margin)."""
+    K64 = np.asarray(K, np.float64)
+    j, i = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    dirs = np.stack([(i - K64[0, 2]) / K64[0, 0], -(j - K64[1, 2]) / K64[1, 1], -np.ones_like(i)], -1).reshape(-1, 3)
+    c2w = np.asarray(c2w_tgt, np.float64)
+    P = c2w[:3, 3] + np.asarray(depth_tgt, np.float64).reshape(-1, 1) * (dirs @ c2w[:3, :3].T)
+    p = project_f64(P, _w2c64(c2w_ref), K64, H, W, True)
+    inb = p["inb"]
+    diff = np.full(H * W, np.nan)
+    yi, xi = p["y"][inb].astype(np.int64), p["x"][inb].astype(np.int64)
+    with np.errstate(invalid="ignore"):
+        diff[inb] = np.abs(p["Xc"][inb, 2] - np.asarray(depth_ref, np.float64).reshape(H, W)[yi, xi])
+    level = np.where(inb, ladder_level(diff, thr0), NO_LEVEL)
+    return dict(px=p["px"], py=p["py"], inb=inb, diff=diff, level=level, margin=pixel_margin(p["px"], p["py"], H, W), z=p["Xc"][:, 2])
+
+
+def chunk_levels(level, chunk):
+    """Per chunk of `chunk` consecutive pixels: the smallest level in it (NO_LEVEL: nothing in it can pass) -> int [nchunks]."""
+    return np.minimum.reduceat(level, np.arange(0, level.shape[0], chunk))
+
+
+def hard_masks_f64(H, W, K, poses, depths, i_train, thr0, chunk):
+    """oracle.hard_masks restated on hard_mask_pair_f64 -> (masks [N,H,W] bool, {(t, r): fp32 [nchunks] thresholds, NaN for a chunk
+    in which nothing can pass}, the largest level any chunk climbed to).  A pixel is set when its level is its chunk's minimum."""
+    N = len(poses)
+    rungs = ladder(thr0).astype(np.float32)
+    masks, thr, deepest = np.zeros((N, H * W), bool), {}, 0
+    for t in i_train:
+        for r in i_train:
+            if r == t:
+                continue
+            lv = hard_mask_pair_f64(H, W, K, poses[t], poses[r], depths[t], depths[r], thr0)["level"]
+            km = chunk_levels(lv, chunk)
+            live = km < NO_LEVEL
+            masks[t] |= live.repeat(chunk)[:H * W] & (lv == km.repeat(chunk)[:H * W])
+            thr[(t, r)] = np.where(live, rungs[np.minimum(km, KMAX)], np.float32(np.nan)).astype(np.float32)
+            deepest = max(deepest, int(km[live].max()) if live.any() else 0)
+    return masks.reshape(N, H, W), thr, deepest
+
+
+# |z - D_ref| of two fp32 evaluations differs by the roundings of the target ray (3), the point (2), the camera coordinate (4) and
+# the host's fp32 matrix inverse: below 32 u times the scene's extent (camera distance 4 + depth <= 8 -> 12), whatever the rung
+DIFF_ABS_MARGIN = 32 * U32 * 12.0
+
+
+def _undecided(H, W, K, poses, depths, t, r, thr0s):
+    q = hard_mask_pair_f64(H, W, K, poses[t], poses[r], depths[t], depths[r], thr0s[0])
+    bad = q["margin"] < 1e-3
+    for thr0 in thr0s:
+        rungs = ladder(thr0)
+        rungs = rungs[np.isfinite(rungs)]
+        d = np.where(q["inb"], q["diff"], np.inf)
+        near = np.abs(d[:, None] - rungs[None, :]) < np.maximum(1e-4 * rungs[None, :], DIFF_ABS_MARGIN)
+        bad |= near.any(-1)
+    return bad
+
+
+def condition_hard_mask_inputs(H, W, K, poses, depths, i_train=GEOMETRY_TRAIN, thr0s=GEOMETRY_THR0, max_iter=8, max_share=0.02):
+    """The kernel's scalar arithmetic and ATen's matmul are two fp32 evaluations of the same formulas and may disagree on a pixel
+    that sits on a decision boundary.  The depth prior is free input: a target pixel's prior is multiplied by 1 + 3e-3 while, for
+    any reference view and in float64, its projection is within 1e-3 px of a rounding tie or of the strict border, or its
+    |z - D_ref| is within 1e-4 relative (or DIFF_ABS_MARGIN absolute, which matters for rungs below it) of a rung of any ladder in
+    `thr0s`.  All pairs at once, to a fixed point: a nudged prior is also the reference prior of the other views.
+    -> (depths fp32, dict(iterations, nudged_share per view)); raises if the fixed point needs more than `max_iter` iterations or
+    more than `max_share` of a view's pixels are touched."""
+    depths = np.array(depths, np.float32)
+    touched = np.zeros((len(poses), H * W), bool)
+    for it in range(max_iter + 1):
+        bad = np.zeros_like(touched)
+        for t in i_train:
+            for r in i_train:
+                if r != t:
+                    bad[t] |= _undecided(H, W, K, poses, depths, t, r, thr0s)
+        if not bad.any():
+            share = touched.mean(-1)
+            if share.max() > max_share:
+                raise AssertionError(f"conditioning touched {share.max():.2%} of a view's pixels (cap {max_share:.0%})")
+            return depths, dict(iterations=it, nudged_share=[float(s) for s in share])
+        touched |= bad
+        flat = depths.reshape(len(poses), -1)
+        flat[bad] = flat[bad] * np.float32(1.0 + 3e-3)
+    raise AssertionError(f"conditioning did not reach a fixed point within {max_iter} iterations")
+
+
+_GEOMETRY_CASES = {}
+
+
+def geometry_case(idx):
+    """Scene `idx` of GEOMETRY_SCENES, conditioned (cached) -> dict(H, W, K, poses, depths, raw_depths, info)."""
+    if idx not in _GEOMETRY_CASES:
+        H, W, focal = GEOMETRY_SCENES[idx]
+        K, poses, raw = geometry_scene(H, W, focal)
+        depths, info = condition_hard_mask_inputs(H, W, K, poses, raw)
+        _GEOMETRY_CASES[idx] = dict(H=H, W=W, K=K, poses=poses, depths=depths, raw_depths=raw, info=info)
+    return _GEOMETRY_CASES[idx]
+
+
+def geometry_chunks(H, W):
+    return (1, 7, 255, 256, 257, 1000, H * W - 1, H * W, H * W + 5, 5120)
+
+
+def hard_mask_cases():
+    """(scene, i_train, chunk, thr0) of the oracle comparison: every chunk size x the two ordinary ladders on every scene (chunk = 1
+    only on the smallest scene with two training views: one oracle iteration per pixel and pair), plus the level-0 and the deep
+    ladder at a ragged chunk size."""
+    out = []
+    for s, (H, W, _) in enumerate(GEOMETRY_SCENES):
+        for chunk in geometry_chunks(H, W):
+            for thr0 in GEOMETRY_THR0[:2]:
+                if chunk == 1 and s != 0:
+                    continue
+                out.append((s, (0, 1) if chunk == 1 else GEOMETRY_TRAIN, chunk, thr0))
+        for thr0 in GEOMETRY_THR0[2:]:
+            out.append((s, GEOMETRY_TRAIN, 257, thr0))
+    return out
+
+
+WARP_N = (0, 1, 255, 256, 257, 100003)
+
+
+# shares of the random kinds among the rows that are not scene points.  Around a camera 4 units from the origin, a point 1e-2 away
+# is ill-conditioned IN FP32 WORLD COORDINATES (P R^T + t cancels to 1e-2 of its terms: the pixel of a third of them is uncertain
+# by more than its distance to a tie), so that kind is kept small: the rows no fp32 evaluation can decide must stay below 2 %
+WARP_SCALES = ((1e-2, 0.005), (1.0, 0.05), (1e2, 0.45), (1e4, 0.495))
+
+
+def warp_envelope_points(case, n=WARP_N[-1], seed=7, view=0, ref=1):
+    """World points for warp_points_k, shuffled so that every prefix holds several kinds: the back-projected pixels of `view` of a
+    geometry_case, the same mirrored through the reference camera's centre (behind it, yet with the same pixel: the reference
+    tests no depth sign), and random points c_ref + s N(0, 1) at the scales s of WARP_SCALES around the reference camera.
+    -> P [n,3] fp32, the reference camera's c2w [3,4] fp32 (the caller inverts it in fp32, as the host code does)."""
+    H, W, K, poses = case["H"], case["W"], case["K"].astype(np.float64), case["poses"]
+    rs = np.random.RandomState(seed)
+    j, i = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    dirs = np.stack([(i - K[0, 2]) / K[0, 0], -(j - K[1, 2]) / K[1, 1], -np.ones_like(i)], -1).reshape(-1, 3)
+    c2w = poses[view].astype(np.float64)
+    scene = c2w[:3, 3] + case["depths"][view].reshape(-1, 1).astype(np.float64) * (dirs @ c2w[:3, :3].T)
+    c_ref = poses[ref][:3, 3].astype(np.float64)
+    parts = [scene, 2 * c_ref - scene]
+    rest = max(0, n - 2 * scene.shape[0])
+    parts += [c_ref + s * rs.normal(size=(int(np.ceil(rest * share)), 3)) for s, share in WARP_SCALES]
+    P = np.concatenate(parts)[:n]
+    return P[rs.permutation(P.shape[0])].astype(np.float32), poses[ref]
+
+
+def warp_decided_rows(P, w2c, K, H, W, flip):
+    """project_f64 of the fp32 inputs and the rows on which every fp32 evaluation must round like it: the pixel is further than
+    max(1e-3 px, the fp32 error bound of that row) from a tie and from the border.  -> (dict, keep [N] bool)"""
+    p = project_f64(P, np.asarray(w2c, np.float64)[:3, :4], K, H, W, flip)
+    with np.errstate(invalid="ignore"):
+        keep = pixel_margin(p["px"], p["py"], H, W) > np.maximum(1e-3, p["err"])
+    return p, keep
+
+
+# coordinate scales of the encoding range (DESIGN.md 7a: sample positions up to 4094 are in range) and what goes with every scale
+EMBED_SCALES = (1e-3, 1.0, 64.0, 1024.0, 4094.0, 1e5)
+
+
+def embed_envelope_inputs(scale, L, n=4096, seed=11):
+    """[n + edge rows, 3] fp32: uniform in [-scale, scale], plus +-0, subnormals, and the fp32 neighbours of multiples of
+    pi/2 * 2^-l (l < L) up to the scale, where sin or cos of the 2^l-fold argument crosses zero or peaks."""
+    rs = np.random.RandomState(seed + L)
+    x = rs.uniform(-scale, scale, size=(n, 3)).astype(np.float32)
+    edge = [0.0, -0.0, 1e-45, -1e-45, 1e-39, -1e-39, 1.1754942e-38]
+    for l in range(L):
+        kmax = max(1, int(scale / (np.pi / 2 * 2.0 ** -l)))
+        for k in sorted(set([1, 2, 3, 4, kmax // 2 + 1, kmax])):
+            v = np.float32(k * np.pi / 2 * 2.0 ** -l)
+            edge += [v, np.nextafter(v, np.float32(np.inf)), np.nextafter(v, np.float32(-np.inf)), -v]
+    e = np.array(edge + [0.0] * (-len(edge) % 3), np.float32).reshape(-1, 3)
+    return np.concatenate([x, e])
+
+
+def embed_f64(x, L):
+    """gamma(x) in float64 on the exact arguments: x * 2^l is exact in fp32 (and in float64)."""
+    x = np.asarray(x, np.float64)
+    parts = [x]
+    for l in range(L):
+        parts += [np.sin(x * 2.0 ** l), np.cos(x * 2.0 ** l)]
+    return np.concatenate(parts, -1)
