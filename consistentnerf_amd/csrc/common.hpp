@@ -103,3 +103,11 @@ int cn_make_geom(const cnerf_net* net, NetGeom* g);
 // per-workgroup partial sums, which the loss tails (loss.hip) index: ONE definition for both files.
 constexpr int CN_CLOSS_RAYS_PER_WG = 8;
 
+// The rules of a cnerf_lossform that hold at every entry point taking one (composite.hip's two launches, loss.hip's finish): both
+// forms in range, a softmask form with its temperature (with_depth: the depth form matters only next to a prior).
+static inline bool cn_lossform_ok(const cnerf_lossform* F, bool with_depth) {
+  return F && F->rgb_form >= CNERF_RGB_HARDMASK && F->rgb_form <= CNERF_RGB_SOFTMASK && F->depth_form >= CNERF_DEPTH_HARDMASK &&
+         F->depth_form <= CNERF_DEPTH_SOFTMASK && !(F->rgb_form == CNERF_RGB_SOFTMASK && !F->temp_rgb) &&
+         !(with_depth && F->depth_form == CNERF_DEPTH_SOFTMASK && !F->temp_depth);
+}
+

@@ -3,6 +3,7 @@
 // transmittance product is a lane-local sequential product + one wave scan, carried in fp64 and
 // rounded to fp32 per sample (the CPU reference's cumprod accumulates fp32 inputs in fp64).
 // HBM-bound: 24 B per ray-sample forward (raw 16 + z 4 in, weights 4 out), 40 B backward.
+#include "loss_terms.hpp"
 #include "raygen.hpp"
 
 namespace {
@@ -40,7 +41,8 @@ struct MseBwd {
 // tail (loss.hip closs_tail_k, the next launch on the stream: it also evaluates the monocular patch term, which needs whole
 // depth maps) sums them in index order, normalises by the (possibly global) counts and leaves the three seed weights the backward
 // uses.  Backward: seed_rgb = (w_m (rgb - target)) * g_rgb, seed_depth = (w_d (depth / far - prior / far)) * g_depth (+ the patch
-// term's d_depth * g_patch on the patch rays) — the operations of masked_loss_k / patch_depth_loss_k and autograd's `d * g`.
+// term's d_depth * g_patch on the patch rays) — the stand-alone kernels' own per-ray functions (loss_terms.hpp, which both files
+// include: that is what makes the two routes agree bit for bit) / patch_depth_loss_k's seeds and autograd's `d * g`.
 // The other live loss forms of V / VC (cnerf_lossform, include/cnerf.h): what the FORMS instantiations of the two kernels add.  The
 // new depth forms divide by far as ATen divides a tensor by a scalar, x * (1 / far): their literal lines run on ATen.
 struct LossForm {
@@ -49,20 +51,6 @@ struct LossForm {
   const float* temp_rgb = nullptr;
   const float* temp_depth = nullptr;
 };
-// weight and weighted powers of one residual under a soft form: softlp (V:58) w = |d|^coef + 1; softmask (V:50) w = exp(d^2 / t)
-__device__ __forceinline__ void soft_sums(bool softmask, float d, float coef, float t, double& sw, double& swd2, double& swd4) {
-  const float d2 = d * d;
-  const float w = softmask ? expf(d2 / t) : powf(fabsf(d), coef) + 1.f;
-  sw += (double)w;
-  swd2 += (double)(w * d2);
-  if (softmask) swd4 += (double)(w * (d2 * d2));
-}
-// d loss / d residual of the same, times inv = 1 / sum(w): soft_lp_k's / softmask_k's expression (loss.hip)
-__device__ __forceinline__ float soft_seed(bool softmask, float d, float coef, float t, float inv) {
-  if (softmask) return (expf((d * d) / t) * (2.f * d + 2.f * ((d * d) * d) / t)) * inv;
-  const float p = powf(fabsf(d), coef);
-  return (d * (coef * p + 2.f * (p + 1.f))) * inv;
-}
 
 struct ClossFwd {
   const float* tgt;      // [B,3]
@@ -231,9 +219,11 @@ __global__ __launch_bounds__(WV * 64) void composite_fwd_k(const float* __restri
   const int lane = threadIdx.x & 63;
   const int64_t b = (int64_t)blockIdx.x * WV + (threadIdx.x >> 6);
   float o4[4] = {0.f, 0.f, 0.f, 0.f};
-  if constexpr (FORMS) {
-    // the v6 masked-loss variant below with a form per kind of term: CNERF_LOSSFORM_SLOTS partials per workgroup (cnerf.h)
-    constexpr int NS = CNERF_LOSSFORM_SLOTS;
+  if (FORMS || cl.tgt != nullptr) {
+    // masked-loss variant: per-ray terms in lane 0 (loss_terms.hpp: the stand-alone kernels' own functions — fp32 terms, fp64 sums),
+    // NS partials per workgroup summed over its waves in wave order; no tickets (see ClossFwd).  FORMS: a form per kind of term,
+    // CNERF_LOSSFORM_SLOTS partials (cnerf.h)
+    constexpr int NS = FORMS ? CNERF_LOSSFORM_SLOTS : LT_MASKED_SLOTS;
     __shared__ double sq[WV][NS];
     double t[NS];
 #pragma unroll
@@ -241,43 +231,40 @@ __global__ __launch_bounds__(WV * 64) void composite_fwd_k(const float* __restri
     if (b < B) {
       composite_ray<C>(raw, ch, z, rays, rs, noise, b, S, white, rgb, disp, acc, depth, weights, cam, nullptr, o4);
       if (lane == 0) {
-        const LossForm& f = cl.form;
         const float m = cl.mask ? cl.mask[b] : 1.f;
-        if (m == 1.f) t[3] = 1.0;
-        if (m == 0.f) t[4] = 1.0;
-        if (f.rgb_form == CNERF_RGB_HARDMASK) {
-          float e = 0.f;
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const float d = o4[c] - cl.tgt[b * 3 + c];
-            e += d * d;
-          }
-          if (m == 1.f) t[0] = (double)e;
-          if (m == 0.f) t[1] = (double)e;
+        const float* const tg = cl.tgt + b * 3;
+        if constexpr (!FORMS) {
+          lt_accum_ray(t, m, lt_sq_err3(o4, tg));
+          if (cl.prior) lt_accum_depth(t, m, lt_depth_res(o4[3], cl.prior[b], cl.far));
         } else {
-          const bool sm = f.rgb_form == CNERF_RGB_SOFTMASK;
-          const float tr = sm ? f.temp_rgb[0] : 1.f;
-#pragma unroll
-          for (int c = 0; c < 3; ++c) soft_sums(sm, o4[c] - cl.tgt[b * 3 + c], f.lp_coef, tr, t[7], t[8], t[9]);
-        }
-        if (cl.prior) {
-          const float inv = 1.f / cl.far, p = cl.prior[b];
-          if (f.depth_form == CNERF_DEPTH_HARDMASK) {
-            const float d = o4[3] / cl.far - p / cl.far;
-            if (m == 1.f) t[2] = (double)(d * d);
-          } else if (f.depth_form == CNERF_DEPTH_HARDMASK_COEF) {
-            const float d = o4[3] * inv - p * inv;
-            if (m == 1.f) t[2] = (double)(d * d);
-            if (m == 0.f) t[5] = (double)(d * d);
-          } else if (f.depth_form == CNERF_DEPTH_NORM) {
-            const float d = o4[3] * inv - (m == 0.f ? 0.f : p) * inv;
-            t[2] = (double)(d * d);
-          } else if (f.depth_form == CNERF_DEPTH_PLAIN) {
-            const float d = o4[3] - (m == 0.f ? 0.f : p);
-            t[2] = (double)(d * d);
+          const LossForm& f = cl.form;
+          lt_accum_counts(t, m);
+          if (f.rgb_form == CNERF_RGB_HARDMASK) {
+            lt_accum_colour(t, m, lt_sq_err3(o4, tg));
           } else {
-            const bool sm = f.depth_form == CNERF_DEPTH_SOFTMASK;
-            soft_sums(sm, o4[3] * inv - p * inv, f.lp_coef, sm ? f.temp_depth[0] : 1.f, t[5], t[6], t[2]);
+            const bool sm = f.rgb_form == CNERF_RGB_SOFTMASK;
+            const float tr = sm ? f.temp_rgb[0] : 1.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) lt_soft_sums(sm, o4[c] - tg[c], f.lp_coef, tr, t[LT_C_W], t[LT_C_WD2], t[LT_C_WD4]);
+          }
+          if (cl.prior) {
+            const float inv = 1.f / cl.far, p = cl.prior[b];
+            if (f.depth_form == CNERF_DEPTH_HARDMASK) {
+              lt_accum_depth(t, m, lt_depth_res(o4[3], p, cl.far));
+            } else if (f.depth_form == CNERF_DEPTH_HARDMASK_COEF) {
+              const float d = lt_depth_res_form(o4[3], p, inv);
+              lt_accum_depth(t, m, d);
+              if (m == 0.f) t[LT_D_W] = (double)(d * d);
+            } else if (f.depth_form == CNERF_DEPTH_NORM) {
+              const float d = lt_depth_res_form(o4[3], m == 0.f ? 0.f : p, inv);
+              t[LT_SD] = (double)(d * d);
+            } else if (f.depth_form == CNERF_DEPTH_PLAIN) {
+              const float d = o4[3] - (m == 0.f ? 0.f : p);
+              t[LT_SD] = (double)(d * d);
+            } else {
+              const bool sm = f.depth_form == CNERF_DEPTH_SOFTMASK;
+              lt_soft_sums(sm, lt_depth_res_form(o4[3], p, inv), f.lp_coef, sm ? f.temp_depth[0] : 1.f, t[LT_D_W], t[LT_D_WD2], t[LT_SD]);
+            }
           }
         }
       }
@@ -288,41 +275,6 @@ __global__ __launch_bounds__(WV * 64) void composite_fwd_k(const float* __restri
     }
     __syncthreads();
     if (threadIdx.x < NS) {
-      double s = 0.0;
-      for (int w = 0; w < WV; ++w) s += sq[w][threadIdx.x];
-      cl.part[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = s;
-    }
-    return;
-  }
-  if (cl.tgt != nullptr) {
-    // masked-loss variant: per-ray terms in lane 0 (the arithmetic of masked_loss_k: e = d0^2 + d1^2 + d2^2 in fp32, sums in
-    // fp64), five partials per workgroup summed over its waves in wave order; no tickets (see ClossFwd)
-    __shared__ double sq[WV][5];
-    double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    if (b < B) {
-      composite_ray<C>(raw, ch, z, rays, rs, noise, b, S, white, rgb, disp, acc, depth, weights, cam, nullptr, o4);
-      if (lane == 0) {
-        const float m = cl.mask ? cl.mask[b] : 1.f;
-        float e = 0.f;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float d = o4[c] - cl.tgt[b * 3 + c];
-          e += d * d;
-        }
-        if (m == 1.f) { t[0] = (double)e; t[3] = 1.0; }
-        if (m == 0.f) { t[1] = (double)e; t[4] = 1.0; }
-        if (cl.prior && m == 1.f) {
-          const float d = o4[3] / cl.far - cl.prior[b] / cl.far;
-          t[2] = (double)(d * d);
-        }
-      }
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < 5; ++k) sq[threadIdx.x >> 6][k] = t[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
       double s = 0.0;
       for (int w = 0; w < WV; ++w) s += sq[w][threadIdx.x];
       cl.part[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = s;
@@ -425,48 +377,45 @@ __global__ __launch_bounds__(WAVES * 64) void composite_bwd_k(const float* __res
     const float g0 = cl.g ? cl.g[0] : 1.f;
     const float m = cl.mask ? cl.mask[b] : 1.f;
     const float* const st = cl.stats + ((cl.seg_row > 0 && b >= cl.seg_row) ? 4 : 0);
-    const float w = m == 1.f ? st[0] : (m == 0.f ? st[1] : 0.f);
+    const float w = lt_ray_w(m, st[0], st[1]);
     const float g_rgb_l = cl.rgb_w * g0;
     bool v6_rgb = true, v6_depth = true;
     if constexpr (FORMS) {
-      // the form's seeds: the operations of the literal lines' backward (mse_k / soft_lp_k / softmask_k's d_x, autograd's `d_x * g`,
-      // then the `* (1 / far)` of ATen's tensor / scalar), see LossForm
+      // the form's seeds: the operations of the literal lines' backward (mse_k's d_x / loss_terms.hpp's soft seeds, autograd's
+      // `d_x * g`, then the `* (1 / far)` of ATen's tensor / scalar), see LossForm
       const LossForm& f = cl.form;
       if (b == 0 && lane == 0 && cl.g_temp) { cl.g_temp[0] = cl.d_temp[0] * g0; cl.g_temp[1] = cl.d_temp[1] * g0; }
       if (f.rgb_form != CNERF_RGB_HARDMASK) {
         v6_rgb = false;
         const bool sm = f.rgb_form == CNERF_RGB_SOFTMASK;
         const float tr = sm ? f.temp_rgb[0] : 1.f;
-        gr += soft_seed(sm, cl.rgb[b * 3 + 0] - cl.tgt[b * 3 + 0], f.lp_coef, tr, st[4]) * g_rgb_l;
-        gg += soft_seed(sm, cl.rgb[b * 3 + 1] - cl.tgt[b * 3 + 1], f.lp_coef, tr, st[4]) * g_rgb_l;
-        gb += soft_seed(sm, cl.rgb[b * 3 + 2] - cl.tgt[b * 3 + 2], f.lp_coef, tr, st[4]) * g_rgb_l;
+        gr += lt_soft_seed(sm, cl.rgb[b * 3 + 0] - cl.tgt[b * 3 + 0], f.lp_coef, tr, st[4]) * g_rgb_l;
+        gg += lt_soft_seed(sm, cl.rgb[b * 3 + 1] - cl.tgt[b * 3 + 1], f.lp_coef, tr, st[4]) * g_rgb_l;
+        gb += lt_soft_seed(sm, cl.rgb[b * 3 + 2] - cl.tgt[b * 3 + 2], f.lp_coef, tr, st[4]) * g_rgb_l;
       }
       if (cl.prior && f.depth_form != CNERF_DEPTH_HARDMASK) {
         v6_depth = false;
         const float inv = 1.f / cl.far, p = cl.prior[b], g_d = cl.depth_w * g0;
         if (f.depth_form == CNERF_DEPTH_HARDMASK_COEF) {
-          const float x = cl.depth[b] * inv - p * inv;
+          const float x = lt_depth_res_form(cl.depth[b], p, inv);
           if (m == 1.f) gd += ((st[2] * x) * g_d) * inv;
           if (m == 0.f) gd += ((st[3] * x) * (g_d * f.coef)) * inv;
         } else if (f.depth_form == CNERF_DEPTH_NORM) {
-          gd += ((st[2] * (cl.depth[b] * inv - (m == 0.f ? 0.f : p) * inv)) * g_d) * inv;
+          gd += ((st[2] * lt_depth_res_form(cl.depth[b], m == 0.f ? 0.f : p, inv)) * g_d) * inv;
         } else if (f.depth_form == CNERF_DEPTH_PLAIN) {
           gd += (st[2] * (cl.depth[b] - (m == 0.f ? 0.f : p))) * g_d;
         } else {
           const bool sm = f.depth_form == CNERF_DEPTH_SOFTMASK;
-          gd += (soft_seed(sm, cl.depth[b] * inv - p * inv, f.lp_coef, sm ? f.temp_depth[0] : 1.f, st[2]) * g_d) * inv;
+          gd += (lt_soft_seed(sm, lt_depth_res_form(cl.depth[b], p, inv), f.lp_coef, sm ? f.temp_depth[0] : 1.f, st[2]) * g_d) * inv;
         }
       }
     }
     if (v6_rgb) {
-      gr += (w * (cl.rgb[b * 3 + 0] - cl.tgt[b * 3 + 0])) * g_rgb_l;
-      gg += (w * (cl.rgb[b * 3 + 1] - cl.tgt[b * 3 + 1])) * g_rgb_l;
-      gb += (w * (cl.rgb[b * 3 + 2] - cl.tgt[b * 3 + 2])) * g_rgb_l;
+      gr += lt_seed_colour(w, cl.rgb[b * 3 + 0], cl.tgt[b * 3 + 0]) * g_rgb_l;
+      gg += lt_seed_colour(w, cl.rgb[b * 3 + 1], cl.tgt[b * 3 + 1]) * g_rgb_l;
+      gb += lt_seed_colour(w, cl.rgb[b * 3 + 2], cl.tgt[b * 3 + 2]) * g_rgb_l;
     }
-    if (cl.prior && v6_depth) {
-      const float dd = m == 1.f ? st[2] * (cl.depth[b] / cl.far - cl.prior[b] / cl.far) : 0.f;
-      gd += dd * (cl.depth_w * g0);
-    }
+    if (cl.prior && v6_depth) gd += lt_seed_depth(m, st[2], cl.depth[b], cl.prior[b], cl.far) * (cl.depth_w * g0);
     if (cl.patch_d && b < cl.n_patch) gd += cl.patch_d[b] * (cl.patch_w * g0);
     if (cl.ssim_d) {   // loss -= ssim_w ssim_level: autograd's `d * ((-g) * ssim_w)`, zero past the patch rays (the padded gradient)
       const float gs = (-g0) * cl.ssim_w;
@@ -634,19 +583,15 @@ extern "C" int cnerf_composite_bwd_mse(const float* raw, int raw_ch, const float
 }
 
 // ---- compositing with ConsistentNeRF's masked rgb / depth losses folded in (V:1645-1865): see ClossFwd / ClossBwd above ----------
-extern "C" int64_t cnerf_closs_ws_floats(int64_t B) { return B <= 0 ? 0 : 10 * cn_div_up(B, MSE_WAVES); }
+extern "C" int64_t cnerf_closs_ws_floats(int64_t B) { return B <= 0 ? 0 : 2 * LT_MASKED_SLOTS * cn_div_up(B, MSE_WAVES); }
 
 namespace {
-// cnerf_lossform -> LossForm, or false: a form out of range, a softmask form without its temperature, a softlp form without its
-// exponent (with_depth: the depth form matters only next to a prior)
+// cnerf_lossform -> LossForm, or false: cn_lossform_ok's rules (common.hpp), and a softlp form without its exponent, which only
+// these launches raise to a power (with_depth: the depth form matters only next to a prior)
 bool make_form(const cnerf_lossform* F, bool with_depth, LossForm* f) {
-  if (!F || F->rgb_form < CNERF_RGB_HARDMASK || F->rgb_form > CNERF_RGB_SOFTMASK || F->depth_form < CNERF_DEPTH_HARDMASK ||
-      F->depth_form > CNERF_DEPTH_SOFTMASK)
-    return false;
+  if (!cn_lossform_ok(F, with_depth)) return false;
   const bool lp = F->rgb_form == CNERF_RGB_SOFTLP || (with_depth && F->depth_form == CNERF_DEPTH_SOFTLP);
-  if ((lp && !(F->lp_coef > 0.f)) || (F->rgb_form == CNERF_RGB_SOFTMASK && !F->temp_rgb) ||
-      (with_depth && F->depth_form == CNERF_DEPTH_SOFTMASK && !F->temp_depth))
-    return false;
+  if (lp && !(F->lp_coef > 0.f)) return false;
   f->rgb_form = F->rgb_form; f->depth_form = F->depth_form; f->lp_coef = F->lp_coef; f->temp_rgb = F->temp_rgb;
   f->temp_depth = F->temp_depth;
   return true;

@@ -2,6 +2,7 @@
 // vanilla MSE (R:769), forward value + gradient seeds for the compositing backward in one launch.
 // Replaces 4 boolean-index gathers (each a host sync) per level.  One workgroup, fixed reduction order.
 #include "common.hpp"
+#include "loss_terms.hpp"
 #include "ssim.hpp"
 
 namespace {
@@ -19,6 +20,28 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
   return s;
 }
 
+// ray i of a stand-alone masked-loss launch into the five partials / its gradient seeds: shared by the one-workgroup kernel and the
+// two stages of the multi-workgroup form below
+__device__ __forceinline__ void masked_accum(double* t, const float* __restrict__ rgb, const float* __restrict__ tgt,
+                                             const float* __restrict__ depth, const float* __restrict__ prior,
+                                             const float* __restrict__ mask, int64_t i, float far) {
+  const float m = mask ? mask[i] : 1.f;
+  lt_accum_ray(t, m, lt_sq_err3(rgb + 3 * i, tgt + 3 * i));
+  if (depth) lt_accum_depth(t, m, lt_depth_res(depth[i], prior[i], far));
+}
+__device__ __forceinline__ void masked_seeds(const LtNorm& nm, const float* __restrict__ rgb, const float* __restrict__ tgt,
+                                             const float* __restrict__ depth, const float* __restrict__ prior,
+                                             const float* __restrict__ mask, int64_t i, float far, float* __restrict__ d_rgb,
+                                             float* __restrict__ d_depth) {
+  const float m = mask ? mask[i] : 1.f;
+  const float w = lt_ray_w(m, nm.w1, nm.w0);
+  if (d_rgb) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d_rgb[3 * i + c] = lt_seed_colour(w, rgb[3 * i + c], tgt[3 * i + c]);
+  }
+  if (d_depth) d_depth[i] = depth ? lt_seed_depth(m, nm.wd, depth[i], prior[i], far) : 0.f;
+}
+
 __global__ __launch_bounds__(T) void masked_loss_k(const float* __restrict__ rgb, const float* __restrict__ tgt,
                                                    const float* __restrict__ depth, const float* __restrict__ prior,
                                                    const float* __restrict__ mask, int64_t B, float far, float coef,
@@ -26,47 +49,15 @@ __global__ __launch_bounds__(T) void masked_loss_k(const float* __restrict__ rgb
                                                    float* __restrict__ loss, float* __restrict__ d_rgb,
                                                    float* __restrict__ d_depth) {
   __shared__ double sh[T / 64];
-  // pass 1: counts and squared-error sums of the two sets (m==1, m==0; other values belong to neither)
-  double n1 = 0, n0 = 0, s1 = 0, s0 = 0, sd = 0;
-  for (int64_t i = threadIdx.x; i < B; i += T) {
-    const float m = mask ? mask[i] : 1.f;
-    const bool in1 = m == 1.f, in0 = m == 0.f;
-    float e = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float d = rgb[3 * i + c] - tgt[3 * i + c];
-      e += d * d;
-    }
-    if (in1) { n1 += 1.0; s1 += (double)e; }
-    if (in0) { n0 += 1.0; s0 += (double)e; }
-    if (depth && in1) {
-      const float d = depth[i] / far - prior[i] / far;
-      sd += (double)(d * d);
-    }
-  }
-  n1 = block_sum(n1, sh); n0 = block_sum(n0, sh);
-  s1 = block_sum(s1, sh); s0 = block_sum(s0, sh); sd = block_sum(sd, sh);
-  // global counts (e.g. all-reduced over ranks) override the local ones for the normalisation
-  const double N1 = counts ? (double)counts[0] : n1;
-  const double N0 = counts ? (double)counts[1] : n0;
-  if (threadIdx.x == 0) {
-    float l = (float)(s1 / (3.0 * N1));
-    if (N0 > 0) l += coef * (float)(s0 / (3.0 * N0));
-    loss[0] = l;
-    loss[1] = depth ? (float)(sd / N1) : 0.f;
-  }
-  const float w1 = g_scale * (float)(2.0 / (3.0 * N1));
-  const float w0 = N0 > 0 ? g_scale * coef * (float)(2.0 / (3.0 * N0)) : 0.f;
-  const float wd = g_scale * (float)(2.0 / N1) / far;
-  for (int64_t i = threadIdx.x; i < B; i += T) {
-    const float m = mask ? mask[i] : 1.f;
-    const float w = m == 1.f ? w1 : (m == 0.f ? w0 : 0.f);
-    if (d_rgb) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) d_rgb[3 * i + c] = w * (rgb[3 * i + c] - tgt[3 * i + c]);
-    }
-    if (d_depth) d_depth[i] = (depth && m == 1.f) ? wd * (depth[i] / far - prior[i] / far) : 0.f;
-  }
+  // pass 1: the five sums (loss_terms.hpp)
+  double t[LT_MASKED_SLOTS] = {0, 0, 0, 0, 0};
+  for (int64_t i = threadIdx.x; i < B; i += T) masked_accum(t, rgb, tgt, depth, prior, mask, i, far);
+  t[LT_N1] = block_sum(t[LT_N1], sh); t[LT_N0] = block_sum(t[LT_N0], sh);
+  t[LT_S1] = block_sum(t[LT_S1], sh); t[LT_S0] = block_sum(t[LT_S0], sh); t[LT_SD] = block_sum(t[LT_SD], sh);
+  const bool writes = threadIdx.x == 0;
+  const LtNorm nm = lt_normalise(t, counts, coef, far, depth != nullptr, g_scale, writes);
+  if (writes) { loss[0] = nm.img; loss[1] = nm.dep; }
+  for (int64_t i = threadIdx.x; i < B; i += T) masked_seeds(nm, rgb, tgt, depth, prior, mask, i, far, d_rgb, d_depth);
 }
 
 
@@ -176,7 +167,7 @@ __global__ void patch_depth_loss_k(const float* __restrict__ depth, const float*
 // ---- the loss tail of a ConsistentNeRF step whose masked losses rode in the compositing launches (composite.hip ClossFwd) -------
 // ONE workgroup: sums each level's five per-workgroup fp64 partials in index order (thread t takes entries t, t + T, ...; then the
 // fixed-order block sum — the value does not depend on the grid's scheduling), normalises with the local or the caller's (global,
-// sharded batch) counts exactly as masked_loss_k does, evaluates the monocular patch term of both levels (one wave per patch: waves
+// sharded batch) counts with the stand-alone kernels' own lt_normalise (loss_terms.hpp), evaluates the monocular patch term of both levels (one wave per patch: waves
 // [0, P) the last level, [P, 2P) the coarse one), assembles the step's loss in the reference's order of accumulation (V:1672-1865:
 // loss += w_rgb img_loss; loss += w_patch mono_mse; loss += w_depth depth_loss; then the same three of the coarse level) and leaves
 // the per-level seed weights (w1, w0, wd) for cnerf_composite_bwd_closs.
@@ -213,9 +204,53 @@ struct ClossTail {
   double B;                  // rays of the batch: the denominator of the norm / plain depth means without global counts
 };
 
+// VT:941-969 — the primary render's terms under `--ss_loss`, mask = the rays `[mask_bound][mask]` selects (cnerf_ss_ref_rays'
+// `sel`), each term behind its own random.randint(0, 1) coin:
+//   img_loss  = coin ? img2mse(rgb[sel], target[sel])      : img2mse(rgb, target)                       (:942)
+//   depth     = coin ? img2mse(depth[sel], prior[sel])      : 0                     (un-normalised: far = 1)   (:950-952)
+//   img_loss0 = coin ? img2mse(rgb0[sel], target[sel])      : img2mse(rgb, target)  (the FINE rgb: the reference's line :959)
+//   depth0    = coin ? img2mse(depth0[sel], prior[sel])     : 0                                          (:966-968)
+// accumulated in that order onto `loss` (loss += each), which is returned.  The fallback of :959 sends its gradient to the fine
+// level's colours.  fine / coarse = the five sums of the levels' primary rays (coarse = nullptr: one level); N1 / N1c = the
+// selected rays the fine / coarse means divide by, Nall = all primary rays; anysel = false: nothing selected, every term takes its
+// un-masked branch; the coarse level's seed weights go to stats[st_coarse ..].  Writes terms[1..6] and the primary seed weights.
+__device__ __forceinline__ float ss_primary_terms(const ClossTail& a, const double* fine, const double* coarse, double N1, double Nall,
+                                                  double N1c, bool anysel, int st_coarse, float loss) {
+  const double s1 = fine[LT_S1], s0 = fine[LT_S0];
+  const float plain = lt_mean3(s1 + s0, Nall);
+  const bool c0 = a.coin[0] && anysel, c2 = a.coin[2] && anysel;
+  const float wall = lt_seed_w3(Nall), wsel = anysel ? lt_seed_w3(N1) : 0.f;
+  const float il = c0 ? lt_mean3(s1, N1) : plain;
+  float w1 = c0 ? wsel : wall, w0 = c0 ? 0.f : wall;
+  loss = loss + il;
+  float dl = 0.f;
+  const bool dep = a.has_depth && a.coin[1] && anysel;
+  if (dep) { dl = lt_mean(fine[LT_SD], N1); loss = loss + dl; }
+  a.terms[1] = il; a.terms[2] = dl; a.terms[3] = 0.f;
+  a.stats[2] = dep ? lt_seed_w(N1) / a.far : 0.f;
+  a.stats[3] = 0.f;
+  a.terms[4] = a.terms[5] = a.terms[6] = 0.f;
+  if (coarse) {
+    const float il0 = c2 ? lt_mean3(coarse[LT_S1], N1c) : plain;
+    loss = loss + il0;
+    float dl0 = 0.f;
+    const bool dep0 = a.has_depth && a.coin[3] && anysel;
+    if (dep0) { dl0 = lt_mean(coarse[LT_SD], N1c); loss = loss + dl0; }
+    a.terms[4] = il0; a.terms[5] = dl0;
+    float* st = a.stats + st_coarse;
+    st[0] = c2 ? lt_seed_w3(N1c) : 0.f;
+    st[1] = 0.f;
+    st[2] = dep0 ? lt_seed_w(N1c) / a.far : 0.f;
+    st[3] = 0.f;
+    if (!c2) { w1 += wall; w0 += wall; }
+  }
+  a.stats[0] = w1; a.stats[1] = w0;
+  return loss;
+}
+
 template <bool FORMS>
 __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
-  constexpr int NS = FORMS ? CNERF_LOSSFORM_SLOTS : 5;
+  constexpr int NS = FORMS ? CNERF_LOSSFORM_SLOTS : LT_MASKED_SLOTS;
   __shared__ double sh[T / 64];
   __shared__ float pshare[2][8];
   __shared__ double tot[2][NS];
@@ -246,10 +281,10 @@ __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
     // The one-render form of the whole `--ss_loss` step (VT:899-969): rays [0, 8 nparts1) are the primary batch (mask = sel, prior =
     // depth_cas_s), rays from there on the second render's warped rays (mask = 1 on the live rows, 0 on the padding; target / prior =
     // the reference view's colours / depth prior at the snapped pixels).  Segment sums in index order, like the sums above.
-    __shared__ double seg[2][2][5];
+    __shared__ double seg[2][2][LT_MASKED_SLOTS];
     for (int lv = 0; lv < levels; ++lv)
       for (int sg = 0; sg < 2; ++sg)
-        for (int k = 0; k < 5; ++k) {
+        for (int k = 0; k < LT_MASKED_SLOTS; ++k) {
           const int lo = sg ? a.nparts1 : 0, hi = sg ? a.nparts : a.nparts1;
           double s = 0.0;
           for (int i = lo + (int)threadIdx.x; i < hi; i += T) s += a.part[lv][(int64_t)k * a.nparts + i];
@@ -259,8 +294,8 @@ __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
     __syncthreads();
     if (threadIdx.x != 0) return;
     // second render first, as the reference accumulates (VT:930-938): img2mse(rgb_ref, target_ref) [+ img2mse(depth_ref, prior_ref)]
-    // then the coarse level's two; then the primary render's four coin-gated terms (VT:941-969, see the ss == 1 branch below)
-    const double M = a.counts3 ? (double)a.counts3[2] : seg[0][1][3];
+    // then the coarse level's two; then the primary render's four coin-gated terms (VT:941-969, ss_primary_terms)
+    const double M = a.counts3 ? (double)a.counts3[2] : seg[0][1][LT_N1];
     float loss = 0.f;
     float ref_t[4] = {0.f, 0.f, 0.f, 0.f};
     // M == 0 (no point of the batch projects into the reference view; the reference's `while mask.sum() == 0` never ends there, and the
@@ -268,48 +303,21 @@ __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
     // the caller, and with no in-bounds ray `sel` is empty too: the primary terms below fall to their un-masked branch.
     const bool have2 = M > 0.0;
     for (int lv = 0; lv < levels; ++lv) {          // level 0 = the last (fine) level: its terms come first in the reference
-      const float il = have2 ? (float)(seg[lv][1][0] / (3.0 * M)) : 0.f;
+      const float il = have2 ? lt_mean3(seg[lv][1][LT_S1], M) : 0.f;
       loss = loss + il;
       ref_t[2 * lv] = il;
       float dl = 0.f;
-      if (a.has_depth && have2) { dl = (float)(seg[lv][1][2] / M); loss = loss + dl; }
+      if (a.has_depth && have2) { dl = lt_mean(seg[lv][1][LT_SD], M); loss = loss + dl; }
       ref_t[2 * lv + 1] = dl;
       float* st = a.stats + 8 * lv + 4;            // segment 2 of this level: live rows weigh 2 / (3 M) and 2 / M, padding rows 0
-      st[0] = have2 ? (float)(2.0 / (3.0 * M)) : 0.f; st[1] = 0.f;
-      st[2] = (a.has_depth && have2) ? (float)(2.0 / M) / a.far : 0.f; st[3] = 0.f;
+      st[0] = have2 ? lt_seed_w3(M) : 0.f; st[1] = 0.f;
+      st[2] = (a.has_depth && have2) ? lt_seed_w(M) / a.far : 0.f; st[3] = 0.f;
     }
-    const double s1 = seg[0][0][0], s0 = seg[0][0][1];
-    const double N1 = a.counts3 ? (double)a.counts3[0] : seg[0][0][3];
-    const double Nall = a.counts3 ? (double)a.counts3[1] : seg[0][0][3] + seg[0][0][4];
-    const float plain = (float)((s1 + s0) / (3.0 * Nall));
-    const bool anysel = N1 > 0.0;                 // (false only with M == 0, see above: the coins then have nothing to select)
-    const bool c0 = a.coin[0] && anysel, c2 = a.coin[2] && anysel;
-    const float wall = (float)(2.0 / (3.0 * Nall)), wsel = anysel ? (float)(2.0 / (3.0 * N1)) : 0.f;
-    const float il = c0 ? (float)(s1 / (3.0 * N1)) : plain;
-    float w1 = c0 ? wsel : wall, w0 = c0 ? 0.f : wall;
-    loss = loss + il;
-    float dl = 0.f;
-    const bool dep = a.has_depth && a.coin[1] && anysel;
-    if (dep) { dl = (float)(seg[0][0][2] / N1); loss = loss + dl; }
-    a.terms[1] = il; a.terms[2] = dl; a.terms[3] = 0.f;
-    a.stats[2] = dep ? (float)(2.0 / N1) / a.far : 0.f;
-    a.stats[3] = 0.f;
-    a.terms[4] = a.terms[5] = a.terms[6] = 0.f;
-    if (levels == 2) {
-      const float il0 = c2 ? (float)(seg[1][0][0] / (3.0 * N1)) : plain;
-      loss = loss + il0;
-      float dl0 = 0.f;
-      const bool dep0 = a.has_depth && a.coin[3] && anysel;
-      if (dep0) { dl0 = (float)(seg[1][0][2] / N1); loss = loss + dl0; }
-      a.terms[4] = il0; a.terms[5] = dl0;
-      a.stats[8] = c2 ? (float)(2.0 / (3.0 * N1)) : 0.f;
-      a.stats[9] = 0.f;
-      a.stats[10] = dep0 ? (float)(2.0 / N1) / a.far : 0.f;
-      a.stats[11] = 0.f;
-      if (!c2) { w1 += wall; w0 += wall; }
-    }
-    a.stats[0] = w1; a.stats[1] = w0;
-    a.terms[0] = loss;
+    // the primary segment's own counts or the global ones; the coarse level's means divide by the same N1.  N1 == 0 only with
+    // M == 0 (see above): the coins then have nothing to select
+    const double N1 = a.counts3 ? (double)a.counts3[0] : seg[0][0][LT_N1];
+    const double Nall = a.counts3 ? (double)a.counts3[1] : seg[0][0][LT_N1] + seg[0][0][LT_N0];
+    a.terms[0] = ss_primary_terms(a, seg[0][0], levels == 2 ? seg[1][0] : nullptr, N1, Nall, N1, N1 > 0.0, 8, loss);
     a.terms[7] = (float)M;
     a.terms[8] = ref_t[0]; a.terms[9] = ref_t[1]; a.terms[10] = ref_t[2]; a.terms[11] = ref_t[3];
     return;
@@ -317,77 +325,43 @@ __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
   __syncthreads();
   if (threadIdx.x != 0) return;
   if (!FORMS && a.ss) {
-    // VT:941-969 — the primary render's terms under `--ss_loss`, mask = the rays `[mask_bound][mask]` selects (cnerf_ss_ref_rays'
-    // `sel`), each term behind its own random.randint(0, 1) coin:
-    //   img_loss  = coin ? img2mse(rgb[sel], target[sel])      : img2mse(rgb, target)                       (:942)
-    //   depth     = coin ? img2mse(depth[sel], prior[sel])      : 0                     (un-normalised: far = 1)   (:950-952)
-    //   img_loss0 = coin ? img2mse(rgb0[sel], target[sel])      : img2mse(rgb, target)  (the FINE rgb: the reference's line :959)
-    //   depth0    = coin ? img2mse(depth0[sel], prior[sel])     : 0                                          (:966-968)
-    // accumulated in that order (loss += each).  The fallback of :959 sends its gradient to the fine level's colours.
-    const double s1 = tot[0][0], s0 = tot[0][1], N1 = tot[0][3], Nall = tot[0][3] + tot[0][4];
-    const float plain = (float)((s1 + s0) / (3.0 * Nall));
-    const float wall = (float)(2.0 / (3.0 * Nall)), wsel = (float)(2.0 / (3.0 * N1));
-    const float il = a.coin[0] ? (float)(s1 / (3.0 * N1)) : plain;
-    float w1 = a.coin[0] ? wsel : wall, w0 = a.coin[0] ? 0.f : wall;
-    float loss = il, dl = 0.f;
-    const bool dep = a.has_depth && a.coin[1];
-    if (dep) { dl = (float)(tot[0][2] / N1); loss = loss + dl; }
-    a.terms[1] = il; a.terms[2] = dl; a.terms[3] = 0.f;
-    a.stats[2] = dep ? (float)(2.0 / N1) / a.far : 0.f;
-    a.stats[3] = 0.f;
-    a.terms[4] = a.terms[5] = a.terms[6] = 0.f;
-    if (levels == 2) {
-      const double N1c = tot[1][3];
-      const float il0 = a.coin[2] ? (float)(tot[1][0] / (3.0 * N1c)) : plain;
-      loss = loss + il0;
-      float dl0 = 0.f;
-      const bool dep0 = a.has_depth && a.coin[3];
-      if (dep0) { dl0 = (float)(tot[1][2] / N1c); loss = loss + dl0; }
-      a.terms[4] = il0; a.terms[5] = dl0;
-      a.stats[4] = a.coin[2] ? (float)(2.0 / (3.0 * N1c)) : 0.f;
-      a.stats[5] = 0.f;
-      a.stats[6] = dep0 ? (float)(2.0 / N1c) / a.far : 0.f;
-      a.stats[7] = 0.f;
-      if (!a.coin[2]) { w1 += wall; w0 += wall; }
-    }
-    a.stats[0] = w1; a.stats[1] = w0;
-    a.terms[0] = loss;
+    // the primary terms alone (the second render has launches of its own): each level's own count of selected rays, and no guard
+    // for an empty selection
+    a.terms[0] = ss_primary_terms(a, tot[0], levels == 2 ? tot[1] : nullptr, tot[0][LT_N1], tot[0][LT_N1] + tot[0][LT_N0],
+                                  levels == 2 ? tot[1][LT_N1] : 0.0, true, 4, 0.f);
     a.terms[7] = 0.f;
     return;
   }
   float loss = 0.f;
   for (int lv = 0; lv < levels; ++lv) {
-    const double s1 = tot[lv][0], s0 = tot[lv][1], sd = tot[lv][2];
-    const double N1 = a.counts ? (double)a.counts[0] : tot[lv][3];
-    const double N0 = a.counts ? (double)a.counts[1] : tot[lv][4];
-    float il = (float)(s1 / (3.0 * N1));
-    if (N0 > 0) il += a.coef * (float)(s0 / (3.0 * N0));
-    float dl = a.has_depth ? (float)(sd / N1) : 0.f;
-    float wd = (float)(2.0 / N1) / a.far, wd0 = 0.f, inv_rgb = 0.f;
+    // the v6 terms and seed weights (g_scale = 1: the upstream gradient joins in the compositing backward); the forms override
+    const LtNorm nm = lt_normalise(tot[lv], a.counts, a.coef, a.far, a.has_depth != 0, 1.f, true);
+    const double sd = tot[lv][LT_SD], N1 = nm.N1, N0 = nm.N0;
+    float il = nm.img, dl = nm.dep;
+    float wd = nm.wd, wd0 = 0.f, inv_rgb = 0.f;
     if constexpr (FORMS) {
-      // L = N / Dn with N = sum(w d^2), Dn = sum(w) (detached in d, not in t); softmask: dL / dt = -(sum(w d^4) / Dn - L^2) / t^2
-      auto d_temp = [](double s4, double Dn, double N, double t) { const double L = N / Dn; return -(s4 / Dn - L * L) / (t * t); };
       float dt_rgb = 0.f, dt_depth = 0.f;
       if (a.rgb_form[lv] != CNERF_RGB_HARDMASK) {
-        const double Dn = tot[lv][7], N = tot[lv][8];
+        const double Dn = tot[lv][LT_C_W], N = tot[lv][LT_C_WD2];
         il = (float)(N / Dn);
         inv_rgb = (float)(1.0 / Dn);
-        if (a.rgb_form[lv] == CNERF_RGB_SOFTMASK) dt_rgb = a.rgb_w * (float)d_temp(tot[lv][9], Dn, N, (double)a.temp_rgb[lv][0]);
+        if (a.rgb_form[lv] == CNERF_RGB_SOFTMASK)
+          dt_rgb = a.rgb_w * (float)lt_softmask_dtemp(tot[lv][LT_C_WD4], Dn, N, (double)a.temp_rgb[lv][0]);
       }
       if (a.has_depth && a.depth_form[lv] != CNERF_DEPTH_HARDMASK) {
         const int df = a.depth_form[lv];
         if (df == CNERF_DEPTH_HARDMASK_COEF) {
-          if (N0 > 0) { dl += a.coef * (float)(tot[lv][5] / N0); wd0 = (float)(2.0 / N0); }
+          if (N0 > 0) { dl += a.coef * (float)(tot[lv][LT_D_W] / N0); wd0 = (float)(2.0 / N0); }
           wd = (float)(2.0 / N1);
         } else if (df == CNERF_DEPTH_NORM || df == CNERF_DEPTH_PLAIN) {
           const double Nall = a.counts ? (double)a.counts[0] + (double)a.counts[1] : a.B;
           dl = (float)(sd / Nall);
           wd = (float)(2.0 / Nall);
         } else {
-          const double Dn = tot[lv][5], N = tot[lv][6];
+          const double Dn = tot[lv][LT_D_W], N = tot[lv][LT_D_WD2];
           dl = (float)(N / Dn);
           wd = (float)(1.0 / Dn);
-          if (df == CNERF_DEPTH_SOFTMASK) dt_depth = a.depth_w * (float)d_temp(sd, Dn, N, (double)a.temp_depth[lv][0]);
+          if (df == CNERF_DEPTH_SOFTMASK) dt_depth = a.depth_w * (float)lt_softmask_dtemp(sd, Dn, N, (double)a.temp_depth[lv][0]);
         }
       }
       a.d_temp[2 * lv + 0] = dt_rgb; a.d_temp[2 * lv + 1] = dt_depth;
@@ -406,8 +380,8 @@ __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
     if (a.has_depth) loss = loss + a.depth_w * dl;
     a.terms[1 + 3 * lv] = il; a.terms[2 + 3 * lv] = dl; a.terms[3 + 3 * lv] = pl;
     float* st = a.stats + (FORMS ? 8 : 4) * lv;
-    st[0] = (float)(2.0 / (3.0 * N1));
-    st[1] = N0 > 0 ? a.coef * (float)(2.0 / (3.0 * N0)) : 0.f;
+    st[0] = nm.w1;
+    st[1] = nm.w0;
     st[2] = wd;
     st[3] = wd0;
     if constexpr (FORMS) { st[4] = inv_rgb; st[5] = st[6] = st[7] = 0.f; }
@@ -460,23 +434,15 @@ __global__ __launch_bounds__(T) void soft_lp_k(const float* __restrict__ x, cons
   __shared__ double sh[T / 64];
   __shared__ double tot[2];
   double num = 0, den = 0;
-  for (int64_t i = threadIdx.x; i < n; i += T) {
-    const float d = x[i] - y[i];
-    const float w = powf(fabsf(d), coef) + 1.f;
-    num += (double)(w * (d * d));
-    den += (double)w;
-  }
+  double unused = 0;
+  for (int64_t i = threadIdx.x; i < n; i += T) lt_soft_sums(false, x[i] - y[i], coef, 1.f, den, num, unused);
   num = block_sum(num, sh);
   den = block_sum(den, sh);
   if (threadIdx.x == 0) { tot[0] = num; tot[1] = den; loss[0] = (float)(num / den); }
   __syncthreads();
   if (!d_x) return;
   const float inv = (float)(1.0 / tot[1]);
-  for (int64_t i = threadIdx.x; i < n; i += T) {
-    const float d = x[i] - y[i];
-    const float p = powf(fabsf(d), coef);
-    d_x[i] = (d * (coef * p + 2.f * (p + 1.f))) * inv;
-  }
+  for (int64_t i = threadIdx.x; i < n; i += T) d_x[i] = lt_soft_seed(false, x[i] - y[i], coef, 1.f, inv);
 }
 }  // namespace
 
@@ -542,28 +508,13 @@ __global__ __launch_bounds__(T) void masked_part_k(const float* __restrict__ rgb
                                                    const float* __restrict__ mask, int64_t B, float far, double* __restrict__ part) {
   __shared__ double sh[T / 64];
   const int64_t lo = (int64_t)blockIdx.x * ML_CHUNK, hi = lo + ML_CHUNK < B ? lo + ML_CHUNK : B;
-  double n1 = 0, n0 = 0, s1 = 0, s0 = 0, sd = 0;
-  for (int64_t i = lo + threadIdx.x; i < hi; i += T) {
-    const float m = mask ? mask[i] : 1.f;
-    const bool in1 = m == 1.f, in0 = m == 0.f;
-    float e = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float d = rgb[3 * i + c] - tgt[3 * i + c];
-      e += d * d;
-    }
-    if (in1) { n1 += 1.0; s1 += (double)e; }
-    if (in0) { n0 += 1.0; s0 += (double)e; }
-    if (depth && in1) {
-      const float d = depth[i] / far - prior[i] / far;
-      sd += (double)(d * d);
-    }
-  }
-  n1 = block_sum(n1, sh); n0 = block_sum(n0, sh);
-  s1 = block_sum(s1, sh); s0 = block_sum(s0, sh); sd = block_sum(sd, sh);
+  double t[LT_MASKED_SLOTS] = {0, 0, 0, 0, 0};
+  for (int64_t i = lo + threadIdx.x; i < hi; i += T) masked_accum(t, rgb, tgt, depth, prior, mask, i, far);
+  t[LT_N1] = block_sum(t[LT_N1], sh); t[LT_N0] = block_sum(t[LT_N0], sh);
+  t[LT_S1] = block_sum(t[LT_S1], sh); t[LT_S0] = block_sum(t[LT_S0], sh); t[LT_SD] = block_sum(t[LT_SD], sh);
   if (threadIdx.x == 0) {
-    double* o = part + 5 * (int64_t)blockIdx.x;
-    o[0] = s1; o[1] = s0; o[2] = sd; o[3] = n1; o[4] = n0;
+    double* o = part + LT_MASKED_SLOTS * (int64_t)blockIdx.x;
+    for (int k = 0; k < LT_MASKED_SLOTS; ++k) o[k] = t[k];
   }
 }
 __global__ __launch_bounds__(T) void masked_fin_k(const float* __restrict__ rgb, const float* __restrict__ tgt,
@@ -571,34 +522,18 @@ __global__ __launch_bounds__(T) void masked_fin_k(const float* __restrict__ rgb,
                                                   const float* __restrict__ mask, int64_t B, float far, float coef,
                                                   const float* __restrict__ counts, float g_scale, const double* __restrict__ part,
                                                   float* __restrict__ loss, float* __restrict__ d_rgb, float* __restrict__ d_depth) {
-  double t[5] = {0, 0, 0, 0, 0};
+  double t[LT_MASKED_SLOTS] = {0, 0, 0, 0, 0};
   for (unsigned p = 0; p < gridDim.x; ++p)
-    for (int k = 0; k < 5; ++k) t[k] += part[5 * (int64_t)p + k];
-  const double N1 = counts ? (double)counts[0] : t[3];
-  const double N0 = counts ? (double)counts[1] : t[4];
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    float l = (float)(t[0] / (3.0 * N1));
-    if (N0 > 0) l += coef * (float)(t[1] / (3.0 * N0));
-    loss[0] = l;
-    loss[1] = depth ? (float)(t[2] / N1) : 0.f;
-  }
-  const float w1 = g_scale * (float)(2.0 / (3.0 * N1));
-  const float w0 = N0 > 0 ? g_scale * coef * (float)(2.0 / (3.0 * N0)) : 0.f;
-  const float wd = g_scale * (float)(2.0 / N1) / far;
+    for (int k = 0; k < LT_MASKED_SLOTS; ++k) t[k] += part[LT_MASKED_SLOTS * (int64_t)p + k];
+  const bool writes = blockIdx.x == 0 && threadIdx.x == 0;
+  const LtNorm nm = lt_normalise(t, counts, coef, far, depth != nullptr, g_scale, writes);
+  if (writes) { loss[0] = nm.img; loss[1] = nm.dep; }
   const int64_t lo = (int64_t)blockIdx.x * ML_CHUNK, hi = lo + ML_CHUNK < B ? lo + ML_CHUNK : B;
-  for (int64_t i = lo + threadIdx.x; i < hi; i += T) {
-    const float m = mask ? mask[i] : 1.f;
-    const float w = m == 1.f ? w1 : (m == 0.f ? w0 : 0.f);
-    if (d_rgb) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) d_rgb[3 * i + c] = w * (rgb[3 * i + c] - tgt[3 * i + c]);
-    }
-    if (d_depth) d_depth[i] = (depth && m == 1.f) ? wd * (depth[i] / far - prior[i] / far) : 0.f;
-  }
+  for (int64_t i = lo + threadIdx.x; i < hi; i += T) masked_seeds(nm, rgb, tgt, depth, prior, mask, i, far, d_rgb, d_depth);
 }
 }  // namespace
 
-extern "C" int64_t cnerf_loss_ws_floats(void) { return 2 * 5 * ML_MAX_PARTS; }
+extern "C" int64_t cnerf_loss_ws_floats(void) { return 2 * LT_MASKED_SLOTS * ML_MAX_PARTS; }
 
 extern "C" int cnerf_masked_loss(const float* rgb, const float* target, const float* depth, const float* prior,
                                  const float* mask, int64_t B, float far, float coef, const float* counts,
@@ -676,10 +611,7 @@ int closs_finish_impl(const cnerf_closs_sum* t, const int32_t* ss_coins, float* 
     if (ss_coins || seg_row != 0 || !fm->d_temp) return CNERF_E_ARG;
     for (int lv = 0; lv < (t->ws_coarse ? 2 : 1); ++lv) {
       const cnerf_lossform* F = fm->F[lv];
-      if (!F || F->rgb_form < CNERF_RGB_HARDMASK || F->rgb_form > CNERF_RGB_SOFTMASK || F->depth_form < CNERF_DEPTH_HARDMASK ||
-          F->depth_form > CNERF_DEPTH_SOFTMASK || (F->rgb_form == CNERF_RGB_SOFTMASK && !F->temp_rgb) ||
-          (t->has_depth && F->depth_form == CNERF_DEPTH_SOFTMASK && !F->temp_depth))
-        return CNERF_E_ARG;
+      if (!cn_lossform_ok(F, t->has_depth != 0)) return CNERF_E_ARG;
       const bool soft = F->rgb_form != CNERF_RGB_HARDMASK || (t->has_depth && F->depth_form >= CNERF_DEPTH_SOFTLP);
       if (soft && t->counts) return CNERF_E_ARG;
       a.rgb_form[lv] = F->rgb_form; a.depth_form[lv] = F->depth_form; a.temp_rgb[lv] = F->temp_rgb; a.temp_depth[lv] = F->temp_depth;
@@ -748,14 +680,7 @@ __global__ __launch_bounds__(T) void softmask_k(const float* __restrict__ x, con
   __shared__ double tot[1];
   const float t = temp[0];
   double num = 0, den = 0, s4 = 0;
-  for (int64_t i = threadIdx.x; i < n; i += T) {
-    const float d = x[i] - y[i];
-    const float d2 = d * d;
-    const float w = expf(d2 / t);
-    den += (double)w;
-    num += (double)(w * d2);
-    s4 += (double)(w * (d2 * d2));
-  }
+  for (int64_t i = threadIdx.x; i < n; i += T) lt_soft_sums(true, x[i] - y[i], 0.f, t, den, num, s4);
   num = block_sum(num, sh);
   den = block_sum(den, sh);
   s4 = block_sum(s4, sh);
@@ -763,15 +688,12 @@ __global__ __launch_bounds__(T) void softmask_k(const float* __restrict__ x, con
     const double L = num / den;
     tot[0] = den;
     loss[0] = (float)L;
-    if (d_temp) d_temp[0] = (float)(-(s4 / den - L * L) / ((double)t * (double)t));
+    if (d_temp) d_temp[0] = (float)lt_softmask_dtemp(s4, den, num, (double)t);
   }
   __syncthreads();
   if (!d_x) return;
   const float inv = (float)(1.0 / tot[0]);
-  for (int64_t i = threadIdx.x; i < n; i += T) {
-    const float d = x[i] - y[i];
-    d_x[i] = (expf((d * d) / t) * (2.f * d + 2.f * ((d * d) * d) / t)) * inv;
-  }
+  for (int64_t i = threadIdx.x; i < n; i += T) d_x[i] = lt_soft_seed(true, x[i] - y[i], 0.f, t, inv);
 }
 }  // namespace
 

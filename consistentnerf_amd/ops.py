@@ -2,7 +2,7 @@
 PyTorch-ROCm plumbing; every computation here is a HIP kernel of libcnerf_hip.so.  No fallbacks."""
 import ctypes as C
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -711,69 +711,58 @@ def composite_forward_closs(raw: Tensor, z: Tensor, rays: Tensor, noise: Optiona
     return rgb, disp, acc, weights, depth, ws
 
 
+class ClossFinish(NamedTuple):
+    """What the loss tail of a step leaves (closs_finish): None where the step has no such term."""
+    terms: Tensor                 # [8]; [10] with the SSIM term or a loss form; [12] with L.seg_row
+    stats: Tensor                 # per level 4 seed weights; 8 with L.seg_row ([2 segments][4]) or a loss form
+    patch_d: Optional[Tensor]     # [levels, P * n]
+    ssim_d: Optional[Tensor]      # [levels, ssim_P * 768]
+    d_temp: Optional[Tensor]      # [4] = per level (rgb_w dL_rgb / d temp_rgb, depth_w dL_depth / d temp_depth): loss forms only
+
+
 def closs_finish(L: ClossSpec, B: int, ws_last: Tensor, ws_coarse: Optional[Tensor], depth_last: Optional[Tensor],
-                 depth_coarse: Optional[Tensor], want_grad: bool = True):
-    """cnerf_closs_finish -> (terms[8], stats[8], patch_d[levels, P * n] | None); with L.seg_row (the one-render in-loop consistency
-    step, cnerf_closs_finish_ss2): terms[12], stats[16] = per level [2 segments][4]."""
+                 depth_coarse: Optional[Tensor], rgb_last: Optional[Tensor] = None, rgb_coarse: Optional[Tensor] = None,
+                 want_grad: bool = True) -> ClossFinish:
+    """The loss tail of a step whose masked losses rode in the compositing launches, through the entry point L asks for:
+    cnerf_lossform_finish (L.forms), cnerf_closs_finish_ssim (L.ssim_P > 0: V's patch SSIM term of every level, from the levels'
+    colour maps), cnerf_closs_finish_ss2 / _ss (L.ss_coins with / without L.seg_row: the in-loop consistency step as one render /
+    its primary terms), else cnerf_closs_finish."""
     dev = ws_last.device
-    terms, stats = torch.empty(12 if L.seg_row else 8, device=dev), torch.empty(16 if L.seg_row else 8, device=dev)
     levels = 2 if ws_coarse is not None else 1
+    extra = L.forms or L.ssim_P > 0
+    terms = torch.empty(12 if L.seg_row else 10 if extra else 8, device=dev)
+    stats = torch.empty(16 if (L.seg_row or L.forms) else 8, device=dev)
     patch_d = torch.empty(levels, L.P * L.n, device=dev) if (L.P > 0 and want_grad) else None
+    ssim_d = torch.empty(levels, L.ssim_P * PATCH_SSIM_RAYS * 3, device=dev) if (L.ssim_P > 0 and want_grad) else None
+    d_temp = torch.empty(4, device=dev) if L.forms else None
     a = lambda x: None if x is None else x.data_ptr()  # noqa: E731
     t = ClossTail(a(ws_last), a(ws_coarse), int(B), a(L.counts), L.coef, L.far, L.rgb_w, L.depth_w, L.patch_w,
                   int(L.prior is not None), a(depth_last) if L.P > 0 else None,
                   a(depth_coarse) if (L.P > 0 and levels == 2) else None, a(L.mono) if L.P > 0 else None, L.P, L.n)
-    if L.ss_coins is not None and L.seg_row:
+    if extra:
+        rgb_last, rgb_coarse = _chk(rgb_last, "rgb"), _chk(rgb_coarse, "rgb0") if levels == 2 else None
+    lib = _lib.load()
+    if L.forms:
+        f0, f1 = L.form_c(0), L.form_c(1)
+        _lib.check(lib.cnerf_lossform_finish(C.byref(t), C.byref(f0), C.byref(f1), int(L.ssim_P), float(L.ssim_w), _p(rgb_last),
+                                             _p(rgb_coarse), _p(L.target), _p(terms), _p(stats), _p(patch_d), _p(ssim_d), _p(d_temp),
+                                             _stream()), "cnerf_lossform_finish")
+    elif L.ssim_P > 0:
+        _lib.check(lib.cnerf_closs_finish_ssim(C.byref(t), int(L.ssim_P), float(L.ssim_w), _p(rgb_last), _p(rgb_coarse), _p(L.target),
+                                               _p(terms), _p(stats), _p(patch_d), _p(ssim_d), _stream()), "cnerf_closs_finish_ssim")
+    elif L.ss_coins is not None and L.seg_row:
         coins = (C.c_int32 * 4)(*L.ss_coins)
-        _lib.check(_lib.load().cnerf_closs_finish_ss2(C.byref(t), coins, int(L.seg_row), _p(L.counts3), _p(terms), _p(stats), _stream()),
+        _lib.check(lib.cnerf_closs_finish_ss2(C.byref(t), coins, int(L.seg_row), _p(L.counts3), _p(terms), _p(stats), _stream()),
                    "cnerf_closs_finish_ss2")
     elif L.ss_coins is not None:
         coins = (C.c_int32 * 4)(*L.ss_coins)
-        _lib.check(_lib.load().cnerf_closs_finish_ss(C.byref(t), coins, _p(terms), _p(stats), _stream()), "cnerf_closs_finish_ss")
+        _lib.check(lib.cnerf_closs_finish_ss(C.byref(t), coins, _p(terms), _p(stats), _stream()), "cnerf_closs_finish_ss")
     else:
-        _lib.check(_lib.load().cnerf_closs_finish(C.byref(t), _p(terms), _p(stats), _p(patch_d), _stream()), "cnerf_closs_finish")
-    return terms, stats, patch_d
+        _lib.check(lib.cnerf_closs_finish(C.byref(t), _p(terms), _p(stats), _p(patch_d), _stream()), "cnerf_closs_finish")
+    return ClossFinish(terms, stats, patch_d, ssim_d, d_temp)
 
 
-def closs_finish_ssim(L: ClossSpec, B: int, ws_last: Tensor, ws_coarse: Optional[Tensor], depth_last: Optional[Tensor],
-                      depth_coarse: Optional[Tensor], rgb_last: Tensor, rgb_coarse: Optional[Tensor], want_grad: bool = True):
-    """cnerf_closs_finish_ssim (L.ssim_P > 0) -> (terms[10], stats[8], patch_d[levels, P * n] | None, ssim_d[levels, ssim_P * 768] |
-    None): closs_finish + V's patch SSIM term of every level."""
-    dev = ws_last.device
-    terms, stats = torch.empty(10, device=dev), torch.empty(8, device=dev)
-    levels = 2 if ws_coarse is not None else 1
-    patch_d = torch.empty(levels, L.P * L.n, device=dev) if (L.P > 0 and want_grad) else None
-    ssim_d = torch.empty(levels, L.ssim_P * PATCH_SSIM_RAYS * 3, device=dev) if want_grad else None
-    a = lambda x: None if x is None else x.data_ptr()  # noqa: E731
-    t = ClossTail(a(ws_last), a(ws_coarse), int(B), a(L.counts), L.coef, L.far, L.rgb_w, L.depth_w, L.patch_w,
-                  int(L.prior is not None), a(depth_last) if L.P > 0 else None,
-                  a(depth_coarse) if (L.P > 0 and levels == 2) else None, a(L.mono) if L.P > 0 else None, L.P, L.n)
-    rgb_last, rgb_coarse = _chk(rgb_last, "rgb"), _chk(rgb_coarse, "rgb0") if levels == 2 else None
-    _lib.check(_lib.load().cnerf_closs_finish_ssim(C.byref(t), int(L.ssim_P), float(L.ssim_w), _p(rgb_last), _p(rgb_coarse),
-                                                   _p(L.target), _p(terms), _p(stats), _p(patch_d), _p(ssim_d), _stream()),
-               "cnerf_closs_finish_ssim")
-    return terms, stats, patch_d, ssim_d
-
-
-def lossform_finish(L: ClossSpec, B: int, ws_last: Tensor, ws_coarse: Optional[Tensor], depth_last: Optional[Tensor],
-                    depth_coarse: Optional[Tensor], rgb_last: Tensor, rgb_coarse: Optional[Tensor], want_grad: bool = True):
-    """cnerf_lossform_finish (L.forms) -> (terms[10], stats[16] = per level 8, patch_d | None, ssim_d | None, d_temp[4] = per level
-    (rgb_w dL_rgb / d temp_rgb, depth_w dL_depth / d temp_depth))."""
-    dev = ws_last.device
-    terms, stats, d_temp = torch.empty(10, device=dev), torch.empty(16, device=dev), torch.empty(4, device=dev)
-    levels = 2 if ws_coarse is not None else 1
-    patch_d = torch.empty(levels, L.P * L.n, device=dev) if (L.P > 0 and want_grad) else None
-    ssim_d = torch.empty(levels, L.ssim_P * PATCH_SSIM_RAYS * 3, device=dev) if (L.ssim_P > 0 and want_grad) else None
-    a = lambda x: None if x is None else x.data_ptr()  # noqa: E731
-    t = ClossTail(a(ws_last), a(ws_coarse), int(B), a(L.counts), L.coef, L.far, L.rgb_w, L.depth_w, L.patch_w,
-                  int(L.prior is not None), a(depth_last) if L.P > 0 else None,
-                  a(depth_coarse) if (L.P > 0 and levels == 2) else None, a(L.mono) if L.P > 0 else None, L.P, L.n)
-    f0, f1 = L.form_c(0), L.form_c(1)
-    rgb_last, rgb_coarse = _chk(rgb_last, "rgb"), _chk(rgb_coarse, "rgb0") if levels == 2 else None
-    _lib.check(_lib.load().cnerf_lossform_finish(C.byref(t), C.byref(f0), C.byref(f1), int(L.ssim_P), float(L.ssim_w), _p(rgb_last),
-                                                 _p(rgb_coarse), _p(L.target), _p(terms), _p(stats), _p(patch_d), _p(ssim_d),
-                                                 _p(d_temp), _stream()), "cnerf_lossform_finish")
-    return terms, stats, patch_d, ssim_d, d_temp
+lossform_finish = closs_finish    # (the name callers of the loss-form launches use: with L.forms the call above IS cnerf_lossform_finish)
 
 
 def composite_backward_closs(raw, z, rays, noise, white_bkgd, L: ClossSpec, rgb, depth, stats4, g_loss, patch_d, ssim_d=None,

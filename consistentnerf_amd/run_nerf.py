@@ -447,17 +447,9 @@ class _RenderClossFn(torch.autograd.Function):
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
             raise ops.CnerfError("render_loss: gradients w.r.t. z_vals / rays are not implemented (only w.r.t. raw)")
         rgb, disp, acc, weights, depth, ws = ops.composite_forward_closs(raw, z, rays, noise, white, L)
-        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        d_temp = None
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or (L.forms and any(ctx.needs_input_grad[12:]))
         ctx.n_temps = len(temps)
-        if L.forms:
-            want = want or any(ctx.needs_input_grad[12:])
-            terms, stats, patch_d, ssim_d, d_temp = ops.lossform_finish(L, z.shape[0], ws, ws_c, depth, depth_c, rgb, rgb_c, want_grad=want)
-        elif L.ssim_P > 0:    # + V's patch SSIM term of every level (loss -= ssim_w ssim_level)
-            terms, stats, patch_d, ssim_d = ops.closs_finish_ssim(L, z.shape[0], ws, ws_c, depth, depth_c, rgb, rgb_c, want_grad=want)
-        else:
-            terms, stats, patch_d = ops.closs_finish(L, z.shape[0], ws, ws_c, depth, depth_c, want_grad=want)
-            ssim_d = None
+        terms, stats, patch_d, ssim_d, d_temp = ops.closs_finish(L, z.shape[0], ws, ws_c, depth, depth_c, rgb, rgb_c, want_grad=want)
         ctx.save_for_backward(raw, raw_c, z, z_c, rays, rgb, rgb_c, depth, depth_c, stats, patch_d, ssim_d, d_temp)
         ctx.noise, ctx.noise_c, ctx.white, ctx.L = noise, noise_c, white, L
         ctx.temp_shapes = [None if t is None else t.shape for t in temps]
@@ -472,21 +464,20 @@ class _RenderClossFn(torch.autograd.Function):
         g_temps = (None,) * ctx.n_temps
         if g_loss is not None:
             L = ctx.L
-            w = 8 if (L.seg_row or L.forms) else 4   # (two segments: per level [2][4] seed weights, cnerf_closs_finish_ss2; forms: [8])
+            w = stats.numel() // 2                   # the level's seed weights: 4, or 8 (two segments / a loss form), ops.ClossFinish
             want_t = L.forms and any(ctx.needs_input_grad[12:])
             g_temp = torch.empty(4, device=raw.device) if want_t else None   # written by the levels' backward launches
-            tk = lambda lv: {} if not L.forms else dict(level=lv, d_temp2=d_temp[2 * lv:2 * lv + 2] if want_t else None,  # noqa: E731
-                                                        g_temp2=g_temp[2 * lv:2 * lv + 2] if want_t else None)
+            pair = lambda x, lv: x[2 * lv:2 * lv + 2] if want_t else None  # noqa: E731   (the level's two temperatures)
             ran = [False, False]
             if ctx.needs_input_grad[0]:
                 d_raw = ops.composite_backward_closs(raw, z, rays, ctx.noise, ctx.white, L, rgb, depth, stats[0:w], g_loss,
                                                      None if patch_d is None else patch_d[0], None if ssim_d is None else ssim_d[0],
-                                                     **tk(0))
+                                                     0, pair(d_temp, 0), pair(g_temp, 0))
                 ran[0] = True
             if raw_c is not None and ctx.needs_input_grad[1]:
                 d_raw_c = ops.composite_backward_closs(raw_c, z_c, rays, ctx.noise_c, ctx.white, L, rgb_c, depth_c, stats[w:2 * w],
                                                        g_loss, None if patch_d is None else patch_d[1],
-                                                       None if ssim_d is None else ssim_d[1], **tk(1))
+                                                       None if ssim_d is None else ssim_d[1], 1, pair(d_temp, 1), pair(g_temp, 1))
                 ran[1] = True
             if want_t:
                 for lv in (0, 1):       # (a level whose raw takes no gradient had no launch to ride in)

@@ -246,6 +246,70 @@ def test_masked_loss_multi_workgroup_form(dev):
     assert torch.equal(d_rgb, r2) and torch.equal(loss, l2)
 
 
+@pytest.mark.parametrize("g_scale", [1.0, 0.3])
+@pytest.mark.parametrize("B,with_ws", [(13, False), (1029, False), (16389, False), (16389, True)])
+def test_masked_loss_seeds_are_the_written_formulas(dev, B, with_ws, g_scale):
+    """cnerf_masked_loss through the C entry point against its statement (csrc/loss_terms.hpp) evaluated in numpy float32: the
+    gradient seeds BIT FOR BIT — w1 = g_scale * fp32(2 / (3 N1)), w0 = g_scale * coef * fp32(2 / (3 N0)) (0 without an m == 0 ray),
+    wd = g_scale * fp32(2 / N1) / far, every double quotient rounded to fp32 first and the fp32 products left to right (g_scale = 0.3
+    is no power of two: a multiplication moved elsewhere shows in the last bit) — and the two loss values against float64 sums of the
+    fp32 per-ray terms at 2e-7 (fp64-association round-off, as test_masked_loss_multi_workgroup_form).  B = 13 / 1029: inside one
+    stride of the 1024-thread loop / its second trip; 16389 without a workspace: the one-workgroup kernel; with one: two parts, the
+    second of 5 rays (masked_part_k + masked_fin_k).  Masks: mixed, mixed with rays at 0.5 (in neither set: zero seeds, not counted),
+    all ones (N0 = 0), none; with and without depth; local counts or a larger global pair.  The same call twice: equal bits."""
+    from consistentnerf_amd import _lib
+    import ctypes as C
+    f32, f64 = np.float32, np.float64
+    far, coef = 7.0, 0.2
+    rs = np.random.RandomState(B)
+    rgb, tgt = rs.uniform(size=(B, 3)).astype(f32), rs.uniform(size=(B, 3)).astype(f32)
+    depth, prior = rs.uniform(0.5, far, size=B).astype(f32), rs.uniform(0.5, far, size=B).astype(f32)
+    mixed = (rs.uniform(size=B) < 0.6).astype(f32)
+    halves = mixed.copy()
+    halves[::5] = 0.5
+    lib = _lib.load()
+    ws = torch.empty(lib.cnerf_loss_ws_floats() // 2, device=dev, dtype=torch.float64) if with_ws else None
+    p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())  # noqa: E731
+    bits = lambda a: np.ascontiguousarray(a, dtype=f32).view(np.int32)  # noqa: E731
+    d = rgb - tgt
+    e = f32(0) + d[:, 0] * d[:, 0]
+    e = e + d[:, 1] * d[:, 1]
+    e = e + d[:, 2] * d[:, 2]
+    r = depth / f32(far) - prior / f32(far)
+    t_rgb, t_tgt, t_depth, t_prior = T(rgb, dev), T(tgt, dev), T(depth, dev), T(prior, dev)
+    for mname, mask in (("mixed", mixed), ("halves", halves), ("ones", np.ones(B, f32)), ("none", None)):
+        m = np.ones(B, f32) if mask is None else mask
+        in1, in0 = m == 1, m == 0
+        t_mask = None if mask is None else T(mask, dev)
+        for with_depth in (True, False):
+            for counts in (None, np.array([40000.0, 30000.0], f32)):
+                N1, N0 = (f64(in1.sum()), f64(in0.sum())) if counts is None else (f64(counts[0]), f64(counts[1]))
+                s1, s0, sd = e[in1].astype(f64).sum(), e[in0].astype(f64).sum(), (r * r)[in1].astype(f64).sum()
+                want_img = s1 / (3.0 * N1) + (f64(f32(coef)) * (s0 / (3.0 * N0)) if N0 > 0 else 0.0)
+                want_dep = sd / N1 if with_depth else 0.0
+                w1 = f32(g_scale) * f32(2.0 / (3.0 * N1))
+                w0 = f32(g_scale) * f32(coef) * f32(2.0 / (3.0 * N0)) if N0 > 0 else f32(0)
+                wd = f32(g_scale) * f32(2.0 / N1) / f32(far)
+                w = np.where(in1, w1, np.where(in0, w0, f32(0))).astype(f32)
+                want_rgb = w[:, None] * d
+                want_depth = np.where(in1, wd * r, f32(0)).astype(f32) if with_depth else np.zeros(B, f32)
+                t_counts = None if counts is None else T(counts, dev)
+                outs = []
+                for _ in range(2):
+                    loss, d_rgb, d_dep = torch.empty(2, device=dev), torch.empty(B, 3, device=dev), torch.empty(B, device=dev)
+                    _lib.check(lib.cnerf_masked_loss(p(t_rgb), p(t_tgt), p(t_depth if with_depth else None),
+                                                     p(t_prior if with_depth else None), p(t_mask), B, far, coef, p(t_counts), g_scale,
+                                                     p(loss), p(d_rgb), p(d_dep), p(ws), None), "cnerf_masked_loss")
+                    outs.append((loss.cpu().numpy(), d_rgb.cpu().numpy(), d_dep.cpu().numpy()))
+                (l, gr, gd), again = outs
+                tag = (mname, with_depth, counts is not None)
+                assert all(np.array_equal(bits(a), bits(b)) for a, b in zip(outs[0], again)), tag
+                assert np.array_equal(bits(gr), bits(want_rgb)), (tag, float(np.abs(gr - want_rgb).max()))
+                assert np.array_equal(bits(gd), bits(want_depth)), (tag, float(np.abs(gd - want_depth).max()))
+                assert abs(f64(l[0]) - want_img) <= 2e-7 * want_img, (tag, l[0], want_img)
+                assert abs(f64(l[1]) - want_dep) <= 2e-7 * want_dep, (tag, l[1], want_dep)
+
+
 # ------------------------------------------------------------------------------------------------ the step
 def test_c3_step_launches_and_graph(dev):
     """The C3 step through the one-call surface (sample_patch_rays -> render_loss -> backward -> FusedAdam with clip 0.1): the same
