@@ -105,6 +105,8 @@ SIGNATURES = {
     "cnerf_pack_weights_pair": (_i, [_NetP, _PtrsP, _vp, _NetP, _PtrsP, _vp, _vp]),
     "cnerf_coarse_z": (_i, [_vp, _i, _i64, _i, _vp, _vp, _i, _vp, _vp]),
     "cnerf_uniform_rng": (_i, [_RngP, _i64, _i, _vp, _vp]),
+    "cnerf_normal_rng": (_i, [_RngP, _i64, _i, _f, _vp, _vp]),
+    "cnerf_density_noise_rng": (_i, [_RngP, _i64, _i, _i, _f, _vp, _vp, _vp]),
     "cnerf_coarse_z_rng": (_i, [_vp, _i, _i64, _i, _vp, _RngP, _i, _vp, _vp]),
     "cnerf_resample_rng": (_i, [_vp, _vp, _RngP, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "cnerf_composite_mse_ws_floats": (_i64, [_i64]),

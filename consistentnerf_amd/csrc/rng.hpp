@@ -6,6 +6,16 @@
 // GLOBAL [total_rays, cols] draw, so a shard of a batch (row0 = its first global row) sees exactly the rows the unsharded call
 // sees, for free.  value = (x0 >> 8) * 2^-24: the 24-bit grid on [0, 1) of ATen's CPU torch.rand for float32.
 // oracle/philox.py restates this in numpy (pinned on the Random123 known-answer vectors); tests compare bit for bit.
+//
+// Next to it, a standard-normal stream for the density noise of raw2outputs (R:287-288) and the `--use_noise` label noise
+// (V:1633-1638): CnRngDev::normal(row, cols, col) — the same element index e = (row0 + row) * cols + col, the same key
+// seed ^ "cnerf_rn", the stream offset in the counter's high half exactly as above — takes words x0 and x1 of that ONE block:
+// u1 = ((x0 >> 8) + 1) * 2^-24 in (0, 1] (exact in fp32), u2 = (x1 >> 8) * 2^-24 in [0, 1), n = sqrtf(-2 logf(u1)) * cospif(2 u2)
+// (Box-Muller; the accurate OCML logf / sqrtf / cospif, no fast forms: the build has no fast-math and -ffp-contract=off).  One block
+// per element wastes the sine half of the pair ON PURPOSE: a value then depends on nothing but its own global index, so shards,
+// odd column counts and the two levels of a render_rays call need no pairing rule (at B = 4096, 64 + 192 samples the whole draw is
+// 2^20 blocks).  |n| <= sqrt(48 ln 2) = 5.7681 (u1 >= 2^-24), never inf or NaN.  A uniform and a normal stream on the same offset
+// share x0: callers give each stream an offset of its own (ops.rng_draw).  tests/_noise_ref.py restates it in float64.
 #pragma once
 #include "common.hpp"
 
@@ -21,7 +31,8 @@ static inline CnRngK cn_rng_arg(const cnerf_rng* r) {
   return k;
 }
 
-__device__ __forceinline__ uint32_t cn_philox_x0(uint64_t ctr_lo, uint64_t ctr_hi, uint64_t key) {
+// words 0 and 1 of the Philox4x32-10 block of (counter, key)
+__device__ __forceinline__ uint2 cn_philox_x01(uint64_t ctr_lo, uint64_t ctr_hi, uint64_t key) {
   uint32_t c0 = (uint32_t)ctr_lo, c1 = (uint32_t)(ctr_lo >> 32), c2 = (uint32_t)ctr_hi, c3 = (uint32_t)(ctr_hi >> 32);
   uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
 #pragma unroll
@@ -31,7 +42,11 @@ __device__ __forceinline__ uint32_t cn_philox_x0(uint64_t ctr_lo, uint64_t ctr_h
     c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
   }
-  return c0;
+  return make_uint2(c0, c1);
+}
+
+__device__ __forceinline__ uint32_t cn_philox_x0(uint64_t ctr_lo, uint64_t ctr_hi, uint64_t key) {
+  return cn_philox_x01(ctr_lo, ctr_hi, key).x;
 }
 
 struct CnRngDev {
@@ -46,5 +61,13 @@ struct CnRngDev {
   __device__ __forceinline__ float uniform(int64_t row, int cols, int col) const {
     const uint64_t e = (uint64_t)(row0 + row) * (uint64_t)cols + (uint64_t)col;
     return (float)(cn_philox_x0(e, off, key) >> 8) * 5.9604644775390625e-8f;
+  }
+  // stream `off + add` (cnerf_density_noise_rng: the second level's stream in the same launch)
+  __device__ __forceinline__ float normal(int64_t row, int cols, int col, uint64_t add = 0) const {
+    const uint64_t e = (uint64_t)(row0 + row) * (uint64_t)cols + (uint64_t)col;
+    const uint2 x = cn_philox_x01(e, off + add, key);
+    const float u1 = (float)((x.x >> 8) + 1u) * 5.9604644775390625e-8f;
+    const float u2 = (float)(x.y >> 8) * 5.9604644775390625e-8f;
+    return sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
   }
 };

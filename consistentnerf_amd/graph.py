@@ -7,14 +7,15 @@ recorded once and replayed with a single launch).  What changes from step to ste
     `FusedAdam.make_capturable()` moves them to device memory; `FusedAdam.advance()` uploads the step's 32 bytes from a ring of
     pinned blocks, stream-ordered ahead of every replay (the upload is NOT part of the recording: a recorded copy would read
     whatever the host has written by the time the GPU gets there);
-  * randomness: the in-kernel jitter / resampling streams (csrc/rng.hpp) read {seed, base offset} from device memory under a
-    recording (ops.RngCapture); `__call__` uploads the device generator's current pair (16 bytes, same pinned-ring discipline as
-    Adam's scalars) and advances the generator by what one replay consumes.  For a step whose only random numbers are these
-    in-kernel streams and which calls render_rays ONCE (the C2 / C4 step: raw_noise_std = 0) a replayed step sees exactly the
-    numbers the eager step in its place would have seen (tested).  Any torch.rand / torch.randn left in the step (raw_noise_std > 0)
-    is graph-safe by itself — torch advances its philox offsets per replay — and its stream stays disjoint from the in-kernel
-    ones, but the offsets interleave differently from eager stepping (the recording reserves all in-kernel offsets first, torch's
-    whole-graph increment after): valid, independent numbers, NOT the eager step's numbers.
+  * randomness: the in-kernel jitter / resampling / density-noise streams (csrc/rng.hpp) read {seed, base offset} from device
+    memory under a recording (ops.RngCapture); `__call__` uploads the device generator's current pair (16 bytes, same pinned-ring
+    discipline as Adam's scalars) and advances the generator by what one replay consumes.  For a step whose only random numbers
+    are these in-kernel streams — the jitter, the resampling positions and, with raw_noise_std > 0, the density noise of both
+    levels (ops.density_noise: offsets +2 / +3 of the same block) — a replayed step sees exactly the numbers the eager step in
+    its place would have seen (tested with the noise off and on).  A torch.rand / torch.randn left in the step (ops.IN_KERNEL_RNG
+    off, a caller-supplied generator) is graph-safe by itself — torch advances its philox offsets per replay — and its stream
+    stays disjoint from the in-kernel ones, but the offsets interleave differently from eager stepping (the recording reserves
+    all in-kernel offsets first, torch's whole-graph increment after): valid, independent numbers, NOT the eager step's numbers.
 
 Data-parallel steps (a `distributed.GradReducer` is passed): the gradient exchange sits between the backward and Adam.
   collective="split"   (default) two graphs around it: [render, loss, backward] -> eager all-reduce of the flat gradient on the

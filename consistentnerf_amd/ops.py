@@ -148,7 +148,8 @@ def _t_vals(n: int, device) -> Tensor:
 # sync) — so torch.manual_seed() / get_rng_state() / set_rng_state() govern these streams exactly like they govern torch.rand, and
 # torch.rand calls in between keep their own numbers.  Under hipGraph capture the pair lives in device memory instead
 # (RngCapture: graph.GraphedStep uploads {seed, offset} before every replay and advances the generator by what a replay consumes).
-RNG_STRIDE = 4          # (torch's generator wants offsets in multiples of 4)
+RNG_STRIDE = 4          # (torch's generator wants offsets in multiples of 4); one render_rays call: +0 jitter, +1 resampling
+                        # (uniform), +2 coarse density noise, +3 fine density noise (standard normal)
 IN_KERNEL_RNG = True    # False: render_rays draws t_rand / u with torch.rand and hands the tensors to the kernels (round-3 form)
 
 
@@ -174,7 +175,9 @@ class RngStream:
 
 
 def rng_draw(device, row0: int = 0) -> RngStream:
-    """Reserve RNG_STRIDE consecutive stream offsets (one render_rays call: +0 jitter, +1 resampling) from the device's generator."""
+    """Reserve RNG_STRIDE consecutive stream offsets from the device's generator.  One render_rays call: +0 jitter t_rand, +1
+    resampling u (uniform streams), +2 density noise of the coarse level, +3 density noise of the fine level (normal streams);
+    stand-alone raw2outputs: +2; run_nerf_view.add_label_noise: +0 rgb, +1 depth, +2 rgb0, +3 depth0 (normal streams)."""
     cap = RngCapture.active
     if cap is not None:
         st = RngStream(0, cap.used, cap.state, row0)
@@ -194,6 +197,31 @@ def uniform_rng(rng: RngStream, rows: int, cols: int, device, offset_add: int = 
     r = rng.c(offset_add)
     _lib.check(_lib.load().cnerf_uniform_rng(C.byref(r), rows, cols, _p(out), _stream()), "cnerf_uniform_rng")
     return out
+
+
+def normal_rng(rng: RngStream, rows: int, cols: int, device, offset_add: int = 0, scale: float = 1.0,
+               row0: Optional[int] = None) -> Tensor:
+    """[rows, cols] = scale * the standard-normal stream `offset_add` of the block `rng` names (csrc/rng.hpp), rows
+    [row0, row0 + rows) of the global draw (`row0` None: the stream's own)."""
+    out = torch.empty(rows, cols, device=device, dtype=torch.float32)
+    if rows == 0:      # (an empty tensor has no storage to point at)
+        return out
+    r = rng.c(offset_add, row0)
+    _lib.check(_lib.load().cnerf_normal_rng(C.byref(r), rows, cols, float(scale), _p(out), _stream()), "cnerf_normal_rng")
+    return out
+
+
+def density_noise(rng: RngStream, B: int, Nc: int, S1: int, std: float, device):
+    """The density noise (R:287-288) of one render_rays call, one launch: (noise0 [B, Nc], noise1 [B, S1] or None when S1 == 0) =
+    std * the normal streams +2 and +3 of the block `rng` names."""
+    noise0 = torch.empty(B, Nc, device=device, dtype=torch.float32)
+    noise1 = torch.empty(B, S1, device=device, dtype=torch.float32) if S1 > 0 else None
+    if B == 0:
+        return noise0, noise1
+    r = rng.c(2)
+    _lib.check(_lib.load().cnerf_density_noise_rng(C.byref(r), B, Nc, S1, float(std), _p(noise0), _p(noise1), _stream()),
+               "cnerf_density_noise_rng")
+    return noise0, noise1
 
 
 def coarse_z(rays: Tensor, Nc: int, t_rand: Optional[Tensor], lindisp: bool, rng: Optional[RngStream] = None) -> Tensor:

@@ -577,8 +577,9 @@ def _jitter_and_u(rows, Nc, Nf, dev, global_rows):
 
 
 def _in_kernel_rng():
-    """The jitter / resampling streams are generated inside coarse_z_k / resample_k (ops.rng_draw) — unless switched off, or a
-    hipGraph is being recorded by something other than graph.GraphedStep (torch.rand is the graph-safe generator then)."""
+    """The jitter / resampling streams are generated inside coarse_z_k / resample_k and the density noise by normal_rng_k
+    (ops.rng_draw) — unless switched off, or a hipGraph is being recorded by something other than graph.GraphedStep (torch.rand /
+    torch.randn are the graph-safe generators then)."""
     return ops.IN_KERNEL_RNG and (ops.RngCapture.active is not None or not torch.cuda.is_current_stream_capturing())
 
 
@@ -586,7 +587,10 @@ def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=F
     """R:265-308 -> (rgb_map, disp_map, acc_map, weights, depth_map)."""
     B = z_vals.shape[0]
     rays = torch.cat([torch.zeros_like(rays_d), rays_d], -1).contiguous()
-    noise = _density_noise(raw.shape[:2], raw_noise_std, pytest, raw.device)
+    if raw_noise_std > 0. and not pytest and _in_kernel_rng():     # its own block of offsets, the coarse level's stream (+2)
+        noise = ops.density_noise(ops.rng_draw(raw.device), raw.shape[0], raw.shape[1], 0, raw_noise_std, raw.device)[0]
+    else:
+        noise = _density_noise(raw.shape[:2], raw_noise_std, pytest, raw.device)
     return _CompositeFn.apply(raw.contiguous(), z_vals.contiguous(), rays, noise, bool(white_bkgd))
 
 
@@ -611,6 +615,8 @@ def _pytest_rows(rows, cols, device, global_rows):
 
 
 def _density_noise(shape, raw_noise_std, pytest, device, global_rows=None):
+    """The host-side density noise: the reference's uniform stream in pytest mode, torch.randn when the in-kernel streams are
+    off (otherwise ops.density_noise draws both levels in one launch, render_rays)."""
     if not raw_noise_std > 0.:
         return None
     if pytest:   # R:290-294: uniform in pytest mode
@@ -758,7 +764,8 @@ def _render_camera(H, W, K, chunk, c2w, ndc, near, far, use_viewdirs, with_depth
     end = H * W if count is None else min(H * W, first0 + count)
     for first in range(first0, end, chunk):
         B = min(chunk, end - first)
-        t_rand = u = None
+        t_rand = u = rng = None
+        ik_noise = std > 0. and not pytest and _in_kernel_rng()
         if perturb > 0.:
             if pytest:
                 t_rand = pytest_uniform((B, Nc), dev)
@@ -769,10 +776,14 @@ def _render_camera(H, W, K, chunk, c2w, ndc, near, far, use_viewdirs, with_depth
                 u = ops.uniform_rng(rng, B, Nf, dev, 1) if Nf > 0 else None
             else:
                 t_rand, u = _jitter_and_u(B, Nc, Nf, dev, None)     # (the same draw as render_rays: bit-identical paths)
-        noise0 = _density_noise((B, Nc), std, pytest, dev)
+        if ik_noise:   # both levels from one launch, on the block of the jitter (render_rays does the same)
+            noise0, noise1 = ops.density_noise(rng if rng is not None else ops.rng_draw(dev), B, Nc, Nc + Nf if Nf > 0 else 0, std, dev)
+        else:
+            noise0 = _density_noise((B, Nc), std, pytest, dev)
         if u is None:
             u = sample_u(B, Nf, perturb == 0., pytest, dev) if Nf > 0 else None
-        noise1 = _density_noise((B, Nc + Nf), std, pytest, dev) if Nf > 0 else None
+        if not ik_noise:
+            noise1 = _density_noise((B, Nc + Nf), std, pytest, dev) if Nf > 0 else None
         if two_nets:
             _prepack_pair(net, fine)
         o = ops.render_forward_cam(net.spec(), _packed(net), fine.spec() if two_nets else None,
@@ -930,7 +941,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                 _with_depth=False, _debug=False, _global_rows=None, _target=None, _live=None):
     """R:311-421 (V:441-551 when _with_depth).  Returns the same dict (+ the sample depths when _debug).
     `_global_rows = (offset, total)`: `ray_batch` is rows [offset, offset + N_rays) of a global batch of `total` rays sharded over
-    ranks — the jitter / resampling / noise streams are drawn for the whole batch and sliced (_rows_of_global).
+    ranks — the in-kernel jitter / resampling / noise streams are indexed by the global row (a shard draws its own rows only); the
+    host-side streams (pytest, ops.IN_KERNEL_RNG off) are drawn for the whole batch and sliced (_rows_of_global).
     `_target` [N_rays, 3] (render_loss): the compositing launches also produce ret['loss'] = img2mse(rgb_map, _target)
     (+ img2mse(rgb0, _target) with two levels) through _RenderLossFn; the maps are then detached values.
     `_live` (device int32 [1]): `ray_batch` is padded to a fixed capacity, only its first _live[0] rows are real rays (the rest are
@@ -952,16 +964,21 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                 ret['depth0'] = e(0)
         return ret
     viewdirs = rays[:, -3:] if rays.shape[-1] > 8 else None
-    t_rand = u_drawn = rng = None
+    t_rand = u_drawn = rng = rng_noise = None
+    row0 = 0 if _global_rows is None else int(_global_rows[0])
     if perturb > 0.:
         if pytest:
             t_rand = _pytest_rows(N_rays, N_samples, dev, _global_rows)
         elif _in_kernel_rng():
             # no generator launch: both streams are generated where they are consumed, indexed by the GLOBAL row (a shard of a
             # batch sees the rows the unsharded call sees without drawing the whole batch's stream)
-            rng = ops.rng_draw(dev, 0 if _global_rows is None else int(_global_rows[0]))
+            rng = ops.rng_draw(dev, row0)
         else:
             t_rand, u_drawn = _jitter_and_u(N_rays, N_samples, N_importance, dev, _global_rows)
+    if raw_noise_std > 0. and not pytest and _in_kernel_rng():
+        # the density noise of both levels: one launch on the SAME block of offsets (+2, +3), so the call still advances the
+        # generator by RNG_STRIDE; without jitter the block is reserved for the noise alone
+        rng_noise = rng if rng is not None else ops.rng_draw(dev, row0)
     z_vals = ops.coarse_z(rays, N_samples, t_rand, lindisp, rng=rng)
     if N_importance > 0:
         _prepack_pair(network_fn, network_fine)
@@ -972,7 +989,12 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         # back to the fine rgb, its depth term is absent) — the coarse level's backward covers the second segment only
         skip_c = int(_target.seg_row)
     raw = network_query_fn(RayPoints(rays, z_vals, _live, skip_c), viewdirs, network_fn)
-    noise = _density_noise((N_rays, N_samples), raw_noise_std, pytest, dev, _global_rows)
+    noise_fine = None
+    if rng_noise is not None:
+        noise, noise_fine = ops.density_noise(rng_noise, N_rays, N_samples, N_samples + N_importance if N_importance > 0 else 0,
+                                              raw_noise_std, dev)
+    else:
+        noise = _density_noise((N_rays, N_samples), raw_noise_std, pytest, dev, _global_rows)
     loss = loss_c = terms = None
     if _target is None:
         rgb_map, disp_map, acc_map, weights, depth_map = _CompositeFn.apply(raw, z_vals, rays, noise, bool(white_bkgd))
@@ -1009,7 +1031,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         raw_coarse = raw
         raw = network_query_fn(RayPoints(rays, z_vals, _live), viewdirs, run_fn)
         _link_levels(raw_coarse, raw)
-        noise = _density_noise((N_rays, N_samples + N_importance), raw_noise_std, pytest, dev, _global_rows)
+        noise = noise_fine if rng_noise is not None else _density_noise((N_rays, N_samples + N_importance), raw_noise_std, pytest,
+                                                                        dev, _global_rows)
         if _target is None:
             rgb_map, disp_map, acc_map, weights, depth_map = _CompositeFn.apply(raw, z_vals, rays, noise, bool(white_bkgd))
         elif isinstance(_target, ops.ClossSpec):

@@ -300,17 +300,23 @@ class Temp_Scheduler:
         return self.curr_temp
 
 
-def add_label_noise(rgb, depth_pred, extras, std, far, generator=None):
+def add_label_noise(rgb, depth_pred, extras, std, far, generator=None, row0=0):
     """The `--use_noise` block (V:1633-1638): N(0, std) added to the rendered colours of both levels, far * N(0, std) to their depths,
-    before the losses.  Returns (rgb, depth_pred, extras) — `extras` is updated in place like the reference's dict.  The draws come
-    from the device generator (the reference draws on the CPU and copies: same distribution, another stream)."""
-    n = lambda t, s: torch.randn(t.shape, device=t.device, dtype=t.dtype, generator=generator) * s  # noqa: E731
-    rgb = rgb + n(rgb, std)
-    depth_pred = depth_pred + far * n(depth_pred, std)
+    before the losses.  Returns (rgb, depth_pred, extras) — `extras` is updated in place like the reference's dict.  The draws are
+    the in-kernel normal streams (csrc/rng.hpp) of ONE ops.rng_draw block — +0 rgb [B, 3], +1 depth [B], +2 rgb0, +3 depth0 — indexed
+    by the global row (`row0`: this call's first row of a sharded batch); with a caller-supplied `generator`, or the in-kernel
+    streams off, torch.randn on the device (the reference draws on the CPU and copies: same distribution, another stream)."""
+    if generator is None and _R._in_kernel_rng():
+        rng = ops.rng_draw(rgb.device, int(row0))
+        n = lambda t, s, k: ops.normal_rng(rng, t.shape[0], t.shape[1] if t.dim() > 1 else 1, t.device, k, s).view(t.shape).to(t.dtype)  # noqa: E731
+    else:
+        n = lambda t, s, k: torch.randn(t.shape, device=t.device, dtype=t.dtype, generator=generator) * s  # noqa: E731
+    rgb = rgb + n(rgb, std, 0)
+    depth_pred = depth_pred + far * n(depth_pred, std, 1)
     if 'rgb0' in extras:
-        extras['rgb0'] = extras['rgb0'] + n(extras['rgb0'], std)
+        extras['rgb0'] = extras['rgb0'] + n(extras['rgb0'], std, 2)
     if 'depth0' in extras:
-        extras['depth0'] = extras['depth0'] + far * n(extras['depth0'], std)
+        extras['depth0'] = extras['depth0'] + far * n(extras['depth0'], std, 3)
     return rgb, depth_pred, extras
 
 

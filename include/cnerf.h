@@ -27,6 +27,8 @@ extern "C" {
                                 * cnerf_composite_bwd_lossform) and the stand-alone cnerf_softmask_loss;  SSIM / MS-SSIM (the ssim section below: cnerf_ssim_fwd,
                                 * cnerf_ssim_bwd, cnerf_avg_pool2, cnerf_patch_ssim_loss and their workspace queries) and V's patch SSIM term
                                 * folded into the C3 step (cnerf_closs_finish_ssim, cnerf_composite_bwd_closs_ssim).
+                                * 6: + the standard-normal stream beside the uniform one: cnerf_normal_rng, and cnerf_density_noise_rng (the density
+                                * noise R:287-288 of both levels of a render_rays call as one launch); append-only.
                                 * 6: + the in-loop consistency step as ONE render whose row count lives on the device: cnerf_ss_batch (the combined
                                 * batch + its live-row count), cnerf_mlp_fwd_live / cnerf_mlp_bwd_live / cnerf_mlp_bwd_pair_live (launches of a fixed
                                 * capacity that stop at a device-side count), cnerf_closs_finish_ss2 (the two-segment loss tail); cnerf_closs gains
@@ -101,6 +103,12 @@ typedef struct cnerf_rng {
 } cnerf_rng;
 /* out[rows, cols] = the stream itself (what the two entry points below consume; for tests and for callers that want the tensor). */
 int cnerf_uniform_rng(const cnerf_rng* rng, int64_t rows, int cols, float* out, void* stream);
+/* The standard-normal stream next to it (same element index, key and offset convention; Box-Muller on words 0 and 1 of the element's
+ * ONE Philox block, csrc/rng.hpp; |value| <= 5.7681, never inf / NaN):  out[r, c] = scale * normal(row0 + r, c) of stream `offset`. */
+int cnerf_normal_rng(const cnerf_rng* rng, int64_t rows, int cols, float scale, float* out, void* stream);
+/* The density noise (R:287-288) of both levels of one render_rays call in ONE launch: noise0[B, Nc] = std * normal stream `offset`
+ * (cols = Nc), noise1[B, S1] = std * normal stream `offset + 1` (cols = S1).  noise1 == NULL or S1 == 0: one level only. */
+int cnerf_density_noise_rng(const cnerf_rng* rng, int64_t B, int Nc, int S1, float std, float* noise0, float* noise1, void* stream);
 /* cnerf_coarse_z with t_rand[b, i] = stream element (row0 + b, i) of an [*, Nc] stream. */
 int cnerf_coarse_z_rng(const float* rays, int ray_stride, int64_t B, int Nc, const float* t_vals, const cnerf_rng* rng,
                        int lindisp, float* z, void* stream);
