@@ -191,6 +191,22 @@ SIGNATURES = {
     "cnerf_adam_hyper": (_i, [_i, C.c_double, C.c_double, C.c_double, C.c_double, _f, _f, _vp]),
     "cnerf_adam_step_dev": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "cnerf_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _i, C.c_double, C.c_double, C.c_double, C.c_double, _f, _f, _vp]),
+    "cnerf_conv3x3_packed_floats": (_i64, [_i64, _i64, _i]),
+    "cnerf_conv3x3_pack": (_i, [_vp, _i64, _i64, _i, _vp, _vp]),
+    "cnerf_conv3x3_ws_floats": (_i64, [_i64, _i64, _i64, _i64, _i64]),
+    "cnerf_conv3x3_fwd": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i, _vp, _vp, _vp]),
+    "cnerf_conv3x3_dgrad": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "cnerf_maxpool2_fwd": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "cnerf_maxpool2_bwd": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "cnerf_lpips_head_ws_floats": (_i64, [_i64, _i64, _i64]),
+    "cnerf_lpips_head_fwd": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "cnerf_lpips_head_bwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "cnerf_lpips_packed_floats": (_i64, []),
+    "cnerf_lpips_pack": (_i, [_PtrsP, _vp, _vp]),
+    "cnerf_lpips_ws_floats": (_i64, [_i64, _i64, _i64, _i]),
+    "cnerf_lpips_act_offset": (_i64, [_i64, _i64, _i64, _i]),
+    "cnerf_lpips_fwd": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
+    "cnerf_lpips_bwd": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -106,6 +106,21 @@ def img2ssim(x, y, mask=None):
         return ssim(x, y, data_range=1), ms_ssim(x, y, data_range=1)
 
 
+def img2lpips(pred, gt, model, mask=None):
+    """V:2055-2059 (and, with mask, V:2072-2076) as one call: pred, gt [N, H, W, 3] images in [0, 1] (numpy arrays or tensors), mask
+    [N, H, W] or None, model = an lpips.LPIPS (consistentnerf_amd.lpips.LPIPS) -> the mean LPIPS over the images as a 0-d tensor:
+    (x - 0.5) * 2, NHWC -> NCHW, with a mask x * mask + (1 - mask) on all three channels, model(gt, pred).mean()."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+    t = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32)  # noqa: E731
+    gt, pred = (t(gt) - 0.5) * 2., (t(pred) - 0.5) * 2.
+    gt, pred = gt.permute([0, 3, 1, 2]), pred.permute([0, 3, 1, 2])
+    if mask is not None:
+        m = t(mask).unsqueeze(1).expand(-1, 3, -1, -1)
+        gt, pred = gt * m + (1 - m), pred * m + (1 - m)
+    with torch.no_grad():
+        return model(gt.contiguous(), pred.contiguous()).mean()
+
+
 def write_metrics(path, psnr, ssim, lpips):
     with open(path, 'w') as f:
         f.write(f'PSNR: {psnr}\n')

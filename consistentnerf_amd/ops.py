@@ -1178,6 +1178,155 @@ def patch_ssim_loss(rgb: Tensor, target: Tensor, P: int, want_grad: bool = True)
     return value, d
 
 
+# ---- LPIPS (csrc/lpips.hip) --------------------------------------------------------------------------------------------------------
+LPIPS_CHANNELS = ((3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256), (256, 512), (512, 512), (512, 512),
+                  (512, 512), (512, 512), (512, 512))          # (Cin, Cout) of the 13 convolutions
+LPIPS_POOL_BEFORE = (2, 4, 7, 10)                              # a 2x2 max pool feeds these layers
+LPIPS_TAPS = (1, 3, 6, 9, 12)                                  # relu1_2, relu2_2, relu3_3, relu4_3, relu5_3
+
+
+def _nchw(t: Tensor, name: str, channels: Optional[int] = None) -> Tensor:
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+        raise CnerfError(f"{name} must be a float32 GPU tensor (consistentnerf_amd has no CPU path), got "
+                         f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '-')}")
+    if t.dim() != 4 or t.numel() == 0 or (channels is not None and t.shape[1] != channels):
+        raise CnerfError(f"{name} must be a non-empty [N, {channels or 'C'}, H, W] tensor, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def conv3x3_pack(w: Tensor, transposed: bool = False) -> Tensor:
+    """cnerf_conv3x3_pack: w [Cout, Cin, 3, 3] -> the MFMA panels of the forward (or, transposed, of the input gradient)."""
+    w = _nchw(w, "w")
+    Cout, Cin = w.shape[:2]
+    if tuple(w.shape[2:]) != (3, 3):
+        raise CnerfError(f"conv3x3_pack: w must be [Cout, Cin, 3, 3], got {tuple(w.shape)}")
+    lib = _lib.load()
+    panel = torch.empty(lib.cnerf_conv3x3_packed_floats(Cin, Cout, int(transposed)), device=w.device)
+    _lib.check(lib.cnerf_conv3x3_pack(_p(w), Cin, Cout, int(transposed), _p(panel), _stream()), "cnerf_conv3x3_pack")
+    return panel
+
+
+def _conv_ws(lib, N, Cin, Cout, H, W, device):
+    n = lib.cnerf_conv3x3_ws_floats(N, Cin, Cout, H, W)
+    return torch.empty(n, device=device) if n else None
+
+
+def conv3x3_forward(x: Tensor, panel: Tensor, bias: Optional[Tensor], Cout: int, relu: bool = True) -> Tensor:
+    """cnerf_conv3x3_fwd: conv2d(x, w, bias, padding=1) (then ReLU) with w packed by conv3x3_pack(w)."""
+    x = _nchw(x, "x")
+    N, Cin, H, W = x.shape
+    lib = _lib.load()
+    out = torch.empty(N, Cout, H, W, device=x.device)
+    ws = _conv_ws(lib, N, Cin, Cout, H, W, x.device)
+    _lib.check(lib.cnerf_conv3x3_fwd(_p(x), _p(panel), _p(_chk(bias, "bias")), N, Cin, Cout, H, W, int(relu), _p(out), _p(ws), _stream()),
+               "cnerf_conv3x3_fwd")
+    return out
+
+
+def conv3x3_dgrad(g: Tensor, panel_t: Tensor, Cin: int, gate: Optional[Tensor] = None) -> Tensor:
+    """cnerf_conv3x3_dgrad: the input gradient of conv2d(., w, padding=1) for the output gradient g [N, Cout, H, W], w packed by
+    conv3x3_pack(w, transposed=True); gate (the layer's post-ReLU output) zeroes g where gate <= 0."""
+    g = _nchw(g, "g")
+    N, Cout, H, W = g.shape
+    gate = None if gate is None else _nchw(gate, "gate", Cout)
+    lib = _lib.load()
+    d = torch.empty(N, Cin, H, W, device=g.device)
+    ws = _conv_ws(lib, N, Cin, Cout, H, W, g.device)
+    _lib.check(lib.cnerf_conv3x3_dgrad(_p(g), _p(gate), _p(panel_t), N, Cin, Cout, H, W, _p(d), _p(ws), _stream()), "cnerf_conv3x3_dgrad")
+    return d
+
+
+def maxpool2_forward(x: Tensor) -> Tensor:
+    """cnerf_maxpool2_fwd: max_pool2d(x, 2, 2)."""
+    x = _nchw(x, "x")
+    N, Cc, H, W = x.shape
+    out = torch.empty(N, Cc, H // 2, W // 2, device=x.device)
+    _lib.check(_lib.load().cnerf_maxpool2_fwd(_p(x), N, Cc, H, W, _p(out), _stream()), "cnerf_maxpool2_fwd")
+    return out
+
+
+def maxpool2_backward(x: Tensor, g: Tensor, add: Optional[Tensor] = None) -> Tensor:
+    """cnerf_maxpool2_bwd: the gradient of max_pool2d(x, 2, 2) w.r.t. x for the output gradient g (+ add)."""
+    x = _nchw(x, "x")
+    N, Cc, H, W = x.shape
+    g = _nchw(g, "g", Cc)
+    add = None if add is None else _nchw(add, "add", Cc)
+    d = torch.empty_like(x)
+    _lib.check(_lib.load().cnerf_maxpool2_bwd(_p(x), _p(g), _p(add), N, Cc, H, W, _p(d), _stream()), "cnerf_maxpool2_bwd")
+    return d
+
+
+def lpips_head_forward(F0: Tensor, F1: Tensor, lin: Tensor) -> Tensor:
+    """cnerf_lpips_head_fwd: one tap's value [N] for the feature sets F0, F1 [N, C, H, W] and the lin weight [C]."""
+    F0, F1 = _nchw(F0, "F0"), _nchw(F1, "F1")
+    N, Cc, H, W = F0.shape
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.cnerf_lpips_head_ws_floats(N, H, W) // 2), device=F0.device, dtype=torch.float64)
+    v = torch.empty(N, device=F0.device)
+    _lib.check(lib.cnerf_lpips_head_fwd(_p(F0), _p(F1), _p(_chk(lin.reshape(-1), "lin")), N, Cc, H, W, _p(v), _p(ws), _stream()),
+               "cnerf_lpips_head_fwd")
+    return v
+
+
+def lpips_head_backward(F0: Tensor, F1: Tensor, lin: Tensor, g: Tensor) -> Tensor:
+    """cnerf_lpips_head_bwd: the gradient of sum(g * value) w.r.t. F0."""
+    F0, F1 = _nchw(F0, "F0"), _nchw(F1, "F1")
+    N, Cc, H, W = F0.shape
+    d = torch.empty_like(F0)
+    _lib.check(_lib.load().cnerf_lpips_head_bwd(_p(F0), _p(F1), _p(_chk(lin.reshape(-1), "lin")), _p(_chk(g.reshape(N), "g")), N, Cc, H, W,
+                                                _p(d), _stream()), "cnerf_lpips_head_bwd")
+    return d
+
+
+def lpips_pack(convs: Sequence[Tensor], lins: Sequence[Tensor], shift: Tensor, scale: Tensor) -> Tensor:
+    """cnerf_lpips_pack: convs = weight, bias of the 13 convolutions in order (26 tensors), lins = the five [C] weights."""
+    ts = [_chk(t, "lpips weight") for t in list(convs) + [w.reshape(-1) for w in lins] + [shift.reshape(-1), scale.reshape(-1)]]
+    want = [s for ci, co in LPIPS_CHANNELS for s in ((co, ci, 3, 3), (co,))] + [(LPIPS_CHANNELS[l][1],) for l in LPIPS_TAPS] + [(3,), (3,)]
+    if [tuple(t.shape) for t in ts] != want:
+        raise CnerfError("lpips_pack: tensor shapes do not match VGG16 + lin + scaling layer")
+    lib = _lib.load()
+    packed = torch.empty(lib.cnerf_lpips_packed_floats(), device=ts[0].device)
+    _lib.check(lib.cnerf_lpips_pack(C.byref(_ptrs(ts)), _p(packed), _stream()), "cnerf_lpips_pack")
+    return packed
+
+
+def lpips_forward(X: Tensor, Y: Tensor, packed: Tensor, keep: bool = False, want_taps: bool = False, want_acts: bool = False):
+    """cnerf_lpips_fwd: (value [N], per-tap [5, N] | None, workspace | None, activations | None).  keep holds the activations in the
+    returned workspace for lpips_backward; want_acts (with keep) also returns the 13 post-ReLU activations [2 N, C, h, w] (X's images
+    first) as copies."""
+    X, Y = _nchw(X, "X", 3), _nchw(Y, "Y", 3)
+    if X.shape != Y.shape:
+        raise CnerfError(f"lpips: X and Y must have one shape, got {tuple(X.shape)} / {tuple(Y.shape)}")
+    N, _, H, W = X.shape
+    lib = _lib.load()
+    n = lib.cnerf_lpips_ws_floats(N, H, W, int(keep))
+    if n <= 0:
+        raise CnerfError(f"lpips: unsupported shape {tuple(X.shape)} (sides >= 16)")
+    ws = torch.empty(n, device=X.device)
+    value = torch.empty(N, device=X.device)
+    taps = torch.empty(5, N, device=X.device) if want_taps else None
+    _lib.check(lib.cnerf_lpips_fwd(_p(X), _p(Y), _p(packed), N, H, W, int(keep), _p(value), _p(taps), _p(ws), _stream()), "cnerf_lpips_fwd")
+    acts = None
+    if want_acts:
+        if not keep:
+            raise CnerfError("lpips_forward: want_acts needs keep=True")
+        acts, h, w = [], H, W
+        for l, (_, co) in enumerate(LPIPS_CHANNELS):
+            if l in LPIPS_POOL_BEFORE:
+                h, w = h // 2, w // 2
+            off = lib.cnerf_lpips_act_offset(N, H, W, l)
+            acts.append(ws[off:off + 2 * N * co * h * w].view(2 * N, co, h, w).clone())
+    return value, taps, (ws if keep else None), acts
+
+
+def lpips_backward(packed: Tensor, ws: Tensor, g: Tensor, shape) -> Tensor:
+    """cnerf_lpips_bwd: the gradient of sum(g * value) w.r.t. X after lpips_forward(X, Y, packed, keep=True) returned ws."""
+    N, _, H, W = shape
+    dX = torch.empty(N, 3, H, W, device=ws.device)
+    _lib.check(_lib.load().cnerf_lpips_bwd(_p(packed), _p(_chk(g.reshape(N), "g")), N, H, W, _p(dX), _p(ws), _stream()), "cnerf_lpips_bwd")
+    return dX
+
+
 def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float, beta1=0.9, beta2=0.999, eps=1e-8,
               clip: float = 0.0, grad_scale: float = 1.0):
     for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):

@@ -352,6 +352,22 @@ def patch_ssim(rgb, target_s, patch_num=4, patch_size=16):
     return _PatchSsimFn.apply(rgb, target_s.reshape(-1, 3), int(patch_num))
 
 
+def patch_lpips(rgb, target_s, model, n_patches=4, patch_size=16):
+    """`lpips_fine` / `lpips_coarse` of V:1699-1706 + V:1721: sum over the batch's first n_patches 16 x 16 patches of
+    lpips_fn((pred - 0.5) * 2, (gt - 0.5) * 2) on the patches as [1, 3, 16, 16] images, divided by V's literal 4 -> [1].  The patches
+    go through ONE batched forward of `model` (an lpips.LPIPS: consistentnerf_amd.lpips.LPIPS on the HIP kernels); differentiable in
+    rgb.  The caller adds 0.005 times element 0 (V:1728)."""
+    if int(patch_size) != 16:
+        raise ValueError(f"patch_lpips: the reference reshapes each patch to [1, 16, 16, 3] (patch_size 16), got {patch_size}")
+    n = int(n_patches) * 256
+    rgb, target_s = rgb.reshape(-1, 3), target_s.reshape(-1, 3)
+    if rgb.shape[0] < n or target_s.shape[0] < n:
+        raise ValueError(f"patch_lpips: need {n_patches} x 256 rays, got {rgb.shape[0]} / {target_s.shape[0]}")
+    pred = ((rgb[:n].reshape(-1, 16, 16, 3) - 0.5) * 2.).permute([0, 3, 1, 2]).contiguous()
+    gt = ((target_s[:n].reshape(-1, 16, 16, 3) - 0.5) * 2.).permute([0, 3, 1, 2]).contiguous()
+    return model(pred, gt).reshape(-1).sum().reshape(1) / 4
+
+
 # ----------------------------------------------------------------------------- the step's loss as one call
 _TERM_NAMES = ("loss", "img_loss", "depth_loss", "patch_loss", "img_loss0", "depth_loss0", "patch_loss0")
 
@@ -429,7 +445,8 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
     loss.backward() bit for bit.  Batches beyond one chunk, more than 8 patches, CPU tensors: the lines above, literally.
     ssim_w (0 = off, the call without the term; 0.005 = V): V's patch SSIM term on the first patch_num 16 x 16 patches of the
     batch (whether or not `mono` is given), folded into the same launches; terms gain `ssim` / `ssim0`, the level values.  LPIPS
-    stays with the caller: loss + 0.005 * lpips(...) on the returned maps, by autograd.
+    stays with the caller, on the returned maps: loss + 0.005 * patch_lpips(rgb, target_s, lpips_fn)[0] (V:1699-1728; the HIP network
+    of consistentnerf_amd.lpips, its own autograd node — not folded into these launches).
 
     rgb_form / depth_form: the other live branches of the reference's two drivers, folded the same way (same launches, no host
     synchronisation; the patch term, the SSIM term and the three weights compose with every form):

@@ -27,6 +27,7 @@ extern "C" {
                                 * cnerf_composite_bwd_lossform) and the stand-alone cnerf_softmask_loss;  SSIM / MS-SSIM (the ssim section below: cnerf_ssim_fwd,
                                 * cnerf_ssim_bwd, cnerf_avg_pool2, cnerf_patch_ssim_loss and their workspace queries) and V's patch SSIM term
                                 * folded into the C3 step (cnerf_closs_finish_ssim, cnerf_composite_bwd_closs_ssim).
+                                * 6: + LPIPS (the lpips section below: cnerf_lpips_*, and its pieces cnerf_conv3x3_*, cnerf_maxpool2_*); append-only.
                                 * 6: + the standard-normal stream beside the uniform one: cnerf_normal_rng, and cnerf_density_noise_rng (the density
                                 * noise R:287-288 of both levels of a render_rays call as one launch); append-only.
                                 * 6: + the in-loop consistency step as ONE render whose row count lives on the device: cnerf_ss_batch (the combined
@@ -649,6 +650,51 @@ int cnerf_avg_pool2(const float* X, int64_t N, int64_t C, int64_t H, int64_t W, 
  * [1, 16, 16, 3] NHWC view (C = ray / 16, H = ray % 16, W = colour; H filtered to 6, W unfiltered).  value[0] = (sum_p ssim_p) / 4
  * (V's literal 4), d_rgb [P 256, 3] (nullable) = d value / d rgb. */
 int cnerf_patch_ssim_loss(const float* rgb, const float* target, int P, float* value, float* d_rgb, void* stream);
+
+/* ---- LPIPS (the lpips package's LPIPS(net='vgg'), version 0.1: V:40, V:1699-1728, the metric V:2055-2087) --------------------- */
+/* The pieces first, each callable alone.  All tensors NCHW; results are identical bits call after call (no atomics).
+ * 3x3 / pad 1 / stride 1 convolution on the exact-fp32 MFMA.  Weights w [Cout, Cin, 3, 3] are packed once into panels:
+ * transposed = 0 for the forward, 1 for the input gradient (taps rotated).  cnerf_conv3x3_fwd: out [N, Cout, H, W] = conv(in) (+ bias
+ * [Cout], nullable) (ReLU if relu).  cnerf_conv3x3_dgrad: d_in [N, Cin, H, W] from g_out [N, Cout, H, W]; gate (nullable, the layer's
+ * stored output [N, Cout, H, W]) zeroes g_out where gate <= 0 (the ReLU backward).  workspace = cnerf_conv3x3_ws_floats() floats
+ * (0 on a large map: NULL is fine then); it holds the partial sums of the channel splits small maps are computed in. */
+int64_t cnerf_conv3x3_packed_floats(int64_t Cin, int64_t Cout, int transposed);
+int cnerf_conv3x3_pack(const float* w, int64_t Cin, int64_t Cout, int transposed, float* panel, void* stream);
+int64_t cnerf_conv3x3_ws_floats(int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W);
+int cnerf_conv3x3_fwd(const float* in, const float* panel, const float* bias, int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W,
+                      int relu, float* out, float* workspace, void* stream);
+int cnerf_conv3x3_dgrad(const float* g_out, const float* gate, const float* panel_t, int64_t N, int64_t Cin, int64_t Cout, int64_t H,
+                        int64_t W, float* d_in, float* workspace, void* stream);
+/* max_pool2d(X, 2, stride 2) (floor): out [N, C, H / 2, W / 2], the first maximum in row-major order under strict > (ATen's rule).
+ * cnerf_maxpool2_bwd: dX [N, C, H, W] = the gradient g_out routed to that element (+ add, nullable, may alias dX); a dropped odd
+ * row / column gets 0. */
+int cnerf_maxpool2_fwd(const float* X, int64_t N, int64_t C, int64_t H, int64_t W, float* out, void* stream);
+int cnerf_maxpool2_bwd(const float* X, const float* g_out, const float* add, int64_t N, int64_t C, int64_t H, int64_t W, float* dX,
+                       void* stream);
+/* One tap's head: value[n] = mean_{hw} sum_c lin[c] (F0 / (|F0|_c + 1e-10) - F1 / (|F1|_c + 1e-10))^2 over F0, F1 [N, C, H, W], sums
+ * in fp64; workspace = cnerf_lpips_head_ws_floats() floats, 8-byte aligned.  cnerf_lpips_head_bwd: dF0 = the gradient of
+ * sum_n g[n] value[n] w.r.t. F0; at a pixel where F0 is zero in every channel it is DEFINED as 0 (autograd: 0 * inf = NaN). */
+int64_t cnerf_lpips_head_ws_floats(int64_t N, int64_t H, int64_t W);
+int cnerf_lpips_head_fwd(const float* F0, const float* F1, const float* lin, int64_t N, int64_t C, int64_t H, int64_t W, float* value,
+                         float* workspace, void* stream);
+int cnerf_lpips_head_bwd(const float* F0, const float* F1, const float* lin, const float* g, int64_t N, int64_t C, int64_t H, int64_t W,
+                         float* dF0, void* stream);
+/* The network.  cnerf_lpips_pack: tensors->p = the 13 VGG16 convolutions' weight [Cout, Cin, 3, 3] and bias in order (p[2l], p[2l+1]),
+ * the five lin weights [C] (p[26..30]), the scaling layer's shift[3] and scale[3] (p[31], p[32]), all DEVICE pointers -> packed
+ * (cnerf_lpips_packed_floats() floats; forward and input-gradient panels of every layer).
+ * cnerf_lpips_fwd: X, Y [N, 3, H, W] in [-1, 1], H, W >= 16 -> value [N] = d(X, Y), per_tap [5, N] (nullable) = the five tap terms.
+ * keep = 1 holds every activation of the batch in the workspace for cnerf_lpips_bwd; keep = 0 walks the batch image by image through
+ * two buffers of one image pair (the values are the same bits either way).  workspace = cnerf_lpips_ws_floats(N, H, W, keep) floats,
+ * 16-byte aligned.  cnerf_lpips_act_offset: where (in floats) the kept workspace holds layer's (0..12) post-ReLU output
+ * [2 N, C, h, w], X's images first.  cnerf_lpips_bwd (after a keep = 1 forward on the same workspace): dX [N, 3, H, W] = the
+ * gradient of sum_n g[n] value[n] w.r.t. X; the gradient w.r.t. Y is that of the call with the roles swapped (d is symmetric). */
+int64_t cnerf_lpips_packed_floats(void);
+int cnerf_lpips_pack(const cnerf_ptrs* tensors, float* packed, void* stream);
+int64_t cnerf_lpips_ws_floats(int64_t N, int64_t H, int64_t W, int keep);
+int64_t cnerf_lpips_act_offset(int64_t N, int64_t H, int64_t W, int layer);
+int cnerf_lpips_fwd(const float* X, const float* Y, const float* packed, int64_t N, int64_t H, int64_t W, int keep, float* value,
+                    float* per_tap, float* workspace, void* stream);
+int cnerf_lpips_bwd(const float* packed, const float* g, int64_t N, int64_t H, int64_t W, float* dX, float* workspace, void* stream);
 
 /* ---- f-1: optimiser tail  (clip_grad_value_ V:1983, Adam R:210/780, lr decay R:784-788) --------- */
 /* In-place Adam over n contiguous floats; clip<=0 disables the value clip; step is 1-based.  The hyper-parameters are
