@@ -176,6 +176,11 @@ SIGNATURES = {
     "cnerf_closs_finish_ssim": (_i, [C.POINTER(ClossTail), _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cnerf_composite_bwd_closs_ssim": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i64, _i, _i, _ClossP, _vp, _vp, _vp, _vp, _f, _f, _f, _vp,
                                             _i64, _f, _vp, _i64, _vp, _vp]),
+    "cnerf_lpips_pack_patches": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    "cnerf_closs_finish_lpips": (_i, [C.POINTER(ClossTail), _i, _f, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cnerf_lpips_seeds": (_i, [_vp, _f, _i, _vp, _vp]),
+    "cnerf_composite_bwd_closs_lpips": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i64, _i, _i, _ClossP, _vp, _vp, _vp, _vp, _f, _f, _f, _vp,
+                                             _i64, _f, _vp, _i64, _vp, _i64, _vp, _vp]),
     "cnerf_lossform_ws_floats": (_i64, [_i64]),
     "cnerf_composite_fwd_lossform": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i64, _i, _i, _ClossP, _FormP, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cnerf_lossform_finish": (_i, [C.POINTER(ClossTail), _FormP, _FormP, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -75,6 +75,8 @@ struct ClossBwd {
   const float* ssim_d;   // [n_ssim * 3] d ssim_level / d rgb of this level (cnerf_closs_finish_ssim), or nullptr
   int64_t n_ssim;
   float ssim_w;
+  const float* lpips_d;  // [n_lpips / 256][3][16][16] cnerf_lpips_bwd's gradient w.r.t. this level's patch images, or nullptr
+  int64_t n_lpips;
   LossForm form;         // the FORMS kernel only: stats = the level's 8 floats of cnerf_lossform_finish
   const float* d_temp;   // [2] the level's (rgb_w dL_rgb / dt, depth_w dL_depth / dt), or nullptr
   float* g_temp;         // [2] <- d_temp * g
@@ -417,13 +419,25 @@ __global__ __launch_bounds__(WAVES * 64) void composite_bwd_k(const float* __res
     }
     if (cl.prior && v6_depth) gd += lt_seed_depth(m, st[2], cl.depth[b], cl.prior[b], cl.far) * (cl.depth_w * g0);
     if (cl.patch_d && b < cl.n_patch) gd += cl.patch_d[b] * (cl.patch_w * g0);
+    float sr = 0.f, sg = 0.f, sb = 0.f;
     if (cl.ssim_d) {   // loss -= ssim_w ssim_level: autograd's `d * ((-g) * ssim_w)`, zero past the patch rays (the padded gradient)
       const float gs = (-g0) * cl.ssim_w;
       const bool in = b < cl.n_ssim;
-      gr += in ? cl.ssim_d[b * 3 + 0] * gs : 0.f;
-      gg += in ? cl.ssim_d[b * 3 + 1] * gs : 0.f;
-      gb += in ? cl.ssim_d[b * 3 + 2] * gs : 0.f;
+      sr = in ? cl.ssim_d[b * 3 + 0] * gs : 0.f;
+      sg = in ? cl.ssim_d[b * 3 + 1] * gs : 0.f;
+      sb = in ? cl.ssim_d[b * 3 + 2] * gs : 0.f;
     }
+    if (!FORMS && cl.lpips_d) {   // (the loss forms take the term on the lines: run_nerf_view.render_loss)
+      // loss += lpips_w lpips_level: the `* 2` of (rgb - 0.5) * 2 on the level's slice of cnerf_lpips_bwd's NCHW gradient, read in place
+      // (ray p 256 + y 16 + x, colour c <- dX[p][c][y][x]; the seeds already carry g lpips_w / 4).  On the lines the engine runs the
+      // LPIPS chain before the SSIM node and the colour term's last: (lpips + ssim) + colour
+      const bool in = b < cl.n_lpips;
+      const float* const d = cl.lpips_d + (b >> 8) * 768 + (b & 255);
+      sr = (in ? d[0] * 2.f : 0.f) + sr;
+      sg = (in ? d[256] * 2.f : 0.f) + sg;
+      sb = (in ? d[512] * 2.f : 0.f) + sb;
+    }
+    if (cl.ssim_d || (!FORMS && cl.lpips_d)) { gr += sr; gg += sg; gb += sb; }
   }
   if (g_acc) ga = g_acc[b];
   if (white) ga -= (gr + gg + gb);
@@ -643,11 +657,13 @@ int composite_bwd_closs_impl(const float* raw, int raw_ch, const float* z, const
                              const float* stats, const float* g_loss, float rgb_w, float depth_w, float patch_w, const float* patch_d,
                              int64_t n_patch_rays, float ssim_w, const float* ssim_d, int64_t n_ssim_rays, float* d_raw, void* stream,
                              const cnerf_lossform* F = nullptr, float coef = 0.f, const float* d_temp = nullptr,
-                             float* g_temp = nullptr) {
+                             float* g_temp = nullptr, const float* lpips_d = nullptr, int64_t n_lpips_rays = 0) {
   if (!raw || !z || !rays || !L || !L->target || !rgb || !stats || !d_raw || B <= 0 || S <= 0 || raw_ch < 4 || ray_stride < 6 ||
-      (L->prior && (!depth || !(L->far > 0.f))) || n_patch_rays < 0 || n_patch_rays > B || n_ssim_rays < 0 || n_ssim_rays > B)
+      (L->prior && (!depth || !(L->far > 0.f))) || n_patch_rays < 0 || n_patch_rays > B || n_ssim_rays < 0 || n_ssim_rays > B ||
+      n_lpips_rays < 0 || n_lpips_rays > B || n_lpips_rays % 256 != 0)
     return CNERF_E_ARG;
   ClossBwd c;
+  c.lpips_d = n_lpips_rays > 0 ? lpips_d : nullptr; c.n_lpips = n_lpips_rays;
   c.d_temp = d_temp; c.g_temp = g_temp;
   if (FORMS && (L->seg_row != 0 || !make_form(F, L->prior != nullptr, &c.form) || (d_temp == nullptr) != (g_temp == nullptr)))
     return CNERF_E_ARG;
@@ -684,6 +700,18 @@ extern "C" int cnerf_composite_bwd_closs_ssim(const float* raw, int raw_ch, cons
   if (!ssim_d || n_ssim_rays <= 0) return CNERF_E_ARG;
   return composite_bwd_closs_impl(raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, L, rgb, depth, stats, g_loss, rgb_w,
                                   depth_w, patch_w, patch_d, n_patch_rays, ssim_w, ssim_d, n_ssim_rays, d_raw, stream);
+}
+
+extern "C" int cnerf_composite_bwd_closs_lpips(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
+                                               const float* noise, int64_t B, int S, int white_bkgd, const cnerf_closs* L, const float* rgb,
+                                               const float* depth, const float* stats, const float* g_loss, float rgb_w, float depth_w,
+                                               float patch_w, const float* patch_d, int64_t n_patch_rays, float ssim_w, const float* ssim_d,
+                                               int64_t n_ssim_rays, const float* lpips_dx, int64_t n_lpips_rays, float* d_raw,
+                                               void* stream) {
+  if (!lpips_dx || n_lpips_rays <= 0 || (n_ssim_rays > 0 && !ssim_d)) return CNERF_E_ARG;
+  return composite_bwd_closs_impl(raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, L, rgb, depth, stats, g_loss, rgb_w,
+                                  depth_w, patch_w, patch_d, n_patch_rays, ssim_w, ssim_d, n_ssim_rays, d_raw, stream, nullptr, 0.f,
+                                  nullptr, nullptr, lpips_dx, n_lpips_rays);
 }
 
 extern "C" int cnerf_composite_bwd_lossform(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,

@@ -196,6 +196,12 @@ struct ClossTail {
   const float* rgb[2];       // colour maps of the levels [B, 3]
   const float* tgt;          // [B, 3]
   float* ssim_d[2];          // [sP * 768] d ssim_level / d rgb per level, or nullptr
+  // V's patch LPIPS term (cnerf_closs_finish_lpips; lP = 0: none): lpips_v[level * lP + p] = the LPIPS value of patch p of the level
+  // (one batched cnerf_lpips_fwd over cnerf_lpips_pack_patches' images); terms[10 + level] = lpips_level = (sum_p v_p) / 4,
+  // loss += lpips_w lpips_level after the level's SSIM term (V:1726-1728)
+  int lP;
+  float lpips_w;
+  const float* lpips_v;
   // the FORMS tail only (cnerf_lossform_finish): a form per kind of term and level, CNERF_LOSSFORM_SLOTS partials per workgroup
   int rgb_form[2], depth_form[2];
   const float* temp_rgb[2];
@@ -377,6 +383,13 @@ __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
       loss = loss - a.ssim_w * sl;
       a.terms[8 + lv] = sl;
     }
+    if (!FORMS && a.lP > 0) {
+      float ll = 0.f;
+      for (int k = 0; k < a.lP; ++k) ll += a.lpips_v[lv * a.lP + k];
+      ll = ll / 4.f;
+      loss = loss + a.lpips_w * ll;
+      a.terms[10 + lv] = ll;
+    }
     if (a.has_depth) loss = loss + a.depth_w * dl;
     a.terms[1 + 3 * lv] = il; a.terms[2 + 3 * lv] = dl; a.terms[3 + 3 * lv] = pl;
     float* st = a.stats + (FORMS ? 8 : 4) * lv;
@@ -393,6 +406,10 @@ __global__ __launch_bounds__(T) void closs_tail_k(ClossTail a) {
   if (FORMS && a.sP == 0) a.terms[8] = a.terms[9] = 0.f;
   if (levels == 1) { a.terms[4] = a.terms[5] = a.terms[6] = 0.f; }
   if (a.sP > 0 && levels == 1) a.terms[9] = 0.f;
+  if (!FORMS && a.lP > 0) {
+    if (a.sP == 0) a.terms[8] = a.terms[9] = 0.f;
+    if (levels == 1) a.terms[11] = 0.f;
+  }
   a.terms[0] = loss;
   a.terms[7] = 0.f;
 }
@@ -574,6 +591,9 @@ struct ClossSsim {            // cnerf_closs_finish_ssim's additions (sP = 0: no
   const float* rgb_coarse = nullptr;
   const float* target = nullptr;
   float* ssim_d = nullptr;
+  int lP = 0;                 // cnerf_closs_finish_lpips' additions (lP = 0: none)
+  float lpips_w = 0.f;
+  const float* lpips_v = nullptr;
 };
 
 struct ClossForms {           // cnerf_lossform_finish's additions
@@ -605,6 +625,7 @@ int closs_finish_impl(const cnerf_closs_sum* t, const int32_t* ss_coins, float* 
   a.sP = sm.sP; a.ssim_w = sm.ssim_w; a.rgb[0] = sm.rgb_last; a.rgb[1] = t->ws_coarse ? sm.rgb_coarse : nullptr; a.tgt = sm.target;
   a.ssim_d[0] = sm.ssim_d;
   a.ssim_d[1] = (sm.ssim_d && t->ws_coarse) ? sm.ssim_d + (int64_t)sm.sP * CN_PATCH_SSIM_RAYS * 3 : nullptr;
+  a.lP = sm.lP; a.lpips_w = sm.lpips_w; a.lpips_v = sm.lpips_v;
   if (fm) {
     // (no in-loop consistency segments here; a softlp / softmask normaliser is a sum of weights, which no caller all-reduces: no
     // global counts with those forms)
@@ -653,6 +674,23 @@ extern "C" int cnerf_closs_finish_ssim(const cnerf_closs_sum* t, int ssim_P, flo
   ClossSsim sm;
   sm.sP = ssim_P; sm.ssim_w = ssim_w; sm.rgb_last = rgb_last; sm.rgb_coarse = rgb_coarse; sm.target = target; sm.ssim_d = ssim_d;
   return closs_finish_impl(t, nullptr, terms10, stats, patch_d, stream, 0, nullptr, sm);
+}
+
+extern "C" int cnerf_closs_finish_lpips(const cnerf_closs_sum* t, int ssim_P, float ssim_w, const float* rgb_last, const float* rgb_coarse,
+                                        const float* target, int lpips_P, float lpips_w, const float* lpips_v, float* terms12, float* stats,
+                                        float* patch_d, float* ssim_d, void* stream) {
+  // V's patch LPIPS term next to the SSIM term (ssim_P = 0: no SSIM term): lpips_v = the [levels lpips_P] per-image values of the
+  // one batched LPIPS forward over the levels' patches (cnerf_lpips_pack_patches' order: the last level's patches first)
+  if (!t || !terms12 || !lpips_v || lpips_P <= 0 || lpips_P > 8 || t->B <= 0 || (int64_t)lpips_P * CN_PATCH_SSIM_RAYS > t->B ||
+      ssim_P < 0 || ssim_P > 8)
+    return CNERF_E_ARG;
+  ClossSsim sm;
+  if (ssim_P > 0) {
+    if (!rgb_last || !target || (int64_t)ssim_P * CN_PATCH_SSIM_RAYS > t->B || (t->ws_coarse && !rgb_coarse)) return CNERF_E_ARG;
+    sm.sP = ssim_P; sm.ssim_w = ssim_w; sm.rgb_last = rgb_last; sm.rgb_coarse = rgb_coarse; sm.target = target; sm.ssim_d = ssim_d;
+  }
+  sm.lP = lpips_P; sm.lpips_w = lpips_w; sm.lpips_v = lpips_v;
+  return closs_finish_impl(t, nullptr, terms12, stats, patch_d, stream, 0, nullptr, sm);
 }
 
 extern "C" int cnerf_lossform_finish(const cnerf_closs_sum* t, const cnerf_lossform* F_last, const cnerf_lossform* F_coarse, int ssim_P,

@@ -257,6 +257,27 @@ __global__ __launch_bounds__(NT) void lp_unscale_k(const float* __restrict__ g, 
   dX[i] = g[i] / sc[3 + (int)((i / HW) % 3)];
 }
 
+// ---- V's patch LPIPS term inside the folded step (cnerf_lpips_pack_patches / cnerf_lpips_seeds) -------------------------------------
+// The patch rays of every level as ONE LPIPS batch: image lv * P + p = patch p of level lv (0 = the last level, 1 = coarse), read from
+// the ray-major [B, 3] maps as the reference's [1, 16, 16, 3] -> permute(0, 3, 1, 2) does: pred[img][c][y][x] = (rgb[p 256 + y 16 + x][c]
+// - 0.5) * 2 (V:1702-1705), gt the same of the target, repeated per level.  One thread per output element.
+__global__ __launch_bounds__(NT) void lp_pack_patches_k(const float* __restrict__ rgb0, const float* __restrict__ rgb1,
+                                                        const float* __restrict__ tgt, int P, int total, float* __restrict__ pred,
+                                                        float* __restrict__ gt) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i >= total) return;
+  const int img = i / 768, c = (i % 768) / 256, r = i % 256;
+  const int lv = img / P, p = img - lv * P;
+  const int64_t src = ((int64_t)p * 256 + r) * 3 + c;
+  pred[i] = ((lv ? rgb1 : rgb0)[src] - 0.5f) * 2.f;
+  gt[i] = (tgt[src] - 0.5f) * 2.f;
+}
+
+// seeds[i] = (g * lpips_w) * 0.25: autograd's own steps from the loss to the per-image LPIPS values (loss += lpips_w (sum_p v_p / 4))
+__global__ __launch_bounds__(64) void lp_seeds_k(const float* __restrict__ g, float lpips_w, int n, float* __restrict__ seeds) {
+  if ((int)threadIdx.x < n) seeds[threadIdx.x] = ((g ? g[0] : 1.f) * lpips_w) * 0.25f;
+}
+
 // ---- head ------------------------------------------------------------------------------------------------------------------------
 // One thread per pixel of pair n: F0 / F1 = [N, C, HW] feature sets; part[n * nblk + block] = the block's sum over its pixels of
 // sum_c lin[c] (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2, in fp64.
@@ -643,6 +664,24 @@ extern "C" int cnerf_lpips_bwd(const float* packed, const float* g, int64_t N, i
   }
   // gc = d / d (scaled input)
   hipLaunchKernelGGL(lp_unscale_k, dim3((unsigned)cn_div_up(N * 3 * H * W, NT)), dim3(NT), 0, st, gc, packed + k.sc, N * 3 * H * W, H * W, dX);
+  CN_CHECK_LAUNCH();
+  return CNERF_OK;
+}
+
+// ---- V's patch LPIPS term inside the folded step (run_nerf._RenderClossFn) ---------------------------------------------------------
+extern "C" int cnerf_lpips_pack_patches(const float* rgb_last, const float* rgb_coarse, const float* target, int P, int64_t B, float* pred,
+                                        float* gt, void* stream) {
+  if (!rgb_last || !target || !pred || !gt || P <= 0 || P > 8 || (int64_t)P * 256 > B) return CNERF_E_ARG;
+  const int total = (rgb_coarse ? 2 : 1) * P * 768;
+  hipLaunchKernelGGL(lp_pack_patches_k, dim3((unsigned)cn_div_up(total, NT)), dim3(NT), 0, cn_stream(stream), rgb_last, rgb_coarse, target,
+                     P, total, pred, gt);
+  CN_CHECK_LAUNCH();
+  return CNERF_OK;
+}
+
+extern "C" int cnerf_lpips_seeds(const float* g_loss, float lpips_w, int n, float* seeds, void* stream) {
+  if (!seeds || n <= 0 || n > 16) return CNERF_E_ARG;
+  hipLaunchKernelGGL(lp_seeds_k, dim3(1), dim3(64), 0, cn_stream(stream), g_loss, lpips_w, n, seeds);
   CN_CHECK_LAUNCH();
   return CNERF_OK;
 }

@@ -657,6 +657,9 @@ class ClossSpec:
     depth_form: int = 0                   # entry points
     lp_coef: float = 0.0                  # the exponent of a softlp form (args.Lp_coef)
     temps: Optional[tuple] = None         # 0-d device tensors (temp_rgb, temp_depth, temp_rgb coarse, temp_depth coarse) or None each
+    lpips_w: float = 0.0                  # V's patch LPIPS term (loss += lpips_w lpips_level per level; 0 = none) over the first lpips_P
+    lpips_P: int = 0                      # patches of 16 x 16 rays, through ONE batched pass of the packed network lpips_packed
+    lpips_packed: Optional[Tensor] = None  # (lpips_pack's blob: cnerf_lpips_pack_patches, cnerf_closs_finish_lpips); default forms only
 
     @property
     def forms(self) -> bool:
@@ -696,6 +699,10 @@ class ClossSpec:
             raise CnerfError(f"closs: the patch SSIM term needs ssim_P <= 8 patches of {PATCH_SSIM_RAYS} rays inside the batch and no "
                              f"ss_coins (ssim_P={sP}, B={B})")
         rf, df = int(self.rgb_form), int(self.depth_form) if pr is not None else 0
+        lP = int(self.lpips_P) if float(self.lpips_w) != 0.0 else 0
+        if lP > 0 and (lP > 8 or lP * PATCH_SSIM_RAYS > B or coins is not None or rf or df or self.lpips_packed is None):
+            raise CnerfError(f"closs: the patch LPIPS term needs lpips_P <= 8 patches of {PATCH_SSIM_RAYS} rays inside the batch, the packed "
+                             f"network, the default loss forms and no ss_coins (lpips_P={lP}, B={B})")
         temps = None
         if rf or df:
             if not (0 <= rf < len(RGB_FORMS) and 0 <= df < len(DEPTH_FORMS)):
@@ -710,7 +717,8 @@ class ClossSpec:
                 raise CnerfError("closs: a softmask form needs its temperature of both levels as device tensors")
         return ClossSpec(t, m, pr, float(self.far), float(self.coef), float(self.rgb_w), float(self.depth_w), float(self.patch_w),
                          mono, P, int(self.n), _chk(self.counts, "counts"), coins, seg, _chk(self.counts3, "counts3") if seg else None,
-                         float(self.ssim_w) if sP else 0.0, sP, rf, df, float(self.lp_coef), temps)
+                         float(self.ssim_w) if sP else 0.0, sP, rf, df, float(self.lp_coef), temps,
+                         float(self.lpips_w) if lP else 0.0, lP, _chk(self.lpips_packed, "lpips_packed") if lP else None)
 
 
 def composite_forward_closs(raw: Tensor, z: Tensor, rays: Tensor, noise: Optional[Tensor], white_bkgd: bool, L: ClossSpec,
@@ -741,24 +749,38 @@ def composite_forward_closs(raw: Tensor, z: Tensor, rays: Tensor, noise: Optiona
 
 class ClossFinish(NamedTuple):
     """What the loss tail of a step leaves (closs_finish): None where the step has no such term."""
-    terms: Tensor                 # [8]; [10] with the SSIM term or a loss form; [12] with L.seg_row
+    terms: Tensor                 # [8]; [10] with the SSIM term or a loss form; [12] with L.seg_row or the LPIPS term
     stats: Tensor                 # per level 4 seed weights; 8 with L.seg_row ([2 segments][4]) or a loss form
     patch_d: Optional[Tensor]     # [levels, P * n]
     ssim_d: Optional[Tensor]      # [levels, ssim_P * 768]
     d_temp: Optional[Tensor]      # [4] = per level (rgb_w dL_rgb / d temp_rgb, depth_w dL_depth / d temp_depth): loss forms only
 
 
+def lpips_step_forward(L: ClossSpec, B: int, rgb_last: Tensor, rgb_coarse: Optional[Tensor], want_grad: bool = True):
+    """The LPIPS forward of the folded step (L.lpips_P > 0) -> (value [levels * lpips_P], kept workspace | None): cnerf_lpips_pack_patches
+    writes the patch rays of every level as one batch (the last level's patches first), ONE lpips_forward over it; the values go to
+    closs_finish(lpips_v=), the workspace (want_grad) to lpips_step_backward."""
+    rgb_last, rgb_coarse = _chk(rgb_last, "rgb"), _chk(rgb_coarse, "rgb0")
+    n = (2 if rgb_coarse is not None else 1) * L.lpips_P
+    pred, gt = torch.empty(n, 3, 16, 16, device=rgb_last.device), torch.empty(n, 3, 16, 16, device=rgb_last.device)
+    _lib.check(_lib.load().cnerf_lpips_pack_patches(_p(rgb_last), _p(rgb_coarse), _p(L.target), int(L.lpips_P), int(B), _p(pred), _p(gt),
+                                                    _stream()), "cnerf_lpips_pack_patches")
+    value, _, ws, _ = lpips_forward(pred, gt, L.lpips_packed, keep=want_grad)
+    return value, ws
+
+
 def closs_finish(L: ClossSpec, B: int, ws_last: Tensor, ws_coarse: Optional[Tensor], depth_last: Optional[Tensor],
                  depth_coarse: Optional[Tensor], rgb_last: Optional[Tensor] = None, rgb_coarse: Optional[Tensor] = None,
-                 want_grad: bool = True) -> ClossFinish:
+                 want_grad: bool = True, lpips_v: Optional[Tensor] = None) -> ClossFinish:
     """The loss tail of a step whose masked losses rode in the compositing launches, through the entry point L asks for:
-    cnerf_lossform_finish (L.forms), cnerf_closs_finish_ssim (L.ssim_P > 0: V's patch SSIM term of every level, from the levels'
-    colour maps), cnerf_closs_finish_ss2 / _ss (L.ss_coins with / without L.seg_row: the in-loop consistency step as one render /
+    cnerf_lossform_finish (L.forms), cnerf_closs_finish_lpips (L.lpips_P > 0: V's patch LPIPS term of every level from lpips_v, the
+    per-image values of lpips_step_forward — with or without the SSIM term),
+    cnerf_closs_finish_ssim (L.ssim_P > 0: V's patch SSIM term of every level, from the levels' colour maps), cnerf_closs_finish_ss2 / _ss (L.ss_coins with / without L.seg_row: the in-loop consistency step as one render /
     its primary terms), else cnerf_closs_finish."""
     dev = ws_last.device
     levels = 2 if ws_coarse is not None else 1
-    extra = L.forms or L.ssim_P > 0
-    terms = torch.empty(12 if L.seg_row else 10 if extra else 8, device=dev)
+    extra = L.forms or L.ssim_P > 0 or L.lpips_P > 0
+    terms = torch.empty(12 if (L.seg_row or L.lpips_P > 0) else 10 if extra else 8, device=dev)
     stats = torch.empty(16 if (L.seg_row or L.forms) else 8, device=dev)
     patch_d = torch.empty(levels, L.P * L.n, device=dev) if (L.P > 0 and want_grad) else None
     ssim_d = torch.empty(levels, L.ssim_P * PATCH_SSIM_RAYS * 3, device=dev) if (L.ssim_P > 0 and want_grad) else None
@@ -770,7 +792,13 @@ def closs_finish(L: ClossSpec, B: int, ws_last: Tensor, ws_coarse: Optional[Tens
     if extra:
         rgb_last, rgb_coarse = _chk(rgb_last, "rgb"), _chk(rgb_coarse, "rgb0") if levels == 2 else None
     lib = _lib.load()
-    if L.forms:
+    if L.lpips_P > 0:
+        if lpips_v is None or lpips_v.numel() != levels * L.lpips_P:
+            raise CnerfError(f"closs_finish: the LPIPS term needs lpips_v [{levels * L.lpips_P}] (lpips_step_forward)")
+        _lib.check(lib.cnerf_closs_finish_lpips(C.byref(t), int(L.ssim_P), float(L.ssim_w), _p(rgb_last), _p(rgb_coarse), _p(L.target),
+                                                int(L.lpips_P), float(L.lpips_w), _p(_chk(lpips_v, "lpips_v")), _p(terms), _p(stats),
+                                                _p(patch_d), _p(ssim_d), _stream()), "cnerf_closs_finish_lpips")
+    elif L.forms:
         f0, f1 = L.form_c(0), L.form_c(1)
         _lib.check(lib.cnerf_lossform_finish(C.byref(t), C.byref(f0), C.byref(f1), int(L.ssim_P), float(L.ssim_w), _p(rgb_last),
                                              _p(rgb_coarse), _p(L.target), _p(terms), _p(stats), _p(patch_d), _p(ssim_d), _p(d_temp),
@@ -793,8 +821,18 @@ def closs_finish(L: ClossSpec, B: int, ws_last: Tensor, ws_coarse: Optional[Tens
 lossform_finish = closs_finish    # (the name callers of the loss-form launches use: with L.forms the call above IS cnerf_lossform_finish)
 
 
+def lpips_step_backward(L: ClossSpec, lpips_ws: Tensor, levels: int, g_loss: Tensor) -> Tensor:
+    """The LPIPS backward of the folded step -> dX [levels * lpips_P, 3, 16, 16]: cnerf_lpips_seeds forms the per-image seeds
+    (g_loss lpips_w) / 4 on the device, ONE lpips_backward over the kept workspace of lpips_step_forward."""
+    n = levels * L.lpips_P
+    seeds = torch.empty(n, device=lpips_ws.device)
+    _lib.check(_lib.load().cnerf_lpips_seeds(_p(_chk(g_loss.reshape(1), "g_loss")), float(L.lpips_w), n, _p(seeds), _stream()),
+               "cnerf_lpips_seeds")
+    return lpips_backward(L.lpips_packed, lpips_ws, seeds, (n, 3, 16, 16))
+
+
 def composite_backward_closs(raw, z, rays, noise, white_bkgd, L: ClossSpec, rgb, depth, stats4, g_loss, patch_d, ssim_d=None,
-                             level: int = 0, d_temp2=None, g_temp2=None) -> Tensor:
+                             level: int = 0, d_temp2=None, g_temp2=None, lpips_dx=None) -> Tensor:
     raw, z, rays, noise = _chk(raw, "raw"), _chk(z, "z"), _chk(rays, "rays"), _chk(noise, "noise")
     B, S = z.shape
     d_raw = torch.empty_like(raw)
@@ -806,6 +844,13 @@ def composite_backward_closs(raw, z, rays, noise, white_bkgd, L: ClossSpec, rgb,
             _p(depth), _p(stats4), _p(g_loss), L.rgb_w, L.depth_w, L.patch_w, L.coef, _p(patch_d),
             L.P * L.n if patch_d is not None else 0, float(L.ssim_w), _p(ssim_d), 0 if ssim_d is None else ssim_d.numel() // 3,
             _p(d_temp2), _p(g_temp2), _p(d_raw), _stream()), "cnerf_composite_bwd_lossform")
+        return d_raw
+    if lpips_dx is not None:    # + V's patch LPIPS seeds, the level's [lpips_P, 3, 16, 16] slice of the gradient (+ the SSIM seeds)
+        _lib.check(_lib.load().cnerf_composite_bwd_closs_lpips(
+            _p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S, int(white_bkgd), C.byref(c), _p(rgb), _p(depth),
+            _p(stats4), _p(g_loss), L.rgb_w, L.depth_w, L.patch_w, _p(patch_d), L.P * L.n if patch_d is not None else 0,
+            float(L.ssim_w), _p(ssim_d), 0 if ssim_d is None else ssim_d.numel() // 3, _p(_chk(lpips_dx, "lpips_dx")),
+            lpips_dx.shape[0] * PATCH_SSIM_RAYS, _p(d_raw), _stream()), "cnerf_composite_bwd_closs_lpips")
         return d_raw
     if ssim_d is not None:      # + V's patch SSIM seeds (cnerf_composite_bwd_closs_ssim)
         _lib.check(_lib.load().cnerf_composite_bwd_closs_ssim(

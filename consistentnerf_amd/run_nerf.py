@@ -440,7 +440,11 @@ class _RenderClossFn(torch.autograd.Function):
     the step: 2 masked-loss + 2 patch-term launches and the ~25 ATen kernels between them (adds, muls, index copies, fills).
     With a loss form (L.forms: the other live branches of V / VC, cnerf_lossform) the same three kinds of launch through the *_lossform
     entry points; `temps` = L.temps as autograd inputs: the softmask temperatures (temp_rgb, temp_depth, coarse temp_rgb, coarse
-    temp_depth; None each), whose gradients the compositing-backward launches leave next to d_raw."""
+    temp_depth; None each), whose gradients the compositing-backward launches leave next to d_raw.
+    With V's patch LPIPS term (L.lpips_P > 0): forward, the patches of BOTH levels packed into one batch, one LPIPS forward and the
+    per-image values into the tail (ops.lpips_step_forward, ops.closs_finish); backward, the per-image seeds from g_loss, ONE LPIPS backward over the kept
+    activations (here, with the real seeds: the arithmetic of lpips._LpipsFn under autograd), and the levels' compositing-backward
+    launches read their slice of its NCHW gradient in place."""
 
     @staticmethod
     def forward(ctx, raw, raw_c, z, z_c, rays, noise, noise_c, white, L, rgb_c, depth_c, ws_c, *temps):
@@ -449,8 +453,12 @@ class _RenderClossFn(torch.autograd.Function):
         rgb, disp, acc, weights, depth, ws = ops.composite_forward_closs(raw, z, rays, noise, white, L)
         want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or (L.forms and any(ctx.needs_input_grad[12:]))
         ctx.n_temps = len(temps)
-        terms, stats, patch_d, ssim_d, d_temp = ops.closs_finish(L, z.shape[0], ws, ws_c, depth, depth_c, rgb, rgb_c, want_grad=want)
-        ctx.save_for_backward(raw, raw_c, z, z_c, rays, rgb, rgb_c, depth, depth_c, stats, patch_d, ssim_d, d_temp)
+        lpips_v = lpips_ws = None
+        if L.lpips_P > 0:
+            lpips_v, lpips_ws = ops.lpips_step_forward(L, z.shape[0], rgb, rgb_c, want_grad=want)
+        terms, stats, patch_d, ssim_d, d_temp = ops.closs_finish(L, z.shape[0], ws, ws_c, depth, depth_c, rgb, rgb_c, want_grad=want,
+                                                                 lpips_v=lpips_v)
+        ctx.save_for_backward(raw, raw_c, z, z_c, rays, rgb, rgb_c, depth, depth_c, stats, patch_d, ssim_d, d_temp, lpips_ws)
         ctx.noise, ctx.noise_c, ctx.white, ctx.L = noise, noise_c, white, L
         ctx.temp_shapes = [None if t is None else t.shape for t in temps]
         ctx.mark_non_differentiable(terms, rgb, disp, acc, weights, depth)
@@ -459,7 +467,7 @@ class _RenderClossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, *_rest):
-        raw, raw_c, z, z_c, rays, rgb, rgb_c, depth, depth_c, stats, patch_d, ssim_d, d_temp = ctx.saved_tensors
+        raw, raw_c, z, z_c, rays, rgb, rgb_c, depth, depth_c, stats, patch_d, ssim_d, d_temp, lpips_ws = ctx.saved_tensors
         d_raw = d_raw_c = None
         g_temps = (None,) * ctx.n_temps
         if g_loss is not None:
@@ -469,15 +477,20 @@ class _RenderClossFn(torch.autograd.Function):
             g_temp = torch.empty(4, device=raw.device) if want_t else None   # written by the levels' backward launches
             pair = lambda x, lv: x[2 * lv:2 * lv + 2] if want_t else None  # noqa: E731   (the level's two temperatures)
             ran = [False, False]
+            lp = (None, None)
+            if lpips_ws is not None and (ctx.needs_input_grad[0] or (raw_c is not None and ctx.needs_input_grad[1])):
+                dX = ops.lpips_step_backward(L, lpips_ws, 2 if raw_c is not None else 1, g_loss)
+                lp = (dX[:L.lpips_P], dX[L.lpips_P:] if raw_c is not None else None)
             if ctx.needs_input_grad[0]:
                 d_raw = ops.composite_backward_closs(raw, z, rays, ctx.noise, ctx.white, L, rgb, depth, stats[0:w], g_loss,
                                                      None if patch_d is None else patch_d[0], None if ssim_d is None else ssim_d[0],
-                                                     0, pair(d_temp, 0), pair(g_temp, 0))
+                                                     0, pair(d_temp, 0), pair(g_temp, 0), lpips_dx=lp[0])
                 ran[0] = True
             if raw_c is not None and ctx.needs_input_grad[1]:
                 d_raw_c = ops.composite_backward_closs(raw_c, z_c, rays, ctx.noise_c, ctx.white, L, rgb_c, depth_c, stats[w:2 * w],
                                                        g_loss, None if patch_d is None else patch_d[1],
-                                                       None if ssim_d is None else ssim_d[1], 1, pair(d_temp, 1), pair(g_temp, 1))
+                                                       None if ssim_d is None else ssim_d[1], 1, pair(d_temp, 1), pair(g_temp, 1),
+                                                       lpips_dx=lp[1])
                 ran[1] = True
             if want_t:
                 for lv in (0, 1):       # (a level whose raw takes no gradient had no launch to ride in)

@@ -321,8 +321,9 @@ def add_label_noise(rgb, depth_pred, extras, std, far, generator=None, row0=0):
 
 
 def midas_patch_loss(depth_pred, mono_dpt_s, patch_num=4, patch_size=16):
-    """`mono_depth_mses` of V:1678-1720 (the monocular-depth patch term; its SSIM / LPIPS neighbours are out of scope):
-    the first patch_num * patch_size^2 rays of the batch are the sampled patches (raybank.sample_patch_rays)."""
+    """`mono_depth_mses` of V:1678-1720 (the monocular-depth patch term; its SSIM / LPIPS neighbours on the same patches are
+    patch_ssim / patch_lpips, and all three fold into render_loss: mono=, ssim_w=, lpips_w=): the first patch_num * patch_size^2 rays
+    of the batch are the sampled patches (raybank.sample_patch_rays)."""
     return _PatchDepthLossFn.apply(depth_pred, mono_dpt_s, int(patch_num), int(patch_size) * int(patch_size))
 
 
@@ -373,13 +374,18 @@ _TERM_NAMES = ("loss", "img_loss", "depth_loss", "patch_loss", "img_loss0", "dep
 
 
 def _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, coef, far, rgb_w, depth_w, mono, P, ps, patch_w, counts,
-                       kwargs, ssim_w=0.0, ssim_patches=4, rgb_form="hardmask", depth_form="hardmask", lp_coef=0.0, temps=None):
+                       kwargs, ssim_w=0.0, ssim_patches=4, rgb_form="hardmask", depth_form="hardmask", lp_coef=0.0, temps=None,
+                       lpips_w=0.0, lpips_fn=None):
     """The reference's own sequence (V:1645-1865) on render()'s maps: what render_loss computes, launch by launch.  ssim_w != 0:
     + V's patch SSIM term of every level over the first ssim_patches 16 x 16 patches (loss -= ssim_w ssim_level, after the
-    level's monocular term).  rgb_form / depth_form: the other branches of V / VC as their own lines (render_loss's docstring);
-    temps = (temp_rgb, temp_depth, coarse temp_rgb, coarse temp_depth)."""
+    level's monocular term).  lpips_w != 0 with lpips_fn: + V's patch LPIPS term of every level, one patch_lpips per level over the
+    same patches (loss += lpips_w lpips_level, after the level's SSIM term, V:1726-1728).  rgb_form / depth_form: the other branches
+    of V / VC as their own lines (render_loss's docstring); temps = (temp_rgb, temp_depth, coarse temp_rgb, coarse temp_depth)."""
     if ssim_w != 0 and int(ps) != 16:
         raise ValueError(f"render_loss: the patch SSIM term needs 16 x 16 patches (V:1699), got patch_size {ps}")
+    with_lpips = lpips_w != 0 and lpips_fn is not None
+    if with_lpips and int(ps) != 16:
+        raise ValueError(f"render_loss: the patch LPIPS term needs 16 x 16 patches (V:1699), got patch_size {ps}")
     rgb, disp, acc, depth, extras = render(H, W, K, chunk=chunk, rays=rays, **kwargs)
     tgt = target_s.reshape(-1, 3)
     with_depth = depth_prior is not None
@@ -413,6 +419,10 @@ def _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, coef, 
             sl = patch_ssim(c, tgt, ssim_patches, ps)
             part = part - ssim_w * sl
             terms["ssim" + suffix] = sl.detach()
+        if with_lpips:
+            ll = patch_lpips(c, tgt, lpips_fn, ssim_patches, ps)[0]
+            part = part + lpips_w * ll
+            terms["lpips" + suffix] = ll.detach()
         if with_depth:
             part = part + depth_w * dl
             terms["depth_loss" + suffix] = dl.detach()
@@ -427,13 +437,15 @@ def _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, coef, 
 
 def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32, rays=None, hardmask_coef=0.2, depth_far=None,
                 rgb_w=1.0, depth_w=1.0, mono=None, patch_num=4, patch_size=16, patch_w=0.001, counts=None, ssim_w=0.0, _ss_coins=None,
-                rgb_form="hardmask", depth_form="hardmask", lp_coef=0.0, temp_rgb=None, temp_depth=None, **kwargs):
+                rgb_form="hardmask", depth_form="hardmask", lp_coef=0.0, temp_rgb=None, temp_depth=None, lpips_w=0.0, lpips_fn=None,
+                **kwargs):
     """The loss of one run_nerf_view.train() step as ONE call (V:1636-1865 with the terms this package builds):
 
         rgb, disp, acc, depth_pred, extras = render(H, W, K, chunk=, rays=batch_rays, retraw=True, **render_kwargs_train)
         img_loss   = img2mse(rgb[m == 1], target_s[m == 1]) + hardmask_coef * img2mse(rgb[m == 0], target_s[m == 0])   # V:1645-1648
         loss       = rgb_w * img_loss + patch_w * mono_depth_mses(depth_pred[:P * ps * ps], mono)                   # V:1672-1726
         loss      -= ssim_w * sum_p ssim(rgb_p.reshape(1, 16, 16, 3), target_p.reshape(1, 16, 16, 3), data_range=1) / 4   # V:1701-1727
+        loss      += lpips_w * sum_p lpips_fn((rgb_p - 0.5) * 2, (target_p - 0.5) * 2) / 4        (patches as [1, 3, 16, 16])   # V:1699-1728
         loss      += depth_w * img2mse(depth_pred[m == 1] / far, depth_prior[m == 1] / far)                         # V:1737
         ... and the same terms of the coarse level (V:1786-1788, V:1855-1858, V:1865)
 
@@ -444,9 +456,16 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
     patch_loss, img_loss0, ...).  Values equal the lines above (fp64-association round-off on the sums), parameter gradients after
     loss.backward() bit for bit.  Batches beyond one chunk, more than 8 patches, CPU tensors: the lines above, literally.
     ssim_w (0 = off, the call without the term; 0.005 = V): V's patch SSIM term on the first patch_num 16 x 16 patches of the
-    batch (whether or not `mono` is given), folded into the same launches; terms gain `ssim` / `ssim0`, the level values.  LPIPS
-    stays with the caller, on the returned maps: loss + 0.005 * patch_lpips(rgb, target_s, lpips_fn)[0] (V:1699-1728; the HIP network
-    of consistentnerf_amd.lpips, its own autograd node — not folded into these launches).
+    batch (whether or not `mono` is given), folded into the same launches; terms gain `ssim` / `ssim0`, the level values.
+    lpips_w (0 = off; 0.005 = V) with lpips_fn (V's `lpips_fn`, always on there): V's patch LPIPS term on the same first patch_num
+    16 x 16 patches, inside this autograd node: with a consistentnerf_amd.lpips.LPIPS on the batch's device and the default forms the
+    patches of BOTH levels go through ONE batched LPIPS forward (and, in the backward pass, one LPIPS backward whose NCHW gradient
+    the compositing-backward launches read in place); any other lpips_fn, or a loss form: one patch_lpips per level on the lines
+    route.  terms gain `lpips` / `lpips0` (positive).  lpips_w = 0 or lpips_fn = None: the call without the term.  The returned maps
+    carry NO graph (this node's outputs are detached values): a term computed from them afterwards, such as
+    `loss + 0.005 * patch_lpips(rgb, target_s, lpips_fn)[0]`, adds a number to the loss and no gradient to either network — pass
+    lpips_w= / lpips_fn= instead (or differentiate render()'s maps, as the lines route does).  Raises ValueError for lpips_w != 0
+    without lpips_fn, with patch_size != 16, or with _ss_coins.
 
     rgb_form / depth_form: the other live branches of the reference's two drivers, folded the same way (same launches, no host
     synchronisation; the patch term, the SSIM term and the three weights compose with every form):
@@ -488,7 +507,15 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
         if form == "softmask" and not all(torch.is_tensor(t) and t.numel() == 1 for t in pair):
             raise ValueError(f"render_loss: the softmask form needs {name} = F.softplus(net.{name}) as a 0-d tensor (or a (fine, coarse) "
                              "pair of them)")
-    ssim_w = float(ssim_w)
+    ssim_w, lpips_w = float(ssim_w), float(lpips_w)
+    if lpips_w != 0 and lpips_fn is None:
+        raise ValueError("render_loss: lpips_w != 0 needs lpips_fn (an lpips.LPIPS; consistentnerf_amd.lpips.LPIPS for the folded route)")
+    if lpips_w != 0 and int(patch_size) != 16:
+        raise ValueError(f"render_loss: the patch LPIPS term needs 16 x 16 patches (V:1699), got patch_size {patch_size}")
+    if lpips_w != 0 and _ss_coins is not None:
+        raise ValueError("render_loss: the in-loop consistency step (VT) has no LPIPS term; lpips_w must be 0 with _ss_coins")
+    if lpips_w == 0:
+        lpips_fn = None
     far = float(kwargs.get('far', 1.)) if depth_far is None else float(depth_far)
     n = rays[0].reshape(-1, 3).shape[0] if rays is not None else 0
     P = int(patch_num) if mono is not None else 0
@@ -504,6 +531,10 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
     if sP > 0 and int(patch_size) != 16:
         raise ValueError(f"render_loss: the patch SSIM term needs 16 x 16 patches (V:1699), got patch_size {patch_size}")
     ok = ok and sP <= 8 and sP * ops.PATCH_SSIM_RAYS <= n
+    lP = int(patch_num) if lpips_fn is not None else 0
+    if lP > 0:      # the folded LPIPS term: the HIP network on this device, the default forms (else the lines, never without the term)
+        from .lpips import LPIPS
+        ok = ok and isinstance(lpips_fn, LPIPS) and not forms and 0 < lP <= 8 and lP * ops.PATCH_SSIM_RAYS <= n
     if _ss_coins is not None:       # the in-loop consistency step's primary terms (ss_step_loss): VT:941-969 on render()'s maps
         if not ok or mask is None:
             rgb, disp, acc, depth, extras = render(H, W, K, chunk=chunk, rays=rays, **kwargs)
@@ -518,10 +549,11 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
     if not ok:
         return _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, hardmask_coef, far, rgb_w, depth_w, mono, P,
                                   patch_size, patch_w, counts, kwargs, ssim_w=ssim_w, ssim_patches=int(patch_num), rgb_form=rgb_form,
-                                  depth_form=depth_form, lp_coef=lp_coef, temps=temps)
+                                  depth_form=depth_form, lp_coef=lp_coef, temps=temps, lpips_w=lpips_w, lpips_fn=lpips_fn)
     spec = ops.ClossSpec(tgt, mask, depth_prior, far, hardmask_coef, rgb_w, depth_w, patch_w, mono, P, ps2, counts, ssim_w=ssim_w,
                          ssim_P=sP, rgb_form=RGB_FORMS.index(rgb_form), depth_form=DEPTH_FORMS.index(depth_form), lp_coef=float(lp_coef),
-                         temps=temps if forms else None)
+                         temps=temps if forms else None, lpips_w=lpips_w if lP else 0.0, lpips_P=lP,
+                         lpips_packed=lpips_fn.packed(tgt.device) if lP else None)
     rgb, disp, acc, depth, extras = render(H, W, K, chunk=chunk, rays=rays, _target=spec, **kwargs)
     loss, t = extras.pop('loss'), extras.pop('loss_terms')
     terms = {k: t[i] for i, k in enumerate(_TERM_NAMES)}
@@ -529,6 +561,10 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
         terms["ssim"] = t[8]
         if 'rgb0' in extras:
             terms["ssim0"] = t[9]
+    if lP > 0:
+        terms["lpips"] = t[10]
+        if 'rgb0' in extras:
+            terms["lpips0"] = t[11]
     return loss, terms, rgb, disp, acc, depth, extras
 
 

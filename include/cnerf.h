@@ -28,6 +28,8 @@ extern "C" {
                                 * cnerf_ssim_bwd, cnerf_avg_pool2, cnerf_patch_ssim_loss and their workspace queries) and V's patch SSIM term
                                 * folded into the C3 step (cnerf_closs_finish_ssim, cnerf_composite_bwd_closs_ssim).
                                 * 6: + LPIPS (the lpips section below: cnerf_lpips_*, and its pieces cnerf_conv3x3_*, cnerf_maxpool2_*); append-only.
+                                * 6: + V's patch LPIPS term folded into the C3 step (cnerf_lpips_pack_patches, cnerf_closs_finish_lpips,
+                                * cnerf_lpips_seeds, cnerf_composite_bwd_closs_lpips); append-only.
                                 * 6: + the standard-normal stream beside the uniform one: cnerf_normal_rng, and cnerf_density_noise_rng (the density
                                 * noise R:287-288 of both levels of a render_rays call as one launch); append-only.
                                 * 6: + the in-loop consistency step as ONE render whose row count lives on the device: cnerf_ss_batch (the combined
@@ -350,6 +352,29 @@ int cnerf_composite_bwd_closs_ssim(const float* raw, int raw_ch, const float* z,
                                    const float* stats, const float* g_loss, float rgb_w, float depth_w, float patch_w,
                                    const float* patch_d, int64_t n_patch_rays, float ssim_w, const float* ssim_d, int64_t n_ssim_rays,
                                    float* d_raw, void* stream);
+/* V's patch LPIPS term (V:1699-1706, V:1721, V:1728, coarse V:1838-1859: loss += 0.005 lpips_level) folded into the same step, the
+ * patches of EVERY level through one batched LPIPS pass (the lpips section below).
+ *   cnerf_lpips_pack_patches: the first P <= 8 patches of 256 rays of rgb_last / rgb_coarse (nullable: one level) [B,3] and of target
+ *       [B,3] as the network's batch, pred / gt [levels P, 3, 16, 16] (the last level's patches first, the target's repeated per
+ *       level): element [c][y][x] of patch p = (map[p 256 + y 16 + x][c] - 0.5) * 2.  Then cnerf_lpips_fwd over levels P pairs.
+ *   cnerf_closs_finish_lpips = cnerf_closs_finish_ssim (ssim_P = 0: no SSIM term) + per level lpips_level = (sum_p lpips_v[level
+ *       lpips_P + p]) / 4, accumulated after the level's SSIM term as loss += lpips_w lpips_level; terms12 = the 10 of
+ *       cnerf_closs_finish_ssim + lpips, lpips0.
+ *   cnerf_lpips_seeds: seeds[0 .. n) = (g_loss[0] lpips_w) 0.25 (g_loss NULL = 1; n <= 16), the per-image seeds of cnerf_lpips_bwd.
+ *   cnerf_composite_bwd_closs_lpips = cnerf_composite_bwd_closs_ssim (n_ssim_rays = 0: none) + g_rgb += 2 lpips_dx[p][c][y][x] on
+ *       the first n_lpips_rays (a multiple of 256) rays, lpips_dx = the level's slice [P, 3, 16, 16] of cnerf_lpips_bwd's gradient,
+ *       read in place; the three addends of a colour seed associate as (lpips + ssim) + colour term. */
+int cnerf_lpips_pack_patches(const float* rgb_last, const float* rgb_coarse, const float* target, int P, int64_t B, float* pred, float* gt,
+                             void* stream);
+int cnerf_closs_finish_lpips(const cnerf_closs_sum* t, int ssim_P, float ssim_w, const float* rgb_last, const float* rgb_coarse,
+                             const float* target, int lpips_P, float lpips_w, const float* lpips_v, float* terms12, float* stats,
+                             float* patch_d, float* ssim_d, void* stream);
+int cnerf_lpips_seeds(const float* g_loss, float lpips_w, int n, float* seeds, void* stream);
+int cnerf_composite_bwd_closs_lpips(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride, const float* noise,
+                                    int64_t B, int S, int white_bkgd, const cnerf_closs* L, const float* rgb, const float* depth,
+                                    const float* stats, const float* g_loss, float rgb_w, float depth_w, float patch_w,
+                                    const float* patch_d, int64_t n_patch_rays, float ssim_w, const float* ssim_d, int64_t n_ssim_rays,
+                                    const float* lpips_dx, int64_t n_lpips_rays, float* d_raw, void* stream);
 
 /* The other live loss forms of the reference's drivers folded the same way (V = run_nerf_view.py, VC =
  * run_nerf_view_cal_correspondance.py): the three launches above with a FORM per kind of term.  d = the residual of one element.
