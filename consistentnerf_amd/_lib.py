@@ -192,6 +192,10 @@ SIGNATURES = {
     "cnerf_ssim_bwd_ws_floats": (_i64, [_i64, _i64, _i64, _i64, _i]),
     "cnerf_ssim_bwd": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "cnerf_avg_pool2": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "cnerf_msssim_ws_floats": (_i64, [_i64, _i64, _i64, _i64, _i, _i]),
+    "cnerf_msssim_fwd": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "cnerf_msssim_bwd_ws_floats": (_i64, [_i64, _i64, _i64, _i64, _i, _i]),
+    "cnerf_msssim_bwd": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cnerf_patch_ssim_loss": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "cnerf_adam_hyper": (_i, [_i, C.c_double, C.c_double, C.c_double, C.c_double, _f, _f, _vp]),
     "cnerf_adam_step_dev": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),

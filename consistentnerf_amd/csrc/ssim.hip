@@ -9,6 +9,8 @@
 //             workgroup at a fixed index; ssim_fin_k sums a plane's partials in index order (no float atomics: identical bits).
 //   backward: ssim_tile_k<1> writes the four coefficient maps (times the upstream gradient / the map's size), ssim_bwd_k applies the
 //             transposed filter (zero-padded full correlation, again through LDS) and combines dX (and dY).
+//   MS-SSIM:  the same kernels level by level.  Its backward seeds the last level's S and every other level's cs (ssim_tile_k<2>),
+//             and ssim_bwd_k adds the 2x2 average pool's backward of the level after it in its epilogue.
 #include "ssim.hpp"
 
 namespace {
@@ -39,6 +41,7 @@ __device__ __forceinline__ double block_sum256(double v, double* sh) {
 
 // MODE 0: per-workgroup partial sums of S and cs -> part[(plane * ntiles + tile) * 2 + {0, 1}]
 // MODE 1: coefficient maps coef[q][plane][Ho][Wo], q = dS/dmu_x, dS/dmu_y, dS/df(x^2), dS/df(xy), times g[plane] * inv_cnt
+// MODE 2: the same four maps of cs instead of S (cn_ssim_pixel_cs): the seed of an MS-SSIM level below the last
 template <int MODE>
 __global__ __launch_bounds__(NT) void ssim_tile_k(const float* __restrict__ X, const float* __restrict__ Y, SsimShape s, SsimWin win,
                                                   double* __restrict__ part, float* __restrict__ coef, const float* __restrict__ g,
@@ -73,7 +76,7 @@ __global__ __launch_bounds__(NT) void ssim_tile_k(const float* __restrict__ X, c
   }
   __syncthreads();
   double sS = 0.0, sC = 0.0;
-  const float gsc = MODE == 1 ? g[plane] * inv_cnt : 0.f;
+  const float gsc = MODE != 0 ? g[plane] * inv_cnt : 0.f;
   for (int i = threadIdx.x; i < FTH * FTW; i += NT) {
     const int r = i / FTW, c = i - r * FTW, orow = r0 + r, ocol = c0 + c;
     if (orow >= s.Ho || ocol >= s.Wo) continue;
@@ -85,8 +88,10 @@ __global__ __launch_bounds__(NT) void ssim_tile_k(const float* __restrict__ X, c
       for (int k = 0; k < win.kw; ++k) a = fma((double)win.gw[k], vq[k], a);
       q[k5] = a;
     }
-    const CnSsimPix p = cn_ssim_pixel_var((float)q[0], (float)q[1], (float)(q[2] - q[0] * q[0]), (float)(q[3] - q[1] * q[1]),
-                                          (float)(q[4] - q[0] * q[1]), s.C1, s.C2, MODE == 1);
+    const float mx = (float)q[0], my = (float)q[1], sxx = (float)(q[2] - q[0] * q[0]), syy = (float)(q[3] - q[1] * q[1]),
+                sxy = (float)(q[4] - q[0] * q[1]);
+    const CnSsimPix p = MODE == 2 ? cn_ssim_pixel_cs(mx, my, sxx, syy, sxy, s.C1, s.C2)
+                                  : cn_ssim_pixel_var(mx, my, sxx, syy, sxy, s.C1, s.C2, MODE == 1);
     if (MODE == 0) {
       sS += (double)p.S; sC += (double)p.cs;
     } else {
@@ -124,10 +129,13 @@ __global__ __launch_bounds__(64) void ssim_fin_k(const double* __restrict__ part
   }
 }
 
-// dX[i] = f^T(ax)[i] + 2 X[i] f^T(b)[i] + Y[i] f^T(c)[i]  (dY with ay, Y, X): one workgroup per BTH x BTW input-space tile of a plane
+// dX[i] = f^T(ax)[i] + 2 X[i] f^T(b)[i] + Y[i] f^T(c)[i]  (dY with ay, Y, X): one workgroup per BTH x BTW input-space tile of a plane.
+// nX / nY (nullable) [nplanes, nH, nW] = the gradient of the next MS-SSIM level, the 2x2 average pool of this one (padding
+// (H % 2, W % 2), counted): its backward, a quarter of the one window pixel (i, j) lies in, is the last addend of the sum.
 __global__ __launch_bounds__(NT) void ssim_bwd_k(const float* __restrict__ X, const float* __restrict__ Y, SsimShape s, SsimWin win,
                                                  const float* __restrict__ coef, int64_t nplanes, float* __restrict__ dX,
-                                                 float* __restrict__ dY) {
+                                                 float* __restrict__ dY, const float* __restrict__ nX, const float* __restrict__ nY,
+                                                 int nH, int nW) {
   extern __shared__ float lds[];
   const int64_t plane = blockIdx.y;
   const int tiles_x = (s.W + BTW - 1) / BTW;
@@ -167,8 +175,15 @@ __global__ __launch_bounds__(NT) void ssim_bwd_k(const float* __restrict__ X, co
     }
     const int64_t o = plane * s.H * s.W + (int64_t)gr * s.W + gc;
     const float x = X[o], y = Y[o];
-    dX[o] = f[0] + 2.f * x * f[1] + y * f[2];
-    if (dY) dY[o] = f[3] + 2.f * y * f[1] + x * f[2];
+    float dx = f[0] + 2.f * x * f[1] + y * f[2];
+    float dy = f[3] + 2.f * y * f[1] + x * f[2];
+    if (nX) {
+      const int64_t n = plane * nH * nW + (int64_t)((gr + (s.H & 1)) >> 1) * nW + ((gc + (s.W & 1)) >> 1);
+      dx += 0.25f * nX[n];
+      if (dY) dy += 0.25f * nY[n];
+    }
+    dX[o] = dx;
+    if (dY) dY[o] = dy;
   }
 }
 
@@ -223,6 +238,67 @@ bool make_shape(int64_t N, int64_t C, int64_t H, int64_t W, int win_size, float 
   return true;
 }
 
+// the two forward launches of one level: per-tile fp64 partials, then the per-plane means (cs_nc nullable)
+int launch_fwd(const float* X, const float* Y, const SsimShape& s, const SsimWin& w, int64_t planes, double* part, float* ssim_nc,
+               float* cs_nc, void* stream) {
+  const size_t lds = sizeof(float) * (size_t)(2 * (FTH + w.kh - 1) * (FTW + w.kw - 1) + 2 * 5 * FTH * (FTW + w.kw - 1));
+  hipLaunchKernelGGL(ssim_tile_k<0>, dim3(s.ntiles, (unsigned)planes), dim3(NT), lds, cn_stream(stream), X, Y, s, w, part,
+                     (float*)nullptr, (const float*)nullptr, 0.f, planes);
+  CN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(ssim_fin_k, dim3((unsigned)planes), dim3(64), 0, cn_stream(stream), part, s.ntiles, (double)s.Ho * (double)s.Wo,
+                     ssim_nc, cs_nc);
+  CN_CHECK_LAUNCH();
+  return CNERF_OK;
+}
+
+// the two backward launches of one level: the coefficient maps of a seed g on the mean of S (on_cs = false) or of cs (true), then
+// the transposed filter + the pooled-back quarter of the next level's gradient nX / nY [planes, nH, nW] (nullable)
+int launch_bwd(const float* X, const float* Y, const SsimShape& s, const SsimWin& w, int64_t planes, bool on_cs, const float* g,
+               float* coef, float* dX, float* dY, const float* nX, const float* nY, int nH, int nW, void* stream) {
+  const size_t lds_f = sizeof(float) * (size_t)(2 * (FTH + w.kh - 1) * (FTW + w.kw - 1) + 2 * 5 * FTH * (FTW + w.kw - 1));
+  const float inv_cnt = (float)(1.0 / ((double)s.Ho * (double)s.Wo));
+  if (on_cs)
+    hipLaunchKernelGGL(ssim_tile_k<2>, dim3(s.ntiles, (unsigned)planes), dim3(NT), lds_f, cn_stream(stream), X, Y, s, w,
+                       (double*)nullptr, coef, g, inv_cnt, planes);
+  else
+    hipLaunchKernelGGL(ssim_tile_k<1>, dim3(s.ntiles, (unsigned)planes), dim3(NT), lds_f, cn_stream(stream), X, Y, s, w,
+                       (double*)nullptr, coef, g, inv_cnt, planes);
+  CN_CHECK_LAUNCH();
+  const int nq = dY ? 4 : 3;
+  const size_t lds_b = sizeof(float) * (size_t)(nq * (BTH + w.kh - 1) * (BTW + w.kw - 1) + nq * BTH * (BTW + w.kw - 1));
+  const int tiles = (int)(cn_div_up(s.W, BTW) * cn_div_up(s.H, BTH));
+  hipLaunchKernelGGL(ssim_bwd_k, dim3(tiles, (unsigned)planes), dim3(NT), lds_b, cn_stream(stream), X, Y, s, w,
+                     (const float*)coef, planes, dX, dY, nX, nY, nH, nW);
+  CN_CHECK_LAUNCH();
+  return CNERF_OK;
+}
+
+constexpr int MS_MAX_LEVELS = 24;
+
+// The MS-SSIM pyramid: level l's sides (l = 0 the input; each next one H / 2 + H % 2), shapes and windows, and where a level >= 1
+// of one image starts inside a pyramid buffer [levels 1.. of X][levels 1.. of Y] (`half` floats each).
+struct MsPlan {
+  int levels;
+  int64_t planes, off[MS_MAX_LEVELS], half, max_part, max_coef;
+  SsimShape s[MS_MAX_LEVELS];
+  SsimWin w[MS_MAX_LEVELS];
+};
+
+bool make_plan(int64_t N, int64_t C, int64_t H, int64_t W, int win_size, float win_sigma, float C1, float C2, int levels, MsPlan* p) {
+  if (levels < 1 || levels > MS_MAX_LEVELS) return false;
+  p->levels = levels; p->planes = N * C; p->half = 0; p->max_part = 0; p->max_coef = 0;
+  for (int l = 0; l < levels; ++l) {
+    if (H <= 0 || W <= 0 || !make_shape(N, C, H, W, win_size, win_sigma, C1, C2, FTW, &p->s[l], &p->w[l])) return false;
+    p->off[l] = p->half;
+    if (l > 0) p->half += p->planes * H * W;
+    const int64_t part = 2 * p->planes * p->s[l].ntiles, coef = 4 * p->planes * p->s[l].Ho * p->s[l].Wo;
+    p->max_part = part > p->max_part ? part : p->max_part;
+    p->max_coef = coef > p->max_coef ? coef : p->max_coef;
+    H = H / 2 + H % 2; W = W / 2 + W % 2;
+  }
+  return true;
+}
+
 }  // namespace
 
 extern "C" int64_t cnerf_ssim_ws_floats(int64_t N, int64_t C, int64_t H, int64_t W, int win_size) {
@@ -238,16 +314,7 @@ extern "C" int cnerf_ssim_fwd(const float* X, const float* Y, int64_t N, int64_t
   if (!X || !Y || !ssim_nc || !workspace || ((uintptr_t)workspace & 7) != 0 ||
       !make_shape(N, C, H, W, win_size, win_sigma, C1, C2, FTW, &s, &w))
     return CNERF_E_ARG;
-  const int64_t planes = N * C;
-  const size_t lds = sizeof(float) * (size_t)(2 * (FTH + w.kh - 1) * (FTW + w.kw - 1) + 2 * 5 * FTH * (FTW + w.kw - 1));
-  double* part = reinterpret_cast<double*>(workspace);
-  hipLaunchKernelGGL(ssim_tile_k<0>, dim3(s.ntiles, (unsigned)planes), dim3(NT), lds, cn_stream(stream), X, Y, s, w, part,
-                     (float*)nullptr, (const float*)nullptr, 0.f, planes);
-  CN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(ssim_fin_k, dim3((unsigned)planes), dim3(64), 0, cn_stream(stream), part, s.ntiles, (double)s.Ho * (double)s.Wo,
-                     ssim_nc, cs_nc);
-  CN_CHECK_LAUNCH();
-  return CNERF_OK;
+  return launch_fwd(X, Y, s, w, N * C, reinterpret_cast<double*>(workspace), ssim_nc, cs_nc, stream);
 }
 
 extern "C" int64_t cnerf_ssim_bwd_ws_floats(int64_t N, int64_t C, int64_t H, int64_t W, int win_size) {
@@ -263,18 +330,7 @@ extern "C" int cnerf_ssim_bwd(const float* X, const float* Y, int64_t N, int64_t
   SsimWin w;
   if (!X || !Y || !g_ssim || !dX || !workspace || !make_shape(N, C, H, W, win_size, win_sigma, C1, C2, FTW, &s, &w))
     return CNERF_E_ARG;
-  const int64_t planes = N * C;
-  const size_t lds_f = sizeof(float) * (size_t)(2 * (FTH + w.kh - 1) * (FTW + w.kw - 1) + 2 * 5 * FTH * (FTW + w.kw - 1));
-  hipLaunchKernelGGL(ssim_tile_k<1>, dim3(s.ntiles, (unsigned)planes), dim3(NT), lds_f, cn_stream(stream), X, Y, s, w,
-                     (double*)nullptr, workspace, g_ssim, (float)(1.0 / ((double)s.Ho * (double)s.Wo)), planes);
-  CN_CHECK_LAUNCH();
-  const int nq = dY ? 4 : 3;
-  const size_t lds_b = sizeof(float) * (size_t)(nq * (BTH + w.kh - 1) * (BTW + w.kw - 1) + nq * BTH * (BTW + w.kw - 1));
-  const int tiles = (int)(cn_div_up(W, BTW) * cn_div_up(H, BTH));
-  hipLaunchKernelGGL(ssim_bwd_k, dim3(tiles, (unsigned)planes), dim3(NT), lds_b, cn_stream(stream), X, Y, s, w, workspace, planes, dX,
-                     dY);
-  CN_CHECK_LAUNCH();
-  return CNERF_OK;
+  return launch_bwd(X, Y, s, w, N * C, false, g_ssim, workspace, dX, dY, nullptr, nullptr, 0, 0, stream);
 }
 
 extern "C" int cnerf_avg_pool2(const float* X, int64_t N, int64_t C, int64_t H, int64_t W, float* out, void* stream) {
@@ -285,6 +341,65 @@ extern "C" int cnerf_avg_pool2(const float* X, int64_t N, int64_t C, int64_t H, 
   hipLaunchKernelGGL(avg_pool2_k, dim3((unsigned)cn_div_up(tot, NT)), dim3(NT), 0, cn_stream(stream), X, N * C, (int)H, (int)W, ph, pw,
                      Ho, Wo, out);
   CN_CHECK_LAUNCH();
+  return CNERF_OK;
+}
+
+// ---- MS-SSIM: the level walk.  Forward: cnerf_ssim_fwd's two launches per level and cnerf_avg_pool2's in between (the same bits as
+// that sequence of calls), the pooled levels kept in `pyr`.  Backward: from the last level down, one coefficient launch (the last
+// level's seed is on the mean of S, every other level's on the mean of cs) and one transposed-filter launch per level, which also
+// adds the pooled-back quarter of the level after it: no un-pool pass, no atomics, nothing read back.
+extern "C" int64_t cnerf_msssim_ws_floats(int64_t N, int64_t C, int64_t H, int64_t W, int win_size, int levels) {
+  MsPlan p;
+  return make_plan(N, C, H, W, win_size, 1.5f, 0.f, 1.f, levels, &p) ? 2 * p.max_part : 0;     // fp64 pairs per tile
+}
+
+extern "C" int cnerf_msssim_fwd(const float* X, const float* Y, int64_t N, int64_t C, int64_t H, int64_t W, int win_size,
+                                float win_sigma, float C1, float C2, int levels, float* v, float* pyr, float* workspace,
+                                void* stream) {
+  MsPlan p;
+  if (!X || !Y || !v || !pyr || !workspace || ((uintptr_t)workspace & 7) != 0 ||
+      !make_plan(N, C, H, W, win_size, win_sigma, C1, C2, levels, &p))
+    return CNERF_E_ARG;
+  const float *x = X, *y = Y;
+  for (int l = 0; l < levels; ++l) {
+    const bool last = l == levels - 1;
+    // below the last level the mean of S lands in v's last row, which the last level then overwrites
+    int rc = launch_fwd(x, y, p.s[l], p.w[l], p.planes, reinterpret_cast<double*>(workspace), v + (levels - 1) * p.planes,
+                        last ? nullptr : v + l * p.planes, stream);
+    if (rc != CNERF_OK) return rc;
+    if (!last) {
+      float *nx = pyr + p.off[l + 1], *ny = pyr + p.half + p.off[l + 1];
+      if ((rc = cnerf_avg_pool2(x, N, C, p.s[l].H, p.s[l].W, nx, stream)) != CNERF_OK) return rc;
+      if ((rc = cnerf_avg_pool2(y, N, C, p.s[l].H, p.s[l].W, ny, stream)) != CNERF_OK) return rc;
+      x = nx; y = ny;
+    }
+  }
+  return CNERF_OK;
+}
+
+extern "C" int64_t cnerf_msssim_bwd_ws_floats(int64_t N, int64_t C, int64_t H, int64_t W, int win_size, int levels) {
+  MsPlan p;
+  return make_plan(N, C, H, W, win_size, 1.5f, 0.f, 1.f, levels, &p) ? p.max_coef + 2 * p.half : 0;
+}
+
+extern "C" int cnerf_msssim_bwd(const float* X, const float* Y, int64_t N, int64_t C, int64_t H, int64_t W, int win_size,
+                                float win_sigma, float C1, float C2, int levels, const float* pyr, const float* g_v, float* dX,
+                                float* dY, float* workspace, void* stream) {
+  MsPlan p;
+  if (!X || !Y || !pyr || !g_v || !dX || !workspace || !make_plan(N, C, H, W, win_size, win_sigma, C1, C2, levels, &p))
+    return CNERF_E_ARG;
+  float *coef = workspace, *wdx = workspace + p.max_coef, *wdy = wdx + p.half;    // the coarser levels' dX / dY, pyr's layout
+  for (int l = levels - 1; l >= 0; --l) {
+    const bool last = l == levels - 1;
+    const float* x = l ? pyr + p.off[l] : X;
+    const float* y = l ? pyr + p.half + p.off[l] : Y;
+    float* dx = l ? wdx + p.off[l] : dX;
+    float* dy = dY ? (l ? wdy + p.off[l] : dY) : nullptr;
+    const int rc = launch_bwd(x, y, p.s[l], p.w[l], p.planes, !last, g_v + l * p.planes, coef, dx, dy,
+                              last ? nullptr : wdx + p.off[l + 1], (last || !dY) ? nullptr : wdy + p.off[l + 1],
+                              last ? 0 : p.s[l + 1].H, last ? 0 : p.s[l + 1].W, stream);
+    if (rc != CNERF_OK) return rc;
+  }
   return CNERF_OK;
 }
 

@@ -7,6 +7,8 @@
 //   dS/d f(x^2) = dS/d f(y^2) = -S / B2,   dS/d f(xy) = 2 l / B2,
 //   dS/d mu_x = cs 2 (mu_y - l mu_x) / B1 + 2 mu_x S / B2 - 2 l mu_y / B2   (and x <-> y)
 // and dX = f^T(dS/dmu_x) + 2 X f^T(dS/df(x^2)) + Y f^T(dS/df(xy)), f^T the zero-padded full correlation.
+// MS-SSIM keeps the mean of cs at every level but the last, so its backward needs the same four derivatives of cs
+// (cn_ssim_pixel_cs) and, per level, a quarter of the next (2x2 average-pooled) level's gradient on top of dX.
 #pragma once
 #include "common.hpp"
 
@@ -48,6 +50,20 @@ __device__ __forceinline__ CnSsimPix cn_ssim_pixel_var(float mx, float my, float
   } else {
     o.ax = o.ay = o.b = o.c = 0.f;
   }
+  return o;
+}
+
+// The same pixel with the four coefficients of a seed on cs instead of S (MS-SSIM's levels below the last keep the mean of cs):
+//   d cs/d f(x^2) = d cs/d f(y^2) = -cs / B2,   d cs/d f(xy) = 2 / B2,   d cs/d mu_x = 2 (mu_x cs - mu_y) / B2   (and x <-> y)
+__device__ __forceinline__ CnSsimPix cn_ssim_pixel_cs(float mx, float my, float sxx, float syy, float sxy, float C1, float C2) {
+  CnSsimPix o;
+  const float B2 = sxx + syy + C2, B1 = mx * mx + my * my + C1;
+  o.cs = (2.f * sxy + C2) / B2;
+  o.S = (2.f * (mx * my) + C1) / B1 * o.cs;
+  o.b = -o.cs / B2;
+  o.c = 2.f / B2;
+  o.ax = 2.f * (mx * o.cs - my) / B2;
+  o.ay = 2.f * (my * o.cs - mx) / B2;
   return o;
 }
 

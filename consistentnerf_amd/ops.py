@@ -1210,6 +1210,49 @@ def avg_pool2(X: Tensor) -> Tensor:
     return out
 
 
+def _msssim_pyr_floats(N: int, Cc: int, H: int, W: int, levels: int) -> int:
+    """Floats of the pooled levels 2 .. `levels` of X and of Y (include/cnerf.h: pyr)."""
+    n = 0
+    for _ in range(int(levels) - 1):
+        H, W = H // 2 + H % 2, W // 2 + W % 2
+        n += N * Cc * H * W
+    return 2 * n
+
+
+def msssim_forward(X: Tensor, Y: Tensor, win_size: int, win_sigma: float, C1: float, C2: float, levels: int):
+    """cnerf_msssim_fwd: (v [levels, N, C], pyr) — v = per plane the mean of cs at the levels below the last and of SSIM at the
+    last; pyr = the pooled levels of X and Y, what msssim_backward needs besides X and Y."""
+    X, Y = _ssim_args(X, Y, win_size)
+    N, Cc, H, W = X.shape
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.cnerf_msssim_ws_floats(N, Cc, H, W, int(win_size), int(levels)) // 2), device=X.device,
+                     dtype=torch.float64)
+    v = torch.empty(int(levels), N, Cc, device=X.device)
+    pyr = torch.empty(max(1, _msssim_pyr_floats(N, Cc, H, W, levels)), device=X.device)
+    _lib.check(lib.cnerf_msssim_fwd(_p(X), _p(Y), N, Cc, H, W, int(win_size), float(win_sigma), float(C1), float(C2), int(levels),
+                                    _p(v), _p(pyr), _p(ws), _stream()), "cnerf_msssim_fwd")
+    return v, pyr
+
+
+def msssim_backward(X: Tensor, Y: Tensor, win_size: int, win_sigma: float, C1: float, C2: float, pyr: Tensor, g_v: Tensor,
+                    want_dY: bool = True):
+    """cnerf_msssim_bwd: (dX, dY | None), the gradient of sum(g_v * v) (g_v [levels, N, C]; pyr from msssim_forward)."""
+    X, Y = _ssim_args(X, Y, win_size)
+    N, Cc, H, W = X.shape
+    levels = g_v.shape[0]
+    g = _chk(g_v.reshape(levels, N, Cc), "g_v")
+    pyr = _chk(pyr, "pyr")
+    if pyr.numel() < _msssim_pyr_floats(N, Cc, H, W, levels):
+        raise CnerfError(f"msssim_backward: pyr holds {pyr.numel()} floats, {levels} levels of {tuple(X.shape)} need more")
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.cnerf_msssim_bwd_ws_floats(N, Cc, H, W, int(win_size), levels)), device=X.device)
+    dX = torch.empty_like(X)
+    dY = torch.empty_like(Y) if want_dY else None
+    _lib.check(lib.cnerf_msssim_bwd(_p(X), _p(Y), N, Cc, H, W, int(win_size), float(win_sigma), float(C1), float(C2), levels, _p(pyr),
+                                    _p(g), _p(dX), _p(dY), _p(ws), _stream()), "cnerf_msssim_bwd")
+    return dX, dY
+
+
 def patch_ssim_loss(rgb: Tensor, target: Tensor, P: int, want_grad: bool = True):
     """V:1696-1720's SSIM lines (cnerf_patch_ssim_loss): (value[1] = sum_p ssim_p / 4, d value / d rgb [P * 256, 3] | None) over
     the first P * 256 rays."""

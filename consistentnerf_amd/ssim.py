@@ -5,8 +5,11 @@ can stand in for it:  `sys.modules['pytorch_msssim'] = consistentnerf_amd.ssim`.
 an 11-tap Gaussian window (sigma 1.5) filtering along H then W (a side shorter than the window is left unfiltered), single-pass
 variances in fp32, per-channel means; MS-SSIM over five levels with 2x2 average pooling in between.
 
-Inputs: CUDA float32 [N, C, H, W] tensors (no CPU path: anything else raises).  `ssim` is differentiable w.r.t. X and Y through the
-HIP backward; `ms_ssim` is a metric (forward only).  Not supported: an explicit `win=` tensor, 5-D (volumetric) inputs.
+Inputs: CUDA float32 [N, C, H, W] tensors (no CPU path: anything else raises).  `ssim` and `ms_ssim` are differentiable w.r.t. X and
+Y through the HIP backward, so `loss = 1 - ms_ssim(x, y)` trains: MS-SSIM's per-level means come from one C call and go back through
+one (two launches per level, the pooling backward inside the transposed filter's); the product over the levels, its relu and powers
+are ATen lines on levels x N x C numbers, so a plane with a level at cs <= 0 gets the gradient 0 exactly, as in the package.
+Not supported: an explicit `win=` tensor, 5-D (volumetric) inputs.
 """
 import torch
 
@@ -70,25 +73,38 @@ def ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5, wi
     return s.mean() if size_average else s.mean(1)
 
 
+class _MsSsimFn(torch.autograd.Function):
+    """(X, Y) -> v [levels, N, C]: the per-channel mean of cs at every level below the last, of SSIM at the last (one C call);
+    the backward walks the levels back in 2 * levels launches.  X, Y and the pooled levels are kept only when a gradient can be
+    asked for."""
+
+    @staticmethod
+    def forward(ctx, X, Y, win_size, win_sigma, C1, C2, levels):
+        v, pyr = ops.msssim_forward(X, Y, win_size, win_sigma, C1, C2, levels)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            ctx.save_for_backward(X, Y, pyr)
+            ctx.cfg = (win_size, win_sigma, C1, C2)
+        return v
+
+    @staticmethod
+    def backward(ctx, g):
+        X, Y, pyr = ctx.saved_tensors
+        dX, dY = ops.msssim_backward(X, Y, *ctx.cfg, pyr, g.contiguous(), want_dY=ctx.needs_input_grad[1])
+        return (dX if ctx.needs_input_grad[0] else None), dY, None, None, None, None, None
+
+
 def ms_ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5, win=None, weights=None, K=(0.01, 0.03)):
     """pytorch_msssim.ms_ssim: prod_l relu(cs_l) ** w_l over the first four levels times relu(ssim_5) ** w_5, the levels 2x2
-    average-pooled (odd sides padded, the padding counted).  Needs min(H, W) > (win_size - 1) * 16.  Forward only."""
+    average-pooled (odd sides padded, the padding counted).  Needs min(H, W) > (win_size - 1) * 16.  Differentiable w.r.t. X and
+    Y; a plane with a level at cs_l <= 0 (ssim_5 <= 0) has the value 0 and the gradient 0."""
     _check(X, Y, win, win_size)
-    if torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad):
-        raise NotImplementedError("ms_ssim: no backward (a metric here); call it under torch.no_grad() or on detached tensors")
     smaller_side = min(X.shape[-2:])
     if not smaller_side > (win_size - 1) * (2 ** 4):
         raise ValueError(f"Image size should be larger than {(win_size - 1) * (2 ** 4)} due to the 4 downsamplings in ms-ssim")
     w = X.new_tensor(MS_WEIGHTS if weights is None else weights)
     C1, C2 = _consts(data_range, K)
-    mcs = []
-    for i in range(w.shape[0]):
-        s, cs = ops.ssim_forward(X, Y, int(win_size), float(win_sigma), float(C1), float(C2))
-        if i < w.shape[0] - 1:
-            mcs.append(torch.relu(cs))
-            X, Y = ops.avg_pool2(X), ops.avg_pool2(Y)
-    s = torch.relu(s)
-    val = torch.prod(torch.stack(mcs + [s], dim=0) ** w.view(-1, 1, 1), dim=0)
+    v = _MsSsimFn.apply(X, Y, int(win_size), float(win_sigma), float(C1), float(C2), int(w.shape[0]))
+    val = torch.prod(torch.relu(v) ** w.view(-1, 1, 1), dim=0)
     return val.mean() if size_average else val.mean(1)
 
 

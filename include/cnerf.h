@@ -27,6 +27,7 @@ extern "C" {
                                 * cnerf_composite_bwd_lossform) and the stand-alone cnerf_softmask_loss;  SSIM / MS-SSIM (the ssim section below: cnerf_ssim_fwd,
                                 * cnerf_ssim_bwd, cnerf_avg_pool2, cnerf_patch_ssim_loss and their workspace queries) and V's patch SSIM term
                                 * folded into the C3 step (cnerf_closs_finish_ssim, cnerf_composite_bwd_closs_ssim).
+                                * 6: + MS-SSIM with its backward as one call each (cnerf_msssim_fwd, cnerf_msssim_bwd and their workspace queries); append-only.
                                 * 6: + LPIPS (the lpips section below: cnerf_lpips_*, and its pieces cnerf_conv3x3_*, cnerf_maxpool2_*); append-only.
                                 * 6: + V's patch LPIPS term folded into the C3 step (cnerf_lpips_pack_patches, cnerf_closs_finish_lpips,
                                 * cnerf_lpips_seeds, cnerf_composite_bwd_closs_lpips); append-only.
@@ -671,6 +672,24 @@ int cnerf_ssim_bwd(const float* X, const float* Y, int64_t N, int64_t C, int64_t
                    float C1, float C2, const float* g_ssim, float* dX, float* dY, float* workspace, void* stream);
 /* avg_pool2d(X, kernel_size=2, stride=2, padding=(H % 2, W % 2)) with the padding counted: out [N, C, H / 2 + H % 2, W / 2 + W % 2] */
 int cnerf_avg_pool2(const float* X, int64_t N, int64_t C, int64_t H, int64_t W, float* out, void* stream);
+/* MS-SSIM, forward and backward, as one call each.  Levels l = 1 .. levels (1 .. 24): X_1 = X, X_{l+1} = cnerf_avg_pool2(X_l), of
+ * sides H_{l+1} = H_l / 2 + H_l % 2.  v [levels][N C] = per plane the mean of the contrast-structure map of the levels below the last
+ * and the mean of the SSIM map of the last: the bits the sequence cnerf_ssim_fwd / cnerf_avg_pool2 gives (the same launches).  The
+ * product prod_l relu(v_l) ^ w_l is the caller's.  pyr = 2 N C sum_{l >= 2} H_l W_l floats the caller owns (at least one): the pooled
+ * levels 2 .. of X, then of Y; written by cnerf_msssim_fwd and read by cnerf_msssim_bwd.  workspace = cnerf_msssim_ws_floats() floats,
+ * 8-byte aligned.
+ * cnerf_msssim_bwd: dX (and dY, nullable: then Y's part of the work is skipped, as in cnerf_ssim_bwd) [N, C, H, W] = the gradient of
+ * sum_l sum_nc g_v[l][nc] v[l][nc], from pyr of a cnerf_msssim_fwd with the same arguments; workspace =
+ * cnerf_msssim_bwd_ws_floats() floats (one level's coefficient maps and the coarser levels' gradients).  From the last level down,
+ * each level is one coefficient launch and one transposed-filter launch that also adds the pooled-back quarter of the level after
+ * it: 2 levels launches, no atomics (identical bits call after call), no allocation, nothing read back. */
+int64_t cnerf_msssim_ws_floats(int64_t N, int64_t C, int64_t H, int64_t W, int win_size, int levels);
+int cnerf_msssim_fwd(const float* X, const float* Y, int64_t N, int64_t C, int64_t H, int64_t W, int win_size, float win_sigma,
+                     float C1, float C2, int levels, float* v, float* pyr, float* workspace, void* stream);
+int64_t cnerf_msssim_bwd_ws_floats(int64_t N, int64_t C, int64_t H, int64_t W, int win_size, int levels);
+int cnerf_msssim_bwd(const float* X, const float* Y, int64_t N, int64_t C, int64_t H, int64_t W, int win_size, float win_sigma,
+                     float C1, float C2, int levels, const float* pyr, const float* g_v, float* dX, float* dY, float* workspace,
+                     void* stream);
 /* V's patch term on its own: rgb / target = the first P * 256 rays [P 256, 3] (P <= 16); each patch read as the library reads the
  * [1, 16, 16, 3] NHWC view (C = ray / 16, H = ray % 16, W = colour; H filtered to 6, W unfiltered).  value[0] = (sum_p ssim_p) / 4
  * (V's literal 4), d_rgb [P 256, 3] (nullable) = d value / d rgb. */
