@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI (include/cnerf.h).  Device memory, streams and allocation are
 PyTorch-ROCm plumbing; every computation here is a HIP kernel of libcnerf_hip.so.  No fallbacks."""
 import ctypes as C
+import dataclasses
 from dataclasses import dataclass
 from typing import List, NamedTuple, Optional, Sequence
 
@@ -255,23 +256,20 @@ def resample(z: Tensor, weights: Tensor, u: Optional[Tensor], want_samples: bool
              Nf: Optional[int] = None):
     z, weights, u = _chk(z, "z"), _chk(weights, "weights"), _chk(u, "u")
     B, Nc = z.shape
-    if rng is not None:        # u generated in the kernel: stream offset + 1
-        z_fine = torch.empty(B, Nc + Nf, device=z.device, dtype=torch.float32)
-        z_std = torch.empty(B, device=z.device, dtype=torch.float32)
-        samples = torch.empty(B, Nf, device=z.device, dtype=torch.float32) if want_samples else None
-        inds = torch.empty(B, Nf, device=z.device, dtype=torch.int64) if want_samples else None
-        r = rng.c(1)
-        _lib.check(_lib.load().cnerf_resample_rng(_p(z), _p(weights), C.byref(r), B, Nc, Nf, _p(z_fine), _p(z_std), _p(samples),
-                                                  _p(inds), _stream()), "cnerf_resample_rng")
-        return (z_fine, z_std, samples, inds) if want_samples else (z_fine, z_std)
-    Nf = u.shape[-1]
-    stride = 0 if u.dim() == 1 or u.shape[0] == 1 else Nf
+    if rng is None:
+        Nf = u.shape[-1]
     z_fine = torch.empty(B, Nc + Nf, device=z.device, dtype=torch.float32)
     z_std = torch.empty(B, device=z.device, dtype=torch.float32)
     samples = torch.empty(B, Nf, device=z.device, dtype=torch.float32) if want_samples else None
     inds = torch.empty(B, Nf, device=z.device, dtype=torch.int64) if want_samples else None
-    _lib.check(_lib.load().cnerf_resample(_p(z), _p(weights), _p(u), stride, B, Nc, Nf, _p(z_fine), _p(z_std),
-                                          _p(samples), _p(inds), _stream()), "cnerf_resample")
+    if rng is not None:        # u generated in the kernel: stream offset + 1
+        r = rng.c(1)
+        _lib.check(_lib.load().cnerf_resample_rng(_p(z), _p(weights), C.byref(r), B, Nc, Nf, _p(z_fine), _p(z_std), _p(samples),
+                                                  _p(inds), _stream()), "cnerf_resample_rng")
+    else:
+        stride = 0 if u.dim() == 1 or u.shape[0] == 1 else Nf
+        _lib.check(_lib.load().cnerf_resample(_p(z), _p(weights), _p(u), stride, B, Nc, Nf, _p(z_fine), _p(z_std),
+                                              _p(samples), _p(inds), _stream()), "cnerf_resample")
     return (z_fine, z_std, samples, inds) if want_samples else (z_fine, z_std)
 
 
@@ -451,34 +449,38 @@ class RenderState:
         self.__dict__.update(kw)
 
 
-def render_forward(spec_c: NetSpec, packed_c: Tensor, spec_f: Optional[NetSpec], packed_f: Optional[Tensor], rays: Tensor,
-                   Nc: int, Nf: int, t_rand: Optional[Tensor] = None, u: Optional[Tensor] = None,
-                   noise0: Optional[Tensor] = None, noise1: Optional[Tensor] = None, lindisp: bool = False,
-                   white_bkgd: bool = False, train: bool = False, retraw: bool = False):
-    """cnerf_render_fwd: render_rays (R:311-421 / V:441-551) of one ray batch in one C call.  Returns (dict with the
-    reference's keys + depth maps, RenderState for render_backward)."""
+def _render_setup(spec_c: NetSpec, spec_f: Optional[NetSpec], B: int, dev, Nc, Nf, lindisp, white_bkgd, ray_stride, train, retraw, u):
+    """What cnerf_render_fwd and cnerf_render_fwd_cam take alike -> (lib, config, coarse net, pointer to the fine net | None,
+    workspace, the dict of output maps, its struct cnerf_render_out, the row stride of u)."""
     lib = _lib.load()
-    rays, t_rand, u = _chk(rays, "rays"), _chk(t_rand, "t_rand"), _chk(u, "u")
-    noise0, noise1 = _chk(noise0, "noise0"), _chk(noise1, "noise1")
-    B, dev = rays.shape[0], rays.device
-    cfg = RenderCfg(int(Nc), int(Nf), int(lindisp), int(white_bkgd), int(rays.shape[1]), int(train))
+    cfg = RenderCfg(int(Nc), int(Nf), int(lindisp), int(white_bkgd), int(ray_stride), int(train))
     nc, nf = spec_c.c(), (spec_f.c() if spec_f is not None else None)
     nfp = C.byref(nf) if nf is not None else None
     n = lib.cnerf_render_ws_floats(C.byref(nc), nfp, C.byref(cfg), B)
     if n < 0:
         raise CnerfError("cnerf_render_ws_floats: inconsistent arguments")
     ws = torch.empty(n, device=dev, dtype=torch.float32)
-    S = Nc + Nf
     ch = (spec_f if (spec_f is not None and Nf > 0) else spec_c).raw_ch
     o = {k: torch.empty(B, 3, device=dev) if k.startswith("rgb") else torch.empty(B, device=dev)
-         for k in ("rgb_map", "disp_map", "acc_map", "depth_map")}
-    if Nf > 0:
-        o.update({k: torch.empty(B, 3, device=dev) if k.startswith("rgb") else torch.empty(B, device=dev)
-                  for k in ("rgb0", "disp0", "acc0", "depth0", "z_std")})
+         for k in ("rgb_map", "disp_map", "acc_map", "depth_map") + (("rgb0", "disp0", "acc0", "depth0", "z_std") if Nf > 0 else ())}
     if retraw:
-        o["raw"] = torch.empty(B, S, ch, device=dev)
+        o["raw"] = torch.empty(B, Nc + Nf, ch, device=dev)
     out = RenderOut(**{k: v.data_ptr() for k, v in o.items()})
     stride = 0 if (u is None or u.dim() == 1 or u.shape[0] == 1) else Nf
+    return lib, cfg, nc, nfp, ws, o, out, stride
+
+
+def render_forward(spec_c: NetSpec, packed_c: Tensor, spec_f: Optional[NetSpec], packed_f: Optional[Tensor], rays: Tensor,
+                   Nc: int, Nf: int, t_rand: Optional[Tensor] = None, u: Optional[Tensor] = None,
+                   noise0: Optional[Tensor] = None, noise1: Optional[Tensor] = None, lindisp: bool = False,
+                   white_bkgd: bool = False, train: bool = False, retraw: bool = False):
+    """cnerf_render_fwd: render_rays (R:311-421 / V:441-551) of one ray batch in one C call.  Returns (dict with the
+    reference's keys + depth maps, RenderState for render_backward)."""
+    rays, t_rand, u = _chk(rays, "rays"), _chk(t_rand, "t_rand"), _chk(u, "u")
+    noise0, noise1 = _chk(noise0, "noise0"), _chk(noise1, "noise1")
+    B, dev = rays.shape[0], rays.device
+    lib, cfg, nc, nfp, ws, o, out, stride = _render_setup(spec_c, spec_f, B, dev, Nc, Nf, lindisp, white_bkgd, rays.shape[1], train,
+                                                          retraw, u)
     _lib.check(lib.cnerf_render_fwd(C.byref(nc), _p(packed_c), nfp, _p(packed_f), _p(rays), B, C.byref(cfg),
                                     _p(_t_vals(Nc, dev)), _p(t_rand), _p(u), stride, _p(noise0), _p(noise1), C.byref(out),
                                     _p(ws), _stream()), "cnerf_render_fwd")
@@ -493,34 +495,13 @@ def render_forward_cam(spec_c: NetSpec, packed_c: Tensor, spec_f: Optional[NetSp
                        noise1: Optional[Tensor] = None, lindisp: bool = False, white_bkgd: bool = False, retraw: bool = False):
     """cnerf_render_fwd_cam: render_rays (inference) of the image chunk [first, first + B) of a camera whose rays are
     generated inside the kernels — no [H*W, 11] ray tensor.  Returns the dict of cnerf_render_fwd."""
-    lib = _lib.load()
     t_rand, u, noise0, noise1 = _chk(t_rand, "t_rand"), _chk(u, "u"), _chk(noise0, "noise0"), _chk(noise1, "noise1")
-    dev = packed_c.device
-    cfg = RenderCfg(int(Nc), int(Nf), int(lindisp), int(white_bkgd), 11, 0)
-    nc, nf = spec_c.c(), (spec_f.c() if spec_f is not None else None)
-    nfp = C.byref(nf) if nf is not None else None
-    n = lib.cnerf_render_ws_floats(C.byref(nc), nfp, C.byref(cfg), B)
-    if n < 0:
-        raise CnerfError("cnerf_render_ws_floats: inconsistent arguments")
-    ws = torch.empty(n, device=dev, dtype=torch.float32)
-    if isinstance(c2w, torch.Tensor):
-        c2w = c2w.detach().cpu().numpy()
-    cam = RayGen(int(H), int(W), float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]), _f4(c2w), float(near),
-                 float(far), int(use_viewdirs), int(ndc), float(ndc_coef[0]), float(ndc_coef[1]), int(first))
-    S = Nc + Nf
-    ch = (spec_f if (spec_f is not None and Nf > 0) else spec_c).raw_ch
-    o = {k: torch.empty(B, 3, device=dev) if k.startswith("rgb") else torch.empty(B, device=dev)
-         for k in ("rgb_map", "disp_map", "acc_map", "depth_map")}
-    if Nf > 0:
-        o.update({k: torch.empty(B, 3, device=dev) if k.startswith("rgb") else torch.empty(B, device=dev)
-                  for k in ("rgb0", "disp0", "acc0", "depth0", "z_std")})
-    if retraw:
-        o["raw"] = torch.empty(B, S, ch, device=dev)
-    out = RenderOut(**{k: v.data_ptr() for k, v in o.items()})
-    stride = 0 if (u is None or u.dim() == 1 or u.shape[0] == 1) else Nf
-    with _timed("render_fwd_cam", B * (Nc + (S if Nf > 0 else 0))):
+    lib, cfg, nc, nfp, ws, o, out, stride = _render_setup(spec_c, spec_f, B, packed_c.device, Nc, Nf, lindisp, white_bkgd, 11, 0, retraw, u)
+    cam = RayGen(int(H), int(W), *_intrinsics(K), _f4(c2w), float(near), float(far), int(use_viewdirs), int(ndc), float(ndc_coef[0]),
+                 float(ndc_coef[1]), int(first))
+    with _timed("render_fwd_cam", B * (Nc + (Nc + Nf if Nf > 0 else 0))):
         _lib.check(lib.cnerf_render_fwd_cam(C.byref(nc), _p(packed_c), nfp, _p(packed_f), C.byref(cam), B, C.byref(cfg),
-                                            _p(_t_vals(Nc, dev)), _p(t_rand), _p(u), stride, _p(noise0), _p(noise1),
+                                            _p(_t_vals(Nc, packed_c.device)), _p(t_rand), _p(u), stride, _p(noise0), _p(noise1),
                                             C.byref(out), _p(ws), _stream()), "cnerf_render_fwd_cam")
     return o
 
@@ -541,16 +522,24 @@ def render_backward(st: RenderState, grads_in: dict, grads_c: List[Tensor], grad
 
 
 # ------------------------------------------------------------------------------------------ compositing
-def composite_forward(raw: Tensor, z: Tensor, rays: Tensor, noise: Optional[Tensor], white_bkgd: bool):
-    raw, z, rays, noise = _chk(raw, "raw"), _chk(z, "z"), _chk(rays, "rays"), _chk(noise, "noise")
+def _composite_args(raw, z, rays, noise, white_bkgd):
+    """-> (the checked raw, B, S, the nine arguments every compositing entry point starts with, the checked tensors those point
+    into: the caller holds them until its launch is enqueued)."""
+    keep = raw, z, rays, noise = _chk(raw, "raw"), _chk(z, "z"), _chk(rays, "rays"), _chk(noise, "noise")
     B, S = z.shape
-    dev = raw.device
-    rgb = torch.empty(B, 3, device=dev)
-    disp, acc, depth = torch.empty(B, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev)
-    weights = torch.empty(B, S, device=dev)
-    _lib.check(_lib.load().cnerf_composite_fwd(_p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S,
-                                               int(white_bkgd), _p(rgb), _p(disp), _p(acc), _p(depth), _p(weights),
-                                               _stream()), "cnerf_composite_fwd")
+    return raw, B, S, (_p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S, int(white_bkgd)), keep
+
+
+def _composite_outputs(B, S, dev):
+    """(rgb, disp, acc, depth, weights) in the order the compositing entry points take them; the wrappers return weights fourth."""
+    return (torch.empty(B, 3, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev),
+            torch.empty(B, S, device=dev))
+
+
+def composite_forward(raw: Tensor, z: Tensor, rays: Tensor, noise: Optional[Tensor], white_bkgd: bool):
+    raw, B, S, pre, _keep = _composite_args(raw, z, rays, noise, white_bkgd)
+    rgb, disp, acc, depth, weights = outs = _composite_outputs(B, S, raw.device)
+    _lib.check(_lib.load().cnerf_composite_fwd(*pre, *map(_p, outs), _stream()), "cnerf_composite_fwd")
     return rgb, disp, acc, weights, depth
 
 
@@ -595,34 +584,26 @@ def end_capture(device):
 def composite_forward_mse(raw: Tensor, z: Tensor, rays: Tensor, noise: Optional[Tensor], white_bkgd: bool, target: Tensor,
                           loss_add: Optional[Tensor] = None):
     """cnerf_composite_fwd_mse -> (rgb, disp, acc, weights, depth, loss[1]): raw2outputs + img2mse(rgb_map, target) (+ loss_add)."""
-    raw, z, rays, noise = _chk(raw, "raw"), _chk(z, "z"), _chk(rays, "rays"), _chk(noise, "noise")
+    raw, B, S, pre, _keep = _composite_args(raw, z, rays, noise, white_bkgd)
     target, loss_add = _chk(target, "target"), _chk(loss_add, "loss_add")
-    B, S = z.shape
     if B == 0 or tuple(target.shape) != (B, 3):
         raise CnerfError(f"composite_forward_mse: target must be [{B}, 3] with B > 0, got {tuple(target.shape)}")
     dev = raw.device
-    rgb = torch.empty(B, 3, device=dev)
-    disp, acc, depth = torch.empty(B, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev)
-    weights = torch.empty(B, S, device=dev)
+    rgb, disp, acc, depth, weights = outs = _composite_outputs(B, S, dev)
     loss = torch.empty(1, device=dev)
     lib = _lib.load()
     ws = torch.empty(lib.cnerf_composite_mse_ws_floats(B) // 2, device=dev, dtype=torch.float64)
-    _lib.check(lib.cnerf_composite_fwd_mse(_p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S,
-                                           int(white_bkgd), _p(target), _p(loss_add), _p(rgb), _p(disp), _p(acc), _p(depth),
-                                           _p(weights), _p(loss), _p(ws), _p(_mse_counter(dev)), _stream()),
-               "cnerf_composite_fwd_mse")
+    _lib.check(lib.cnerf_composite_fwd_mse(*pre, _p(target), _p(loss_add), *map(_p, outs), _p(loss), _p(ws), _p(_mse_counter(dev)),
+                                           _stream()), "cnerf_composite_fwd_mse")
     return rgb, disp, acc, weights, depth, loss
 
 
 def composite_backward_mse(raw, z, rays, noise, white_bkgd, rgb, target, g_loss) -> Tensor:
     """cnerf_composite_bwd_mse: d_raw of mean((rgb_map - target)^2) * g_loss (a device scalar, or None = 1)."""
-    raw, z, rays, noise = _chk(raw, "raw"), _chk(z, "z"), _chk(rays, "rays"), _chk(noise, "noise")
+    raw, _, _, pre, _keep = _composite_args(raw, z, rays, noise, white_bkgd)
     rgb, target, g_loss = _chk(rgb, "rgb"), _chk(target, "target"), _chk(g_loss, "g_loss")
-    B, S = z.shape
     d_raw = torch.empty_like(raw)
-    _lib.check(_lib.load().cnerf_composite_bwd_mse(_p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S,
-                                                   int(white_bkgd), _p(rgb), _p(target), _p(g_loss), _p(d_raw), _stream()),
-               "cnerf_composite_bwd_mse")
+    _lib.check(_lib.load().cnerf_composite_bwd_mse(*pre, _p(rgb), _p(target), _p(g_loss), _p(d_raw), _stream()), "cnerf_composite_bwd_mse")
     return d_raw
 
 
@@ -715,35 +696,30 @@ class ClossSpec:
             need = [k for k in (0, 2) if rf == RGB_FORMS.index("softmask")] + [k for k in (1, 3) if df == DEPTH_FORMS.index("softmask")]
             if len(temps) != 4 or any(temps[k] is None for k in need):
                 raise CnerfError("closs: a softmask form needs its temperature of both levels as device tensors")
-        return ClossSpec(t, m, pr, float(self.far), float(self.coef), float(self.rgb_w), float(self.depth_w), float(self.patch_w),
-                         mono, P, int(self.n), _chk(self.counts, "counts"), coins, seg, _chk(self.counts3, "counts3") if seg else None,
-                         float(self.ssim_w) if sP else 0.0, sP, rf, df, float(self.lp_coef), temps,
-                         float(self.lpips_w) if lP else 0.0, lP, _chk(self.lpips_packed, "lpips_packed") if lP else None)
+        return dataclasses.replace(
+            self, target=t, mask=m, prior=pr, far=float(self.far), coef=float(self.coef), rgb_w=float(self.rgb_w), depth_w=float(self.depth_w),
+            patch_w=float(self.patch_w), mono=mono, P=P, n=int(self.n), counts=_chk(self.counts, "counts"), ss_coins=coins, seg_row=seg,
+            counts3=_chk(self.counts3, "counts3") if seg else None, ssim_w=float(self.ssim_w) if sP else 0.0, ssim_P=sP, rgb_form=rf,
+            depth_form=df, lp_coef=float(self.lp_coef), temps=temps, lpips_w=float(self.lpips_w) if lP else 0.0, lpips_P=lP,
+            lpips_packed=_chk(self.lpips_packed, "lpips_packed") if lP else None)
+
+
+def _closs_args(L: ClossSpec, level: int):
+    """struct cnerf_closs of the batch (+ struct cnerf_lossform of the level with a loss form), by reference."""
+    return [C.byref(L.c())] + ([C.byref(L.form_c(level))] if L.forms else [])
 
 
 def composite_forward_closs(raw: Tensor, z: Tensor, rays: Tensor, noise: Optional[Tensor], white_bkgd: bool, L: ClossSpec,
                             level: int = 0):
     """-> (rgb, disp, acc, weights, depth, ws): raw2outputs + the level's five masked-loss partial sums per workgroup in `ws` (with
     a loss form, L.forms: cnerf_composite_fwd_lossform's ten; level 0 = the last level, 1 = coarse: whose temperatures to read)."""
-    raw, z, rays, noise = _chk(raw, "raw"), _chk(z, "z"), _chk(rays, "rays"), _chk(noise, "noise")
-    B, S = z.shape
-    dev = raw.device
-    rgb = torch.empty(B, 3, device=dev)
-    disp, acc, depth = torch.empty(B, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev)
-    weights = torch.empty(B, S, device=dev)
+    raw, B, S, pre, _keep = _composite_args(raw, z, rays, noise, white_bkgd)
+    rgb, disp, acc, depth, weights = outs = _composite_outputs(B, S, raw.device)
     lib = _lib.load()
-    c = L.c()
-    if L.forms:
-        ws = torch.empty(lib.cnerf_lossform_ws_floats(B) // 2, device=dev, dtype=torch.float64)
-        f = L.form_c(level)
-        _lib.check(lib.cnerf_composite_fwd_lossform(_p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S,
-                                                    int(white_bkgd), C.byref(c), C.byref(f), _p(rgb), _p(disp), _p(acc), _p(depth),
-                                                    _p(weights), _p(ws), _stream()), "cnerf_composite_fwd_lossform")
-        return rgb, disp, acc, weights, depth, ws
-    ws = torch.empty(lib.cnerf_closs_ws_floats(B) // 2, device=dev, dtype=torch.float64)
-    _lib.check(lib.cnerf_composite_fwd_closs(_p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S,
-                                             int(white_bkgd), C.byref(c), _p(rgb), _p(disp), _p(acc), _p(depth), _p(weights),
-                                             _p(ws), _stream()), "cnerf_composite_fwd_closs")
+    name, floats = ("cnerf_composite_fwd_lossform", lib.cnerf_lossform_ws_floats) if L.forms else ("cnerf_composite_fwd_closs",
+                                                                                                   lib.cnerf_closs_ws_floats)
+    ws = torch.empty(floats(B) // 2, device=raw.device, dtype=torch.float64)
+    _lib.check(getattr(lib, name)(*pre, *_closs_args(L, level), *map(_p, outs), _p(ws), _stream()), name)
     return rgb, disp, acc, weights, depth, ws
 
 
@@ -833,65 +809,53 @@ def lpips_step_backward(L: ClossSpec, lpips_ws: Tensor, levels: int, g_loss: Ten
 
 def composite_backward_closs(raw, z, rays, noise, white_bkgd, L: ClossSpec, rgb, depth, stats4, g_loss, patch_d, ssim_d=None,
                              level: int = 0, d_temp2=None, g_temp2=None, lpips_dx=None) -> Tensor:
-    raw, z, rays, noise = _chk(raw, "raw"), _chk(z, "z"), _chk(rays, "rays"), _chk(noise, "noise")
-    B, S = z.shape
+    raw, _, _, pre, _keep = _composite_args(raw, z, rays, noise, white_bkgd)
     d_raw = torch.empty_like(raw)
-    c = L.c()
-    if L.forms:                 # the form's seeds (cnerf_composite_bwd_lossform); stats4 = the level's 8 floats
-        f = L.form_c(level)
-        _lib.check(_lib.load().cnerf_composite_bwd_lossform(
-            _p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S, int(white_bkgd), C.byref(c), C.byref(f), _p(rgb),
-            _p(depth), _p(stats4), _p(g_loss), L.rgb_w, L.depth_w, L.patch_w, L.coef, _p(patch_d),
-            L.P * L.n if patch_d is not None else 0, float(L.ssim_w), _p(ssim_d), 0 if ssim_d is None else ssim_d.numel() // 3,
-            _p(d_temp2), _p(g_temp2), _p(d_raw), _stream()), "cnerf_composite_bwd_lossform")
-        return d_raw
-    if lpips_dx is not None:    # + V's patch LPIPS seeds, the level's [lpips_P, 3, 16, 16] slice of the gradient (+ the SSIM seeds)
-        _lib.check(_lib.load().cnerf_composite_bwd_closs_lpips(
-            _p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S, int(white_bkgd), C.byref(c), _p(rgb), _p(depth),
-            _p(stats4), _p(g_loss), L.rgb_w, L.depth_w, L.patch_w, _p(patch_d), L.P * L.n if patch_d is not None else 0,
-            float(L.ssim_w), _p(ssim_d), 0 if ssim_d is None else ssim_d.numel() // 3, _p(_chk(lpips_dx, "lpips_dx")),
-            lpips_dx.shape[0] * PATCH_SSIM_RAYS, _p(d_raw), _stream()), "cnerf_composite_bwd_closs_lpips")
-        return d_raw
-    if ssim_d is not None:      # + V's patch SSIM seeds (cnerf_composite_bwd_closs_ssim)
-        _lib.check(_lib.load().cnerf_composite_bwd_closs_ssim(
-            _p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S, int(white_bkgd), C.byref(c), _p(rgb), _p(depth),
-            _p(stats4), _p(g_loss), L.rgb_w, L.depth_w, L.patch_w, _p(patch_d), L.P * L.n if patch_d is not None else 0,
-            float(L.ssim_w), _p(ssim_d), ssim_d.numel() // 3, _p(d_raw), _stream()), "cnerf_composite_bwd_closs_ssim")
-        return d_raw
-    _lib.check(_lib.load().cnerf_composite_bwd_closs(_p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S,
-                                                     int(white_bkgd), C.byref(c), _p(rgb), _p(depth), _p(stats4), _p(g_loss),
-                                                     L.rgb_w, L.depth_w, L.patch_w, _p(patch_d),
-                                                     L.P * L.n if patch_d is not None else 0, _p(d_raw), _stream()),
-               "cnerf_composite_bwd_closs")
+    lpips_dx = _chk(lpips_dx, "lpips_dx")
+    # what the four entry points take alike (a loss form: + its struct after the batch's, + coef after the weights); stats4 = the
+    # level's 4 floats, 8 with a loss form
+    args = [*pre, *_closs_args(L, level), _p(rgb), _p(depth), _p(stats4), _p(g_loss), L.rgb_w, L.depth_w, L.patch_w,
+            *([L.coef] if L.forms else []), _p(patch_d), L.P * L.n if patch_d is not None else 0]
+    ssim = [float(L.ssim_w), _p(ssim_d), 0 if ssim_d is None else ssim_d.numel() // 3]      # V's patch SSIM seeds
+    if L.forms:
+        name, args = "cnerf_composite_bwd_lossform", args + ssim + [_p(d_temp2), _p(g_temp2)]
+    elif lpips_dx is not None:  # + V's patch LPIPS seeds, the level's [lpips_P, 3, 16, 16] slice of the gradient (+ the SSIM seeds)
+        name, args = "cnerf_composite_bwd_closs_lpips", args + ssim + [_p(lpips_dx), lpips_dx.shape[0] * PATCH_SSIM_RAYS]
+    elif ssim_d is not None:
+        name, args = "cnerf_composite_bwd_closs_ssim", args + ssim
+    else:
+        name = "cnerf_composite_bwd_closs"
+    _lib.check(getattr(_lib.load(), name)(*args, _p(d_raw), _stream()), name)
     return d_raw
 
 
 def composite_backward(raw, z, rays, noise, white_bkgd, g_rgb, g_disp, g_acc, g_depth) -> Tensor:
-    raw, z, rays, noise = _chk(raw, "raw"), _chk(z, "z"), _chk(rays, "rays"), _chk(noise, "noise")
-    g_rgb, g_disp, g_acc, g_depth = (_chk(g, "grad") for g in (g_rgb, g_disp, g_acc, g_depth))
-    B, S = z.shape
+    raw, _, _, pre, _keep = _composite_args(raw, z, rays, noise, white_bkgd)
+    grads = [_chk(g, "grad") for g in (g_rgb, g_disp, g_acc, g_depth)]
     d_raw = torch.empty_like(raw)
-    _lib.check(_lib.load().cnerf_composite_bwd(_p(raw), raw.shape[-1], _p(z), _p(rays), rays.shape[1], _p(noise), B, S,
-                                               int(white_bkgd), _p(g_rgb), _p(g_disp), _p(g_acc), _p(g_depth),
-                                               _p(d_raw), _stream()), "cnerf_composite_bwd")
+    _lib.check(_lib.load().cnerf_composite_bwd(*pre, *map(_p, grads), _p(d_raw), _stream()), "cnerf_composite_bwd")
     return d_raw
 
 
 # ------------------------------------------------------------------------------------------ rays
 def _f4(a) -> "C.Array":
+    """The top 3 x 4 of a pose (host array, or a tensor: ONE device-to-host copy) as float[12]."""
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
     a = np.ascontiguousarray(np.asarray(a, dtype=np.float32)[:3, :4]).reshape(-1)
     return (C.c_float * 12)(*a.tolist())
+
+
+def _intrinsics(K):
+    """(fx, fy, cx, cy) of a 3 x 3 camera matrix."""
+    return float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
 
 
 def gen_rays(H: int, W: int, K, c2w, near: float, far: float, use_viewdirs: bool, ndc: bool, device,
              ndc_coef=(0.0, 0.0)) -> Tensor:
     rays = torch.empty(H * W, 11 if use_viewdirs else 8, device=device, dtype=torch.float32)
-    if isinstance(c2w, torch.Tensor):
-        c2w = c2w.detach().cpu().numpy()
-    _lib.check(_lib.load().cnerf_gen_rays(H, W, float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]),
-                                          _f4(c2w), float(near), float(far), int(use_viewdirs), int(ndc),
-                                          float(ndc_coef[0]), float(ndc_coef[1]), _p(rays), _stream()),
-               "cnerf_gen_rays")
+    _lib.check(_lib.load().cnerf_gen_rays(H, W, *_intrinsics(K), _f4(c2w), float(near), float(far), int(use_viewdirs), int(ndc),
+                                          float(ndc_coef[0]), float(ndc_coef[1]), _p(rays), _stream()), "cnerf_gen_rays")
     return rays
 
 
@@ -923,9 +887,7 @@ def sample_pixels(H: int, W: int, K, c2w, near: float, far: float, use_viewdirs:
     starts = np.zeros((0, 2), np.int64) if patch_starts is None else np.asarray(patch_starts, np.int64).reshape(-1, 2)
     P = starts.shape[0]
     cfg = PixelBatch()
-    cfg.H, cfg.W, cfg.fx, cfg.fy, cfg.cx, cfg.cy = H, W, float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
-    if isinstance(c2w, torch.Tensor):
-        c2w = c2w.detach().cpu().numpy()
+    cfg.H, cfg.W, (cfg.fx, cfg.fy, cfg.cx, cfg.cy) = H, W, _intrinsics(K)
     cfg.c2w = _f4(c2w)
     cfg.near, cfg.far, cfg.use_viewdirs, cfg.ndc = float(near), float(far), int(use_viewdirs), int(ndc)
     cfg.ndc_ax, cfg.ndc_ay = float(ndc_coef[0]), float(ndc_coef[1])
@@ -960,10 +922,7 @@ def warp_points(P: Tensor, w2c, K, H: int, W: int, flip: bool):
     Xc = torch.empty(N, 3, device=dev)
     px, py = torch.empty(N, device=dev), torch.empty(N, device=dev)
     inb = torch.empty(N, device=dev, dtype=torch.uint8)
-    if isinstance(w2c, torch.Tensor):
-        w2c = w2c.detach().cpu().numpy()
-    _lib.check(_lib.load().cnerf_warp_points(_p(P), N, _f4(w2c), float(K[0][0]), float(K[1][1]), float(K[0][2]),
-                                             float(K[1][2]), H, W, int(flip), _p(Xc), _p(px), _p(py), _p(inb),
+    _lib.check(_lib.load().cnerf_warp_points(_p(P), N, _f4(w2c), *_intrinsics(K), H, W, int(flip), _p(Xc), _p(px), _p(py), _p(inb),
                                              _stream()), "cnerf_warp_points")
     return Xc, px, py, inb.bool()
 
@@ -989,18 +948,8 @@ def ss_ref_rays(rays_o: Tensor, rays_d: Tensor, depth: Tensor, w2c_ref, c2w_ref,
     rays_o, rays_d, depth = _chk(rays_o.reshape(-1, 3), "rays_o"), _chk(rays_d.reshape(-1, 3), "rays_d"), _chk(depth.reshape(-1), "depth")
     image, depth_ref = _chk(image, "image"), _chk(depth_ref, "depth_ref")
     N, dev = rays_o.shape[0], rays_o.device
-    if image.dim() != 3 or image.shape[0] != H or image.shape[1] != W or image.shape[2] < 3 or depth_ref.numel() != H * W:
-        raise CnerfError(f"ss_ref_rays: image must be [{H}, {W}, >=3] and depth_ref [{H}, {W}]")
-    if rays_d.shape[0] != N or depth.shape[0] != N or N == 0:
-        raise CnerfError("ss_ref_rays: rays_o / rays_d / depth must describe the same (non-empty) batch")
-    cfg = SsWarp()
-    r = cfg.ref
-    r.H, r.W, r.fx, r.fy, r.cx, r.cy = int(H), int(W), float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
-    r.c2w = _f4(c2w_ref.detach().cpu().numpy() if isinstance(c2w_ref, torch.Tensor) else c2w_ref)
-    r.near, r.far, r.use_viewdirs, r.ndc = float(near), float(far), int(use_viewdirs), int(ndc)
-    r.ndc_ax, r.ndc_ay, r.first = float(ndc_coef[0]), float(ndc_coef[1]), 0
-    cfg.w2c = _f4(w2c_ref.detach().cpu().numpy() if isinstance(w2c_ref, torch.Tensor) else w2c_ref)
-    cfg.flip, cfg.image_ch, cfg.thr0 = int(flip), int(image.shape[2]), float(thr0)
+    _ss_check("ss_ref_rays", H, W, image, depth_ref, rays_d=rays_d, depth=depth, rays_o=rays_o)
+    cfg = _ss_cfg(w2c_ref, c2w_ref, K, H, W, image, thr0, near, far, use_viewdirs, ndc, ndc_coef, flip)
     rows = torch.empty(N, 11 if use_viewdirs else 8, device=dev) if want_rows else None
     od = torch.empty(2, N, 3, device=dev)
     target, dtgt, diff = torch.empty(N, 3, device=dev), torch.empty(N, device=dev), torch.empty(N, device=dev)
@@ -1021,14 +970,23 @@ def ss_ref_rays(rays_o: Tensor, rays_d: Tensor, depth: Tensor, w2c_ref, c2w_ref,
                 depth_diff=diff[:M], inb=inb, mask=mask[:M], sel=sel, rank=rank)
 
 
+def _ss_check(who, H, W, image, depth_ref, rays_o, **per_ray):
+    """The shape rules ss_ref_rays and ss_batch share: the reference view's image and depth, one non-empty batch."""
+    if image.dim() != 3 or image.shape[0] != H or image.shape[1] != W or image.shape[2] < 3 or depth_ref.numel() != H * W:
+        raise CnerfError(f"{who}: image must be [{H}, {W}, >=3] and depth_ref [{H}, {W}]")
+    N = rays_o.shape[0]
+    if N == 0 or any(t.shape[0] != N for t in per_ray.values()):
+        raise CnerfError(f"{who}: {' / '.join(['rays_o', *per_ray])} must describe the same (non-empty) batch")
+
+
 def _ss_cfg(w2c_ref, c2w_ref, K, H, W, image, thr0, near, far, use_viewdirs, ndc, ndc_coef, flip) -> "SsWarp":
     cfg = SsWarp()
     r = cfg.ref
-    r.H, r.W, r.fx, r.fy, r.cx, r.cy = int(H), int(W), float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
-    r.c2w = _f4(c2w_ref.detach().cpu().numpy() if isinstance(c2w_ref, torch.Tensor) else c2w_ref)
+    r.H, r.W, (r.fx, r.fy, r.cx, r.cy) = int(H), int(W), _intrinsics(K)
+    r.c2w = _f4(c2w_ref)
     r.near, r.far, r.use_viewdirs, r.ndc = float(near), float(far), int(use_viewdirs), int(ndc)
     r.ndc_ax, r.ndc_ay, r.first = float(ndc_coef[0]), float(ndc_coef[1]), 0
-    cfg.w2c = _f4(w2c_ref.detach().cpu().numpy() if isinstance(w2c_ref, torch.Tensor) else w2c_ref)
+    cfg.w2c = _f4(w2c_ref)
     cfg.flip, cfg.image_ch, cfg.thr0 = int(flip), int(image.shape[2]), float(thr0)
     return cfg
 
@@ -1045,10 +1003,7 @@ def ss_batch(rays_o: Tensor, rays_d: Tensor, depth: Tensor, target_s: Tensor, w2
     target_s = _chk(target_s.reshape(-1, 3), "target_s")
     image, depth_ref, amin_global = _chk(image, "image"), _chk(depth_ref, "depth_ref"), _chk(amin_global, "amin_global")
     N, dev = rays_o.shape[0], rays_o.device
-    if image.dim() != 3 or image.shape[0] != H or image.shape[1] != W or image.shape[2] < 3 or depth_ref.numel() != H * W:
-        raise CnerfError(f"ss_batch: image must be [{H}, {W}, >=3] and depth_ref [{H}, {W}]")
-    if rays_d.shape[0] != N or depth.shape[0] != N or target_s.shape[0] != N or N == 0:
-        raise CnerfError("ss_batch: rays_o / rays_d / depth / target_s must describe the same (non-empty) batch")
+    _ss_check("ss_batch", H, W, image, depth_ref, rays_d=rays_d, depth=depth, target_s=target_s, rays_o=rays_o)
     cfg = _ss_cfg(w2c_ref, c2w_ref, K, H, W, image, thr0, near, far, use_viewdirs, ndc, ndc_coef, flip)
     rows = torch.empty(2 * N, 11 if use_viewdirs else 8, device=dev)
     target, prior, mask2 = torch.empty(2 * N, 3, device=dev), torch.empty(2 * N, device=dev), torch.empty(2 * N, device=dev)
@@ -1079,9 +1034,8 @@ def hard_mask_pair(H, W, K, c2w_tgt, w2c_ref, depth_tgt: Tensor, depth_ref: Tens
         raise CnerfError("hard_mask_pair: mask must be a contiguous uint8 tensor on the device of the depths (it is written in place)")
     nchunks = (H * W + chunk - 1) // chunk
     thr = torch.empty(nchunks, device=mask.device) if want_thr else None
-    _lib.check(_lib.load().cnerf_hard_mask_pair(H, W, float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]),
-                                                _f4(c2w_tgt), _f4(w2c_ref), _p(depth_tgt), _p(depth_ref), float(thr0),
-                                                chunk, _p(mask), _p(thr), _stream()), "cnerf_hard_mask_pair")
+    _lib.check(_lib.load().cnerf_hard_mask_pair(H, W, *_intrinsics(K), _f4(c2w_tgt), _f4(w2c_ref), _p(depth_tgt), _p(depth_ref),
+                                                float(thr0), chunk, _p(mask), _p(thr), _stream()), "cnerf_hard_mask_pair")
     return thr
 
 

@@ -949,6 +949,97 @@ def _create_nerf(args, model_cls, view_variant):
     return render_kwargs_train, render_kwargs_test, start, grad_vars, optimizer
 
 
+def _random_streams(rows, Nc, Nf, perturb, raw_noise_std, pytest, dev, global_rows):
+    """Every random stream of one render_rays call, decided in one place -> (t_rand | None, rng | None, u(), noise(level)).
+    t_rand: the jitter as a tensor (pytest; torch.rand when the in-kernel streams are off) and rng: the block of in-kernel stream
+    offsets (ops.rng_draw: jitter +0, u +1, noise +2 / +3) are taken here.  u() -> the resampling stream (None: generated inside
+    resample_k) and noise(level) -> the density noise of level 0 (coarse) / 1 (fine) or None draw where render_rays calls them — u()
+    after the coarse level, noise() once per level, coarse first — so the calls on torch's generator keep the reference's order."""
+    in_kernel = _in_kernel_rng()
+    row0 = 0 if global_rows is None else int(global_rows[0])
+    t_rand = u_drawn = rng = rng_noise = None
+    if perturb > 0.:
+        if pytest:
+            t_rand = _pytest_rows(rows, Nc, dev, global_rows)
+        elif in_kernel:
+            # no generator launch: both streams are generated where they are consumed, indexed by the GLOBAL row (a shard of a
+            # batch sees the rows the unsharded call sees without drawing the whole batch's stream)
+            rng = ops.rng_draw(dev, row0)
+        else:
+            t_rand, u_drawn = _jitter_and_u(rows, Nc, Nf, dev, global_rows)
+    if raw_noise_std > 0. and not pytest and in_kernel:
+        # the density noise of both levels: one launch on the SAME block of offsets (+2, +3), so the call still advances the
+        # generator by RNG_STRIDE; without jitter the block is reserved for the noise alone
+        rng_noise = rng if rng is not None else ops.rng_draw(dev, row0)
+    both = []
+
+    def noise(level):
+        if rng_noise is None:
+            return _density_noise((rows, Nc + Nf if level else Nc), raw_noise_std, pytest, dev, global_rows)
+        if not both:
+            both.extend(ops.density_noise(rng_noise, rows, Nc, Nc + Nf if Nf > 0 else 0, raw_noise_std, dev))
+        return both[level]
+
+    def u():
+        if rng is not None or u_drawn is not None:     # inside resample_k / drawn together with the jitter (one generator call)
+            return u_drawn
+        if perturb == 0.:                              # H:221 det = perturb == 0
+            return sample_u(rows, Nf, True, pytest, dev)
+        if pytest:
+            return _pytest_rows(rows, Nf, dev, global_rows)
+        return _rows_of_global(lambda n, c: torch.rand(n, c, device=dev), rows, Nf, global_rows)    # (perturb < 0 too: no jitter)
+    return t_rand, rng, u, noise
+
+
+def _coarse_coins_off(L):
+    """VT:959 / VT:966 with both coarse coins 0: no primary term depends on the coarse network (its colour term falls back to the
+    FINE rgb, its depth term is absent)."""
+    return L.ss_coins is not None and not (L.ss_coins[2] or (L.prior is not None and L.ss_coins[3]))
+
+
+def _composite_level(raw, z, rays, noise, white, target, coarse_of_two, below=(None,) * 6, temps=()):
+    """raw2outputs of one level under the call's loss fold (target: None, the MSE target or a checked ops.ClossSpec) ->
+    (loss, terms, (rgb, disp, acc, depth), weights, carry).  The coarse level of two: its loss term (MSE) / partial sums (ClossSpec)
+    ride in its compositing launch and come back as `carry`; the autograd node comes with the last level, which takes
+    below = (raw, z, noise, rgb, depth, carry) of that coarse level."""
+    loss = terms = carry = None
+    closs = isinstance(target, ops.ClossSpec)
+    if target is None:
+        rgb, disp, acc, weights, depth = _CompositeFn.apply(raw, z, rays, noise, white)
+    elif coarse_of_two and closs:
+        rgb, disp, acc, weights, depth, carry = ops.composite_forward_closs(raw, z, rays, noise, white, target, level=1)
+    elif coarse_of_two:
+        rgb, disp, acc, weights, depth, carry = ops.composite_forward_mse(raw, z, rays, noise, white, target)
+    else:
+        raw_c, z_c, noise_c, rgb_c, depth_c, carry_c = below
+        if closs:
+            loss, terms, rgb, disp, acc, weights, depth = _RenderClossFn.apply(raw, raw_c, z, z_c, rays, noise, noise_c, white, target,
+                                                                               rgb_c, depth_c, carry_c, *temps)
+        else:
+            loss, rgb, disp, acc, weights, depth = _RenderLossFn.apply(raw, raw_c, z, z_c, rays, noise, noise_c, white, target, rgb_c,
+                                                                       carry_c)
+    return loss, terms, (rgb, disp, acc, depth), weights, carry
+
+
+def _ray_results(last, coarse, z_std, raw, retraw, with_depth, loss=None, terms=None):
+    """render_rays' dict from (rgb, disp, acc, depth) of the last level and of the coarse level of two (None: one level)."""
+    ret = {'rgb_map': last[0], 'disp_map': last[1], 'acc_map': last[2]}
+    if loss is not None:
+        ret['loss'] = loss
+    if terms is not None:
+        ret['loss_terms'] = terms
+    if with_depth:
+        ret['depth_map'] = last[3]
+    if retraw:
+        ret['raw'] = raw
+    if coarse is not None:
+        ret['rgb0'], ret['disp0'], ret['acc0'] = coarse[:3]
+        if with_depth:
+            ret['depth0'] = coarse[3]
+        ret['z_std'] = z_std
+    return ret
+
+
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
                 _with_depth=False, _debug=False, _global_rows=None, _target=None, _live=None):
@@ -962,124 +1053,47 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     valid dummy rays whose loss weight is 0): the MLP training kernels stop at the count, which never visits the host."""
     rays = ray_batch if ray_batch.is_contiguous() else ray_batch.contiguous()
     N_rays, dev = rays.shape[0], rays.device
+    two = N_importance > 0
     if N_rays == 0:   # nothing to launch (the reference's batchify_rays raises on an empty batch; here: empty maps)
-        S = N_samples + N_importance
-        last = network_fn if (network_fine is None or N_importance <= 0) else network_fine
-        e = lambda *sh: torch.empty(*sh, device=dev)  # noqa: E731
-        ret = {'rgb_map': e(0, 3), 'disp_map': e(0), 'acc_map': e(0)}
-        if _with_depth:
-            ret['depth_map'] = e(0)
-        if retraw:
-            ret['raw'] = e(0, S, last.spec().raw_ch)
-        if N_importance > 0:
-            ret.update({'rgb0': e(0, 3), 'disp0': e(0), 'acc0': e(0), 'z_std': e(0)})
-            if _with_depth:
-                ret['depth0'] = e(0)
-        return ret
+        last = network_fn if (network_fine is None or not two) else network_fine
+        maps = lambda: tuple(torch.empty(*sh, device=dev) for sh in ((0, 3), (0,), (0,), (0,)))  # noqa: E731
+        return _ray_results(maps(), maps() if two else None, torch.empty(0, device=dev),
+                            torch.empty(0, N_samples + N_importance, last.spec().raw_ch, device=dev) if retraw else None, retraw, _with_depth)
     viewdirs = rays[:, -3:] if rays.shape[-1] > 8 else None
-    t_rand = u_drawn = rng = rng_noise = None
-    row0 = 0 if _global_rows is None else int(_global_rows[0])
-    if perturb > 0.:
-        if pytest:
-            t_rand = _pytest_rows(N_rays, N_samples, dev, _global_rows)
-        elif _in_kernel_rng():
-            # no generator launch: both streams are generated where they are consumed, indexed by the GLOBAL row (a shard of a
-            # batch sees the rows the unsharded call sees without drawing the whole batch's stream)
-            rng = ops.rng_draw(dev, row0)
-        else:
-            t_rand, u_drawn = _jitter_and_u(N_rays, N_samples, N_importance, dev, _global_rows)
-    if raw_noise_std > 0. and not pytest and _in_kernel_rng():
-        # the density noise of both levels: one launch on the SAME block of offsets (+2, +3), so the call still advances the
-        # generator by RNG_STRIDE; without jitter the block is reserved for the noise alone
-        rng_noise = rng if rng is not None else ops.rng_draw(dev, row0)
+    t_rand, rng, draw_u, draw_noise = _random_streams(N_rays, N_samples, N_importance, perturb, raw_noise_std, pytest, dev, _global_rows)
     z_vals = ops.coarse_z(rays, N_samples, t_rand, lindisp, rng=rng)
-    if N_importance > 0:
+    if two:
         _prepack_pair(network_fn, network_fine)
-    skip_c = 0
-    if (_live is not None and isinstance(_target, ops.ClossSpec) and _target.seg_row and _target.ss_coins is not None and N_importance > 0
-            and not (_target.ss_coins[2] or (_target.prior is not None and _target.ss_coins[3]))):
-        # VT:959 / VT:966 with both coarse coins 0: no term of the PRIMARY segment depends on the coarse network (its colour term falls
-        # back to the fine rgb, its depth term is absent) — the coarse level's backward covers the second segment only
-        skip_c = int(_target.seg_row)
-    raw = network_query_fn(RayPoints(rays, z_vals, _live, skip_c), viewdirs, network_fn)
-    noise_fine = None
-    if rng_noise is not None:
-        noise, noise_fine = ops.density_noise(rng_noise, N_rays, N_samples, N_samples + N_importance if N_importance > 0 else 0,
-                                              raw_noise_std, dev)
-    else:
-        noise = _density_noise((N_rays, N_samples), raw_noise_std, pytest, dev, _global_rows)
-    loss = loss_c = terms = None
-    if _target is None:
-        rgb_map, disp_map, acc_map, weights, depth_map = _CompositeFn.apply(raw, z_vals, rays, noise, bool(white_bkgd))
-    elif isinstance(_target, ops.ClossSpec):
-        _form_temps = (_target.temps or ()) if _target.forms else ()    # autograd inputs: checked() below detaches nothing, but
+    # the loss fold of the call: none (_target None), the MSE target, or the whole ConsistentNeRF step loss (ops.ClossSpec)
+    closs = isinstance(_target, ops.ClossSpec)
+    skip_c, form_temps = 0, ()
+    if closs:
+        if _live is not None and _target.seg_row and two and _coarse_coins_off(_target):
+            skip_c = int(_target.seg_row)        # the coarse level's backward covers the second segment only
+        form_temps = (_target.temps or ()) if _target.forms else ()    # autograd inputs: checked() below detaches nothing, but
         _target = _target.checked(N_rays)                              # the node must see the caller's own tensors
-        if N_importance > 0:  # coarse level of two: its partial sums ride in its compositing launch; the autograd node comes below
-            rgb_map, disp_map, acc_map, weights, depth_map, ws_c = ops.composite_forward_closs(raw, z_vals, rays, noise,
-                                                                                               bool(white_bkgd), _target, level=1)
-        else:
-            loss, terms, rgb_map, disp_map, acc_map, weights, depth_map = _RenderClossFn.apply(
-                raw, None, z_vals, None, rays, noise, None, bool(white_bkgd), _target, None, None, None, *_form_temps)
-    elif N_importance > 0:    # coarse level of two: its loss term rides in its compositing launch; the autograd node comes below
-        rgb_map, disp_map, acc_map, weights, depth_map, loss_c = ops.composite_forward_mse(raw, z_vals, rays, noise, bool(white_bkgd),
-                                                                                          _target)
-    else:
-        loss, rgb_map, disp_map, acc_map, weights, depth_map = _RenderLossFn.apply(raw, None, z_vals, None, rays, noise, None,
-                                                                                   bool(white_bkgd), _target, None, None)
-    z_coarse, noise_coarse = z_vals, noise
-    if N_importance > 0:
-        rgb_map_0, disp_map_0, acc_map_0, depth_map_0 = rgb_map, disp_map, acc_map, depth_map
-        if rng is not None:
-            u = None                                     # generated inside resample_k
-        elif u_drawn is not None:
-            u = u_drawn                                  # drawn together with the jitter above (one generator call)
-        elif _global_rows is not None and pytest and perturb != 0.:
-            u = _pytest_rows(N_rays, N_importance, dev, _global_rows)
-        elif _global_rows is not None and perturb != 0.:    # (perturb < 0: random u, no jitter was drawn — H:221 det = perturb == 0)
-            u = _rows_of_global(lambda n, c: torch.rand(n, c, device=dev), N_rays, N_importance, _global_rows)
-        else:
-            u = sample_u(N_rays, N_importance, perturb == 0., pytest, dev)
-        z_vals, z_std = ops.resample(z_vals, weights, u, rng=rng, Nf=N_importance)   # R:395-399 + R:415, no gradient (R:397)
-        run_fn = network_fn if network_fine is None else network_fine
-        raw_coarse = raw
-        raw = network_query_fn(RayPoints(rays, z_vals, _live), viewdirs, run_fn)
+    white = bool(white_bkgd)
+    raw = network_query_fn(RayPoints(rays, z_vals, _live, skip_c), viewdirs, network_fn)
+    noise = draw_noise(0)
+    loss, terms, maps, weights, carry = _composite_level(raw, z_vals, rays, noise, white, _target, two, temps=form_temps)
+    z_coarse, maps_0, z_std = z_vals, None, None
+    if two:
+        maps_0, raw_coarse, noise_coarse = maps, raw, noise
+        z_vals, z_std = ops.resample(z_coarse, weights, draw_u(), rng=rng, Nf=N_importance)   # R:395-399 + R:415, no gradient (R:397)
+        raw = network_query_fn(RayPoints(rays, z_vals, _live), viewdirs, network_fn if network_fine is None else network_fine)
         _link_levels(raw_coarse, raw)
-        noise = noise_fine if rng_noise is not None else _density_noise((N_rays, N_samples + N_importance), raw_noise_std, pytest,
-                                                                        dev, _global_rows)
-        if _target is None:
-            rgb_map, disp_map, acc_map, weights, depth_map = _CompositeFn.apply(raw, z_vals, rays, noise, bool(white_bkgd))
-        elif isinstance(_target, ops.ClossSpec):
-            rc = raw_coarse
-            if (_target.ss_coins is not None and not _target.seg_row
-                    and not (_target.ss_coins[2] or (_target.prior is not None and _target.ss_coins[3]))):
-                # VT:959 / VT:966 with both coarse coins 0: no term of this render depends on the coarse network (its colour term
-                # falls back to the FINE rgb, its depth term is absent) — as in the reference's graph, the coarse level then has no
-                # backward at all (left attached, its dgrad + wgrad would run on zero seeds: 16 % of the step for nothing).  (Not in the
-                # one-render form of the step, seg_row > 0: the second render's coarse terms always reach the coarse network.)
-                rc = raw_coarse.detach()
-            loss, terms, rgb_map, disp_map, acc_map, weights, depth_map = _RenderClossFn.apply(
-                raw, rc, z_vals, z_coarse, rays, noise, noise_coarse, bool(white_bkgd), _target, rgb_map_0, depth_map_0, ws_c,
-                *_form_temps)
-        else:
-            loss, rgb_map, disp_map, acc_map, weights, depth_map = _RenderLossFn.apply(
-                raw, raw_coarse, z_vals, z_coarse, rays, noise, noise_coarse, bool(white_bkgd), _target, rgb_map_0, loss_c)
-    ret = {'rgb_map': rgb_map, 'disp_map': disp_map, 'acc_map': acc_map}
-    if loss is not None:
-        ret['loss'] = loss
-    if terms is not None:
-        ret['loss_terms'] = terms
-    if _with_depth:
-        ret['depth_map'] = depth_map
-    if retraw:
-        ret['raw'] = raw
-    if N_importance > 0:
-        ret['rgb0'], ret['disp0'], ret['acc0'] = rgb_map_0, disp_map_0, acc_map_0
-        if _with_depth:
-            ret['depth0'] = depth_map_0
-        ret['z_std'] = z_std
+        noise = draw_noise(1)
+        # as in the reference's graph, a coarse level that no term of this render reaches has no backward at all (left attached, its
+        # dgrad + wgrad would run on zero seeds: 16 % of the step for nothing).  (Not in the one-render form of the step, seg_row > 0:
+        # the second render's coarse terms always reach the coarse network.)
+        detach = closs and not _target.seg_row and _coarse_coins_off(_target)
+        loss, terms, maps, weights, _ = _composite_level(
+            raw, z_vals, rays, noise, white, _target, False,
+            (raw_coarse.detach() if detach else raw_coarse, z_coarse, noise_coarse, maps_0[0], maps_0[3], carry), form_temps)
+    ret = _ray_results(maps, maps_0, z_std, raw, retraw, _with_depth, loss, terms)
     if _debug:
         ret['_z_coarse'], ret['_z_vals'], ret['_weights'] = z_coarse, z_vals, weights
-        if N_importance > 0:
+        if two:
             ret['_raw_coarse'] = raw_coarse
     if DEBUG:
         for k in ret:

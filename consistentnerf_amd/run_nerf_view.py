@@ -373,6 +373,13 @@ def patch_lpips(rgb, target_s, model, n_patches=4, patch_size=16):
 _TERM_NAMES = ("loss", "img_loss", "depth_loss", "patch_loss", "img_loss0", "depth_loss0", "patch_loss0")
 
 
+def _patch_terms_need_16(patch_size, ssim=False, lpips=False):
+    """V reshapes every patch of its SSIM and LPIPS terms to [1, 16, 16, 3] (V:1699): both routes of render_loss refuse another size."""
+    for on, term in ((ssim, "SSIM"), (lpips, "LPIPS")):
+        if on and int(patch_size) != 16:
+            raise ValueError(f"render_loss: the patch {term} term needs 16 x 16 patches (V:1699), got patch_size {patch_size}")
+
+
 def _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, coef, far, rgb_w, depth_w, mono, P, ps, patch_w, counts,
                        kwargs, ssim_w=0.0, ssim_patches=4, rgb_form="hardmask", depth_form="hardmask", lp_coef=0.0, temps=None,
                        lpips_w=0.0, lpips_fn=None):
@@ -381,11 +388,8 @@ def _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, coef, 
     level's monocular term).  lpips_w != 0 with lpips_fn: + V's patch LPIPS term of every level, one patch_lpips per level over the
     same patches (loss += lpips_w lpips_level, after the level's SSIM term, V:1726-1728).  rgb_form / depth_form: the other branches
     of V / VC as their own lines (render_loss's docstring); temps = (temp_rgb, temp_depth, coarse temp_rgb, coarse temp_depth)."""
-    if ssim_w != 0 and int(ps) != 16:
-        raise ValueError(f"render_loss: the patch SSIM term needs 16 x 16 patches (V:1699), got patch_size {ps}")
     with_lpips = lpips_w != 0 and lpips_fn is not None
-    if with_lpips and int(ps) != 16:
-        raise ValueError(f"render_loss: the patch LPIPS term needs 16 x 16 patches (V:1699), got patch_size {ps}")
+    _patch_terms_need_16(ps, ssim=ssim_w != 0, lpips=with_lpips)
     rgb, disp, acc, depth, extras = render(H, W, K, chunk=chunk, rays=rays, **kwargs)
     tgt = target_s.reshape(-1, 3)
     with_depth = depth_prior is not None
@@ -510,8 +514,7 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
     ssim_w, lpips_w = float(ssim_w), float(lpips_w)
     if lpips_w != 0 and lpips_fn is None:
         raise ValueError("render_loss: lpips_w != 0 needs lpips_fn (an lpips.LPIPS; consistentnerf_amd.lpips.LPIPS for the folded route)")
-    if lpips_w != 0 and int(patch_size) != 16:
-        raise ValueError(f"render_loss: the patch LPIPS term needs 16 x 16 patches (V:1699), got patch_size {patch_size}")
+    _patch_terms_need_16(patch_size, lpips=lpips_w != 0)
     if lpips_w != 0 and _ss_coins is not None:
         raise ValueError("render_loss: the in-loop consistency step (VT) has no LPIPS term; lpips_w must be 0 with _ss_coins")
     if lpips_w == 0:
@@ -528,8 +531,7 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
     sP = int(patch_num) if ssim_w != 0 else 0
     if _ss_coins is not None and ssim_w != 0:
         raise ValueError("render_loss: the in-loop consistency step (VT) has no SSIM term; ssim_w must be 0 with _ss_coins")
-    if sP > 0 and int(patch_size) != 16:
-        raise ValueError(f"render_loss: the patch SSIM term needs 16 x 16 patches (V:1699), got patch_size {patch_size}")
+    _patch_terms_need_16(patch_size, ssim=sP > 0)
     ok = ok and sP <= 8 and sP * ops.PATCH_SSIM_RAYS <= n
     lP = int(patch_num) if lpips_fn is not None else 0
     if lP > 0:      # the folded LPIPS term: the HIP network on this device, the default forms (else the lines, never without the term)
@@ -542,7 +544,8 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
                                               with_depth_loss=depth_prior is not None, coins=_ss_coins_lines(_ss_coins, depth_prior is not None),
                                               sel=mask)
             return loss, dict(loss=loss.detach(), img_loss=il.detach(), img_loss0=None if il0 is None else il0.detach()), rgb, disp, acc, depth, extras
-        spec = ops.ClossSpec(tgt, mask, depth_prior, 1.0, 0.0, 1.0, 1.0, 0.0, None, 0, ps2, None, tuple(_ss_coins))
+        spec = ops.ClossSpec(target=tgt, mask=mask, prior=depth_prior, far=1.0, coef=0.0, rgb_w=1.0, depth_w=1.0, patch_w=0.0, n=ps2,
+                             ss_coins=tuple(_ss_coins))
         rgb, disp, acc, depth, extras = render(H, W, K, chunk=chunk, rays=rays, _target=spec, **kwargs)
         loss, t = extras.pop('loss'), extras.pop('loss_terms')
         return loss, {k: t[i] for i, k in enumerate(_TERM_NAMES)}, rgb, disp, acc, depth, extras
@@ -550,10 +553,10 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
         return _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, hardmask_coef, far, rgb_w, depth_w, mono, P,
                                   patch_size, patch_w, counts, kwargs, ssim_w=ssim_w, ssim_patches=int(patch_num), rgb_form=rgb_form,
                                   depth_form=depth_form, lp_coef=lp_coef, temps=temps, lpips_w=lpips_w, lpips_fn=lpips_fn)
-    spec = ops.ClossSpec(tgt, mask, depth_prior, far, hardmask_coef, rgb_w, depth_w, patch_w, mono, P, ps2, counts, ssim_w=ssim_w,
-                         ssim_P=sP, rgb_form=RGB_FORMS.index(rgb_form), depth_form=DEPTH_FORMS.index(depth_form), lp_coef=float(lp_coef),
-                         temps=temps if forms else None, lpips_w=lpips_w if lP else 0.0, lpips_P=lP,
-                         lpips_packed=lpips_fn.packed(tgt.device) if lP else None)
+    spec = ops.ClossSpec(target=tgt, mask=mask, prior=depth_prior, far=far, coef=hardmask_coef, rgb_w=rgb_w, depth_w=depth_w, patch_w=patch_w,
+                         mono=mono, P=P, n=ps2, counts=counts, ssim_w=ssim_w, ssim_P=sP, rgb_form=RGB_FORMS.index(rgb_form),
+                         depth_form=DEPTH_FORMS.index(depth_form), lp_coef=float(lp_coef), temps=temps if forms else None,
+                         lpips_w=lpips_w if lP else 0.0, lpips_P=lP, lpips_packed=lpips_fn.packed(tgt.device) if lP else None)
     rgb, disp, acc, depth, extras = render(H, W, K, chunk=chunk, rays=rays, _target=spec, **kwargs)
     loss, t = extras.pop('loss'), extras.pop('loss_terms')
     terms = {k: t[i] for i, k in enumerate(_TERM_NAMES)}
@@ -747,7 +750,9 @@ def _ss_step_one_render(H, W, K, batch_rays, target_s, depth_cas_s, pose_ref, im
                         occlusion_threshold, with_depth_loss, coins, global_stats, group):
     """VT:899-969 as ONE render of 2N rows (ops.ss_batch + the two-segment loss tail): no host synchronisation anywhere — the second
     render's ray count M exists only in device memory (the MLP launches are sized for the capacity and stop at the device-side
-    count), so the step can be recorded as a hipGraph; 15 launches, all own kernels."""
+    count), so the step can be recorded as a hipGraph.  The loss and its backward are 12 launching C entry points (13 with density
+    noise: tests/golden/entry_sequences.json, `ss.one_render.1100`); a training step is 16 launches, all own kernels: those with the
+    merged backward's wgrad reduction as a launch of its own, + the sampling launch, the weight re-pack and Adam."""
     rays_o, rays_d = batch_rays[0], batch_rays[1]
     dev = rays_o.device
     c2w_ref, w2c_ref = _ss_pose(pose_ref)
@@ -770,8 +775,8 @@ def _ss_step_one_render(H, W, K, batch_rays, target_s, depth_cas_s, pose_ref, im
     else:
         b = ops.ss_batch(*args, flip=False)
     N = b["N"]
-    spec = ops.ClossSpec(b["target"], b["mask"], b["prior"] if with_depth_loss else None, 1.0, 0.0, 1.0, 1.0, 0.0, None, 0, 256, None,
-                         tuple(coins), N, counts3)
+    spec = ops.ClossSpec(target=b["target"], mask=b["mask"], prior=b["prior"] if with_depth_loss else None, far=1.0, coef=0.0, rgb_w=1.0,
+                         depth_w=1.0, patch_w=0.0, n=256, ss_coins=tuple(coins), seg_row=N, counts3=counts3)
     kw = {k: v for k, v in render_kwargs.items() if k not in ('near', 'far', 'ndc', 'use_viewdirs', 'c2w_staticcam', 'c2w')}
     ret = batchify_rays(b["rows"], chunk, _with_depth=True, _target=spec, _live=b["live"], **dict(kw, retraw=True))
     loss, t = ret.pop('loss'), ret.pop('loss_terms')
