@@ -216,6 +216,10 @@ SIGNATURES = {
     "cnerf_lpips_act_offset": (_i64, [_i64, _i64, _i64, _i]),
     "cnerf_lpips_fwd": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
     "cnerf_lpips_bwd": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "cnerf_depthvis_ws_bytes": (_i64, [_i64, _i64, _i64]),
+    "cnerf_depthvis": (_i, [_vp, _vp, _i64, _i64, _i64, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cnerf_eval_prep_ws_bytes": (_i64, [_i64, _i64, _i64]),
+    "cnerf_eval_prep": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -6,13 +6,18 @@
   img2psnr_mask             alky/vis_utils.py:24-42: mean over images of the PSNR of the foreground-masked MSE
   img2ssim                  alky/vis_utils.py:44-53: (SSIM, MS-SSIM) of [N, H, W, 3] images, optionally masked (the HIP kernels, ssim.py)
   write_metrics             V:2078-2087: metrics.txt
+  img2psnr                  V:2047-2048: PSNR of the mean squared error over all images
+  lky_visualize_depth       alky/vis_utils.py:88-150: the depth-map image (turbo colormap between weighted percentiles), the HIP kernel
+  save_img_u8               alky/vis_utils.py:59-65: a [0, 1] image -> 8-bit PNG (PIL, else the zlib encoder below)
   llff_poses                load_llff.py: `poses_bounds.npy` -> poses / bounds / 60-pose spiral render path / hold-out view
   pose_spherical, read_transforms   load_blender.py:30-35, 38-70, 212-214: Blender camera ring and `transforms_*.json`
 """
 import io
 import pickle
 import re
+import struct
 import zipfile
+import zlib
 
 import numpy as np
 import torch
@@ -126,6 +131,64 @@ def write_metrics(path, psnr, ssim, lpips):
         f.write(f'PSNR: {psnr}\n')
         f.write(f'SSIM: {ssim}\n')
         f.write(f'LPIPS: {lpips}')
+
+
+def img2psnr(x, y):
+    """V:2047-2048: mse2psnr(img2mse(x, y)) over all images at once -> a 0-d tensor (computed where x lives)."""
+    x, y = torch.as_tensor(x, dtype=torch.float32), torch.as_tensor(y, dtype=torch.float32)
+    mse = torch.mean((x - y.to(x.device)) ** 2)
+    return -10. * torch.log(mse) / torch.log(torch.tensor([10.], device=mse.device))[0]
+
+
+def lky_visualize_depth(x, acc, lo=None, hi=None):
+    """alky/vis_utils.py:145-150: x (the depth 1 / disp, NaN where nothing accumulated) and acc, [H, W] or [N, H, W], numpy arrays or
+    tensors -> the float image [H, W, 3] ([N, H, W, 3]), a numpy array for numpy input and a GPU tensor otherwise.  The kernel
+    (ops.depthvis) takes the disparity, so x passes through one more reciprocal here (at most an ulp of x)."""
+    from . import ops
+    if not torch.cuda.is_available():
+        raise RuntimeError("lky_visualize_depth: needs a GPU (consistentnerf_amd has no CPU path)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    as_np = not torch.is_tensor(x)
+    t = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32)  # noqa: E731
+    x, acc = t(x), t(acc)
+    single = x.dim() == 2
+    if single:
+        x, acc = x[None], acc[None]
+    img = ops.depthvis(1. / x, acc, lo=lo, hi=hi, want_u8=False)[0]
+    img = img[0] if single else img
+    return img.cpu().numpy() if as_np else img
+
+
+def png_bytes(img8):
+    """An [H, W, 3] (RGB) or [H, W] (grey) uint8 array -> the bytes of an 8-bit PNG: one zlib stream, filter 0 on every row."""
+    img8 = np.ascontiguousarray(img8)
+    if img8.dtype != np.uint8 or not (img8.ndim == 2 or (img8.ndim == 3 and img8.shape[2] == 3)) or img8.size == 0:
+        raise ValueError(f"png_bytes: [H, W] or [H, W, 3] uint8, got {img8.dtype} {img8.shape}")
+    h, w = img8.shape[:2]
+    rows = np.concatenate([np.zeros((h, 1), np.uint8), img8.reshape(h, -1)], 1).tobytes()
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+    ihdr = struct.pack(">IIBBBBB", w, h, 8, 2 if img8.ndim == 3 else 0, 0, 0, 0)
+    return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", zlib.compress(rows, 6)) + chunk(b"IEND", b"")
+
+
+def save_img_u8(img, pth, use_pil=True):
+    """alky/vis_utils.py:59-65: an image in [0, 1] -> uint8(clip(nan_to_num(img), 0, 1) * 255) as a PNG at pth (a uint8 array is
+    written as it is).  PIL where it is installed (and use_pil), else png_bytes."""
+    img = img.detach().cpu().numpy() if torch.is_tensor(img) else np.asarray(img)
+    if img.dtype != np.uint8:
+        img = (np.clip(np.nan_to_num(img), 0., 1.) * 255.).astype(np.uint8)
+    if use_pil:
+        try:
+            from PIL import Image
+        except ImportError:
+            use_pil = False
+    with open(pth, 'wb') as f:
+        if use_pil:
+            Image.fromarray(img).save(f, 'PNG')
+        else:
+            f.write(png_bytes(img))
 
 
 # ---- camera files of the two other dataset families (SURVEY §8 f-3): poses only, images stay the caller's ------------

@@ -1394,3 +1394,61 @@ def adam_step_dev(p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyp_dev: Tensor):
             raise CnerfError(f"adam_step_dev: {n} must be a contiguous fp32 GPU tensor")
     _lib.check(_lib.load().cnerf_adam_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyp_dev), _stream()),
                "cnerf_adam_step_dev")
+
+
+# ---- the test-set pass (V:2034-2087): depth-map images and the metric inputs ---------------------------------------------------------
+def _frames(t: Tensor, name: str, dims: int) -> Tensor:
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+        raise CnerfError(f"{name} must be a float32 GPU tensor (consistentnerf_amd has no CPU path), got "
+                         f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '-')}")
+    if t.dim() != dims or t.numel() == 0:
+        raise CnerfError(f"{name} must be a non-empty {dims}-d tensor, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def depthvis(disp: Tensor, acc: Tensor, lo: Optional[float] = None, hi: Optional[float] = None, want_f32: bool = True,
+             want_u8: bool = True):
+    """cnerf_depthvis: disp, acc [N, H, W] -> (img_f32 [N, H, W, 3] | None, img_u8 [N, H, W, 3] uint8 | None, bounds [N, 2]) =
+    lky_visualize_depth(1 / disp, acc, lo, hi), its save_img_u8 bytes, and the automatic (lo_auto, hi_auto) of every frame."""
+    disp, acc = _frames(disp, "disp", 3), _frames(acc, "acc", 3)
+    if disp.shape != acc.shape:
+        raise CnerfError(f"depthvis: disp and acc must have one shape, got {tuple(disp.shape)} / {tuple(acc.shape)}")
+    N, H, W = disp.shape
+    lib = _lib.load()
+    n = lib.cnerf_depthvis_ws_bytes(N, H, W)
+    if n <= 0:
+        raise CnerfError(f"depthvis: unsupported shape {tuple(disp.shape)}")
+    ws = torch.empty((n + 7) // 8, device=disp.device, dtype=torch.float64)
+    f32 = torch.empty(N, H, W, 3, device=disp.device) if want_f32 else None
+    u8 = torch.empty(N, H, W, 3, device=disp.device, dtype=torch.uint8) if want_u8 else None
+    bounds = torch.empty(N, 2, device=disp.device)
+    _lib.check(lib.cnerf_depthvis(_p(disp), _p(acc), N, H, W, float(lo or 0.), float(hi or 0.), int(lo is not None), int(hi is not None),
+                                  _p(f32), _p(u8), _p(bounds), _p(ws), _stream()), "cnerf_depthvis")
+    return f32, u8, bounds
+
+
+def eval_prep(pred: Tensor, gt: Tensor, mask: Optional[Tensor] = None, want_ssim: bool = True, want_lpips: bool = True,
+              want_sums: bool = True):
+    """cnerf_eval_prep: pred, gt [N, H, W, 3] in [0, 1], mask [N, H, W] | None -> ((ssim_pred, ssim_gt) | None, (lpips_pred, lpips_gt)
+    | None, sums [1 + 2 N] float64 | None): the [N, 3, H, W] inputs of img2ssim's and img2lpips' kernels and the PSNR partial sums
+    (include/cnerf.h)."""
+    pred, gt = _frames(pred, "pred", 4), _frames(gt, "gt", 4)
+    if pred.shape != gt.shape or pred.shape[-1] != 3:
+        raise CnerfError(f"eval_prep: pred and gt must be [N, H, W, 3] of one shape, got {tuple(pred.shape)} / {tuple(gt.shape)}")
+    N, H, W, _ = pred.shape
+    if mask is not None:
+        mask = _frames(mask, "mask", 3)
+        if mask.shape != pred.shape[:3]:
+            raise CnerfError(f"eval_prep: mask must be {tuple(pred.shape[:3])}, got {tuple(mask.shape)}")
+    lib = _lib.load()
+    n = lib.cnerf_eval_prep_ws_bytes(N, H, W)
+    if n <= 0:
+        raise CnerfError(f"eval_prep: unsupported shape {tuple(pred.shape)}")
+    new = lambda: torch.empty(N, 3, H, W, device=pred.device)  # noqa: E731
+    ssim = (new(), new()) if want_ssim else None
+    lp = (new(), new()) if want_lpips else None
+    sums = torch.empty(1 + 2 * N, device=pred.device, dtype=torch.float64) if want_sums else None
+    ws = torch.empty((n + 7) // 8, device=pred.device, dtype=torch.float64) if want_sums else None
+    _lib.check(lib.cnerf_eval_prep(_p(pred), _p(gt), _p(mask), N, H, W, _p(ssim[0] if ssim else None), _p(ssim[1] if ssim else None),
+                                   _p(lp[0] if lp else None), _p(lp[1] if lp else None), _p(sums), _p(ws), _stream()), "cnerf_eval_prep")
+    return ssim, lp, sums

@@ -1,6 +1,7 @@
 """Drop-in for the hot-path surface of the reference's run_nerf_view.py (V) — the ConsistentNeRF driver:
 
   render V:183-249 (4 maps + extras) | render_path V:252-294 (rgbs, disps, accs) | create_nerf V:297-389 |
+  the test-set pass V:2034-2087 (`evaluate_testset`: metrics.txt and the depth-map images, frames kept on the device) |
   render_rays V:441-551 | raw2outputs V:392-438 | get_rays_ref V:553 | get_ref_rays V:576 |
   get_test_label V:630 | the hard-mask precompute of train() V:994-1046 (`compute_hard_masks`) |
   the masked RGB / depth losses V:1645-1648, V:1737, V:1786-1788, V:1865 (`hardmask_losses`) |
@@ -58,6 +59,70 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
         if savedir is not None:
             _R._save_png(os.path.join(savedir, 'color_{:03d}.png'.format(i)), to8b(rgbs[-1]))
     return np.stack(rgbs, 0), np.stack(disps, 0), np.stack(accs, 0)
+
+
+def write_testset_metrics(outdir, metrics):
+    """V:2065-2087: metrics.txt holds the foreground-masked numbers where a mask was evaluated (the DTU branch), else the plain ones."""
+    from .io_formats import write_metrics
+    sfx = "_mask" if "psnr_mask" in metrics else ""
+    path = os.path.join(outdir, "metrics.txt")
+    write_metrics(path, metrics["psnr" + sfx], metrics["ssim" + sfx], metrics["lpips" + sfx])
+    return path
+
+
+def evaluate_testset(render_poses, hwf, K, chunk, render_kwargs, gt_imgs, lpips_fn, depth_mask=None, savedir=None, outdir=None,
+                     render_factor=0):
+    """The test-set pass V:2034-2087 as one call: render the poses (as render_path does, the frames staying on the device), PSNR /
+    SSIM / MS-SSIM / LPIPS against gt_imgs [N, H, W, 3] (and, with depth_mask [N, H, W] — DTU's `depths > 0` — their foreground-masked
+    forms), the depth-map images of 1 / disp.  One ops.eval_prep launch per case feeds all the metric kernels; frames cross to the host
+    once, at the end.  -> dict: psnr, ssim, msssim, lpips (floats) [+ *_mask], rgbs / disps / accs (numpy, as render_path returns
+    them), depth_vis_u8 [N, H, W, 3] uint8, depth_bounds [N, 2].  outdir: metrics.txt and depth_{ind:03d}.png; savedir: the colour
+    frames under render_path's names."""
+    from .io_formats import save_img_u8
+    from .ssim import ms_ssim, ssim
+    H, W, focal = hwf
+    if render_factor != 0:
+        H, W, focal = H // render_factor, W // render_factor, focal / render_factor
+    rgbs, disps, accs = [], [], []
+    with torch.no_grad():
+        for c2w in render_poses:
+            rgb, disp, acc, _, _ = render(H, W, K, chunk=chunk, c2w=c2w[:3, :4], **render_kwargs)
+            rgbs.append(rgb)
+            disps.append(disp)
+            accs.append(acc)
+        rgb, disp, acc = torch.stack(rgbs, 0), torch.stack(disps, 0), torch.stack(accs, 0)
+        n = rgb.shape[0]
+        gt = torch.as_tensor(gt_imgs).to(device=rgb.device, dtype=torch.float32)
+        dev = {}
+
+        def metrics_of(mask, sfx):
+            (sp, sg), (lp, lg), sums = ops.eval_prep(rgb, gt, mask)
+            dev["ssim" + sfx], dev["msssim" + sfx] = ssim(sp, sg, data_range=1), ms_ssim(sp, sg, data_range=1)
+            dev["lpips" + sfx] = lpips_fn(lg, lp).mean()
+            dev["sums" + sfx] = sums
+        metrics_of(None, "")
+        if depth_mask is not None:
+            metrics_of(torch.as_tensor(depth_mask).to(device=rgb.device, dtype=torch.float32), "_mask")
+        _, u8, bounds = ops.depthvis(disp, acc, want_f32=False)
+        # the one crossing to the host
+        out = {k: v.cpu() for k, v in dev.items()}
+        res = {"rgbs": rgb.cpu().numpy(), "disps": disp.cpu().numpy(), "accs": acc.cpu().numpy(), "depth_vis_u8": u8.cpu().numpy(),
+               "depth_bounds": bounds.cpu().numpy()}
+    for sfx in ("", "_mask") if depth_mask is not None else ("",):
+        res.update({k + sfx: float(out[k + sfx]) for k in ("ssim", "msssim", "lpips")})
+    s = out["sums"].numpy()
+    res["psnr"] = float(-10. * np.log10(s[0] / (n * H * W * 3)))                    # V:2047-2048
+    if depth_mask is not None:
+        s = out["sums_mask"].numpy()
+        res["psnr_mask"] = float(np.mean(-10. * np.log10(s[1::2] / s[2::2])))         # vis_utils.py:35-42
+    if savedir is not None:
+        for i in range(n):
+            save_img_u8(to8b(res["rgbs"][i]), os.path.join(savedir, 'color_{:03d}.png'.format(i)))
+    if outdir is not None:
+        write_testset_metrics(outdir, res)
+        for i in range(n):
+            save_img_u8(res["depth_vis_u8"][i], os.path.join(outdir, 'depth_{:03d}.png'.format(i)))
+    return res
 
 
 def create_nerf(args):

@@ -754,6 +754,28 @@ int cnerf_adam_hyper(int step, double lr, double beta1, double beta2, double eps
                      float* hyp8_host);
 int cnerf_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyp8_dev, void* stream);
 
+/* ---- the test-set pass (V:2034-2087): depth-map images and the metric inputs ------------------------------------------------- */
+/* lky_visualize_depth -> save_img_u8 (alky/vis_utils.py:59-150) for N frames [N, H, W] (H W <= 2^28) in the same launches.  The
+ * visualised value is x = 1 / disp (NaN where acc == 0), the weight acc.  bounds [N, 2] (nullable) = the weighted percentiles 0.5 /
+ * 99.5 of x under acc (np.interp on the running sum of the weights sorted by x, ties in x in pixel order, NaN last), found by a radix
+ * select with fp64 weight sums combined in a fixed order; limits lo = lo_auto - eps32 / hi = hi_auto + eps32 unless use_lo / use_hi
+ * and the passed value is not 0 (the reference's `lo or ...`); curve -log(v + eps32), normalised and clipped to [0, 1], NaN -> 0;
+ * turbo LUT at min(int(t 256), 255); matted over white with acc.  img_f32 [N, H, W, 3] (nullable) = that image, img_u8 [N, H, W, 3]
+ * (nullable) = uint8(clip(nan_to_num(img), 0, 1) * 255); at least one of the three outputs.  workspace = cnerf_depthvis_ws_bytes()
+ * BYTES, 8-byte aligned.  No float atomics (identical bits call after call), no allocation, nothing read back. */
+int64_t cnerf_depthvis_ws_bytes(int64_t N, int64_t H, int64_t W);
+int cnerf_depthvis(const float* disp, const float* acc, int64_t N, int64_t H, int64_t W, float lo, float hi, int use_lo, int use_hi,
+                   float* img_f32, uint8_t* img_u8, float* bounds, void* workspace, void* stream);
+/* pred, gt [N, H, W, 3] in [0, 1], mask [N, H, W] (nullable) -> in one pass, each output nullable (at least one):
+ * ssim_pred / ssim_gt [N, 3, H, W] = mask * x (x without a mask: vis_utils.py:44-50); lpips_pred / lpips_gt [N, 3, H, W] =
+ * (x - 0.5) * 2, then * mask + (1 - mask) with a mask (V:2055-2058, V:2073-2075), every operation rounded on its own; sums
+ * [1 + 2 N] fp64: sums[0] = the squared error over all N H W 3 values (V:2047), sums[1 + 2 n] = sum mask * mean_c (x - y)^2 and
+ * sums[2 + 2 n] = sum mask of image n (vis_utils.py:35-39; mask = 1 without one), per-workgroup partials combined in a fixed order
+ * by a second, one-wave launch.  workspace = cnerf_eval_prep_ws_bytes() BYTES, 8-byte aligned (needed with sums only). */
+int64_t cnerf_eval_prep_ws_bytes(int64_t N, int64_t H, int64_t W);
+int cnerf_eval_prep(const float* pred, const float* gt, const float* mask, int64_t N, int64_t H, int64_t W, float* ssim_pred,
+                    float* ssim_gt, float* lpips_pred, float* lpips_gt, double* sums, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
