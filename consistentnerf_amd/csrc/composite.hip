@@ -506,100 +506,41 @@ int dispatch_c(int S, F f) {
   return CNERF_E_UNSUPPORTED;
 }
 
-}  // namespace
+// ---- the host path: every entry point below fills records and goes through launch_fwd / launch_bwd.  Batch = what each starts with;
+// cam (the kernel generates the rays: cn_composite_fwd_cam) is the one variation of its check.  An empty batch passes: the plain
+// forms answer it with CNERF_OK, the folded losses refuse it themselves.
+struct Batch {
+  const float* raw; int raw_ch; const float* z; const float* rays; int ray_stride; const float* noise; int64_t B; int S; int white_bkgd;
+  bool ok(bool cam = false) const { return raw && z && (cam || (rays && ray_stride >= 6)) && B >= 0 && S > 0 && raw_ch >= 4; }
+};
+struct FwdOut { float *rgb, *disp, *acc, *depth, *weights; };
+struct BwdSeeds { const float *g_rgb, *g_disp, *g_acc, *g_depth; };   // the plain backward's upstream gradients (a folded loss: null)
 
-extern "C" int cnerf_composite_fwd(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
-                                   const float* noise, int64_t B, int S, int white_bkgd, float* rgb, float* disp,
-                                   float* acc, float* depth, float* weights, void* stream) {
-  if (!raw || !z || !rays || B < 0 || S <= 0 || raw_ch < 4 || ray_stride < 6) return CNERF_E_ARG;
-  if (B == 0) return CNERF_OK;
-  return dispatch_c(S, [&](auto c) -> int {
-    constexpr int C = decltype(c)::value;
-    hipLaunchKernelGGL((composite_fwd_k<C, WAVES>), dim3((unsigned)cn_div_up(B, WAVES)), dim3(WAVES * 64), 0,
-                       cn_stream(stream), raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, rgb, disp, acc,
-                       depth, weights, cn_no_raygen(), MseFwd{}, ClossFwd{});
+template <int WV, bool FORMS = false>
+int launch_fwd(const Batch& b, const FwdOut& o, const RayGenDev& cam, const MseFwd& m, const ClossFwd& c, hipStream_t st) {
+  if (b.B == 0) return CNERF_OK;
+  return dispatch_c(b.S, [&](auto cc) -> int {
+    constexpr int C = decltype(cc)::value;
+    hipLaunchKernelGGL((composite_fwd_k<C, WV, FORMS>), dim3((unsigned)cn_div_up(b.B, WV)), dim3(WV * 64), 0, st, b.raw, b.raw_ch, b.z,
+                       b.rays, b.ray_stride, b.noise, b.B, b.S, b.white_bkgd, o.rgb, o.disp, o.acc, o.depth, o.weights, cam, m, c);
     CN_CHECK_LAUNCH();
     return CNERF_OK;
   });
 }
 
-// compositing for the rays of a camera generated in-kernel; used by cnerf_render_fwd_cam
-int cn_composite_fwd_cam(const float* raw, int raw_ch, const float* z, const RayGenDev& cam, const float* noise, int64_t B,
-                         int S, int white_bkgd, float* rgb, float* disp, float* acc, float* depth, float* weights,
-                         hipStream_t st) {
-  if (!raw || !z || B < 0 || S <= 0 || raw_ch < 4) return CNERF_E_ARG;
-  if (B == 0) return CNERF_OK;
-  return dispatch_c(S, [&](auto c) -> int {
-    constexpr int C = decltype(c)::value;
-    hipLaunchKernelGGL((composite_fwd_k<C, WAVES>), dim3((unsigned)cn_div_up(B, WAVES)), dim3(WAVES * 64), 0, st, raw, raw_ch, z,
-                       (const float*)nullptr, 0, noise, B, S, white_bkgd, rgb, disp, acc, depth, weights, cam, MseFwd{}, ClossFwd{});
+template <bool FORMS = false>
+int launch_bwd(const Batch& b, const BwdSeeds& g, float* d_raw, const MseBwd& m, const ClossBwd& c, void* stream) {
+  if (b.B == 0) return CNERF_OK;
+  return dispatch_c(b.S, [&](auto cc) -> int {
+    constexpr int C = decltype(cc)::value;
+    hipLaunchKernelGGL((composite_bwd_k<C, FORMS>), dim3((unsigned)cn_div_up(b.B, WAVES)), dim3(WAVES * 64), 0, cn_stream(stream),
+                       b.raw, b.raw_ch, b.z, b.rays, b.ray_stride, b.noise, b.B, b.S, b.white_bkgd, g.g_rgb, g.g_disp, g.g_acc, g.g_depth,
+                       d_raw, m, c);
     CN_CHECK_LAUNCH();
     return CNERF_OK;
   });
 }
 
-extern "C" int cnerf_composite_bwd(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
-                                   const float* noise, int64_t B, int S, int white_bkgd, const float* g_rgb,
-                                   const float* g_disp, const float* g_acc, const float* g_depth, float* d_raw,
-                                   void* stream) {
-  if (!raw || !z || !rays || !d_raw || B < 0 || S <= 0 || raw_ch < 4 || ray_stride < 6) return CNERF_E_ARG;
-  if (B == 0) return CNERF_OK;
-  return dispatch_c(S, [&](auto c) -> int {
-    constexpr int C = decltype(c)::value;
-    hipLaunchKernelGGL((composite_bwd_k<C>), dim3((unsigned)cn_div_up(B, WAVES)), dim3(WAVES * 64), 0,
-                       cn_stream(stream), raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, g_rgb, g_disp,
-                       g_acc, g_depth, d_raw, MseBwd{}, ClossBwd{});
-    CN_CHECK_LAUNCH();
-    return CNERF_OK;
-  });
-}
-
-// ---- compositing with img2mse(rgb_map, target) folded in (R:769-775): see MseFwd / MseBwd above ---------------------------------
-extern "C" int64_t cnerf_composite_mse_ws_floats(int64_t B) { return B <= 0 ? 0 : 2 * cn_div_up(B, WAVES) + 2; }
-extern "C" int64_t cnerf_composite_mse_counter_words(void) { return MSE_CTR_WORDS; }
-extern "C" int64_t cnerf_composite_mse_max_rays(void) { return (int64_t)(MSE_CTR_WORDS / MSE_CTR_STRIDE - 1) * MSE_GROUP * MSE_WAVES; }
-
-extern "C" int cnerf_composite_fwd_mse(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
-                                       const float* noise, int64_t B, int S, int white_bkgd, const float* target,
-                                       const float* loss_add, float* rgb, float* disp, float* acc, float* depth, float* weights,
-                                       float* loss, float* workspace, unsigned* counter, void* stream) {
-  if (!raw || !z || !rays || !target || !rgb || !loss || !workspace || !counter || B <= 0 || S <= 0 || raw_ch < 4 ||
-      ray_stride < 6 || ((uintptr_t)workspace & 7) != 0)
-    return CNERF_E_ARG;
-  if (B > cnerf_composite_mse_max_rays()) return CNERF_E_UNSUPPORTED;
-  MseFwd m;
-  m.tgt = target; m.part = reinterpret_cast<double*>(workspace); m.counter = counter; m.loss = loss; m.loss_add = loss_add;
-  m.n = 3.0 * (double)B;
-  return dispatch_c(S, [&](auto c) -> int {
-    constexpr int C = decltype(c)::value;
-    hipLaunchKernelGGL((composite_fwd_k<C, MSE_WAVES>), dim3((unsigned)cn_div_up(B, MSE_WAVES)), dim3(MSE_WAVES * 64), 0,
-                       cn_stream(stream), raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, rgb, disp, acc, depth, weights,
-                       cn_no_raygen(), m, ClossFwd{});
-    CN_CHECK_LAUNCH();
-    return CNERF_OK;
-  });
-}
-
-extern "C" int cnerf_composite_bwd_mse(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
-                                       const float* noise, int64_t B, int S, int white_bkgd, const float* rgb, const float* target,
-                                       const float* g_loss, float* d_raw, void* stream) {
-  if (!raw || !z || !rays || !rgb || !target || !d_raw || B <= 0 || S <= 0 || raw_ch < 4 || ray_stride < 6) return CNERF_E_ARG;
-  MseBwd m;
-  m.rgb = rgb; m.tgt = target; m.g = g_loss; m.w = (float)(2.0 / (3.0 * (double)B));
-  return dispatch_c(S, [&](auto c) -> int {
-    constexpr int C = decltype(c)::value;
-    hipLaunchKernelGGL((composite_bwd_k<C>), dim3((unsigned)cn_div_up(B, WAVES)), dim3(WAVES * 64), 0, cn_stream(stream), raw, raw_ch,
-                       z, rays, ray_stride, noise, B, S, white_bkgd, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, d_raw, m, ClossBwd{});
-    CN_CHECK_LAUNCH();
-    return CNERF_OK;
-  });
-}
-
-// ---- compositing with ConsistentNeRF's masked rgb / depth losses folded in (V:1645-1865): see ClossFwd / ClossBwd above ----------
-extern "C" int64_t cnerf_closs_ws_floats(int64_t B) { return B <= 0 ? 0 : 2 * LT_MASKED_SLOTS * cn_div_up(B, MSE_WAVES); }
-
-namespace {
 // cnerf_lossform -> LossForm, or false: cn_lossform_ok's rules (common.hpp), and a softlp form without its exponent, which only
 // these launches raise to a power (with_depth: the depth form matters only next to a prior)
 bool make_form(const cnerf_lossform* F, bool with_depth, LossForm* f) {
@@ -611,85 +552,144 @@ bool make_form(const cnerf_lossform* F, bool with_depth, LossForm* f) {
   return true;
 }
 
+// The rules a folded loss adds to Batch::ok, forward and backward alike: rays to sum over, the batch's struct and its target, the
+// level's depth map and a far bound next to a prior.  FORMS: one segment only, and a form that make_form takes (-> *f).
 template <bool FORMS>
-int composite_fwd_closs_impl(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride, const float* noise,
-                             int64_t B, int S, int white_bkgd, const cnerf_closs* L, const cnerf_lossform* F, float* rgb, float* disp,
-                             float* acc, float* depth, float* weights, float* workspace, void* stream) {
-  if (!raw || !z || !rays || !L || !L->target || !rgb || !workspace || B <= 0 || S <= 0 || raw_ch < 4 || ray_stride < 6 ||
-      ((uintptr_t)workspace & 7) != 0 || (L->prior && (!depth || !(L->far > 0.f))))
-    return CNERF_E_ARG;
-  ClossFwd c;
+bool closs_ok(const Batch& b, const cnerf_closs* L, const cnerf_lossform* F, const float* depth, LossForm* f) {
+  if (!b.ok() || b.B == 0 || !L || !L->target || (L->prior && (!depth || !(L->far > 0.f)))) return false;
+  return !FORMS || (L->seg_row == 0 && make_form(F, L->prior != nullptr, f));
+}
+
+template <bool FORMS>
+int fwd_closs(const Batch& b, const cnerf_closs* L, const cnerf_lossform* F, const FwdOut& o, float* workspace, void* stream) {
+  ClossFwd c{};
+  if (!closs_ok<FORMS>(b, L, F, o.depth, &c.form) || !o.rgb || !workspace || ((uintptr_t)workspace & 7) != 0) return CNERF_E_ARG;
   c.tgt = L->target; c.mask = L->mask; c.prior = L->prior; c.far = L->far; c.part = reinterpret_cast<double*>(workspace);
-  if (FORMS && (L->seg_row != 0 || !make_form(F, L->prior != nullptr, &c.form))) return CNERF_E_ARG;
-  return dispatch_c(S, [&](auto cc) -> int {
-    constexpr int C = decltype(cc)::value;
-    hipLaunchKernelGGL((composite_fwd_k<C, MSE_WAVES, FORMS>), dim3((unsigned)cn_div_up(B, MSE_WAVES)), dim3(MSE_WAVES * 64), 0,
-                       cn_stream(stream), raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, rgb, disp, acc, depth, weights,
-                       cn_no_raygen(), MseFwd{}, c);
-    CN_CHECK_LAUNCH();
-    return CNERF_OK;
-  });
+  return launch_fwd<MSE_WAVES, FORMS>(b, o, cn_no_raygen(), MseFwd{}, c, cn_stream(stream));
+}
+
+// The seeds of a closs backward: what the four entry points pass beyond the batch, in their order.  A group of per-ray seeds covers
+// the batch's first n rays (n = 0: no such term); required: the entry point is named after the group (_ssim, _lpips).
+struct SeedGroup { const float* d; int64_t n; bool required; };
+struct ClossSeeds {
+  const cnerf_closs* L;
+  const float *rgb, *depth, *stats, *g_loss;      // the level's forward maps, the seed weights of its finish, the upstream gradient
+  float rgb_w, depth_w, patch_w;
+  SeedGroup patch;
+  float ssim_w;
+  SeedGroup ssim, lpips;
+  const cnerf_lossform* F; float coef; const float* d_temp; float* g_temp;      // _lossform only; the pair: both or neither
+};
+
+// A group's rays lie inside the batch, and a required group is there.  strict: a count comes with its seeds — the SSIM and LPIPS
+// groups; a patch count without seeds passes and runs without the patch term.
+bool group_ok(const SeedGroup& g, int64_t B, bool strict) {
+  return g.n >= 0 && g.n <= B && !(g.required && (!g.d || g.n == 0)) && !(strict && g.n > 0 && !g.d);
+}
+
+// Every argument rule of a closs backward, once (all of them CNERF_E_ARG; the sample count is the dispatcher's).  Fills *f.
+template <bool FORMS>
+bool validate(const Batch& b, const ClossSeeds& s, const float* d_raw, LossForm* f) {
+  return closs_ok<FORMS>(b, s.L, s.F, s.depth, f) && s.rgb && s.stats && d_raw && group_ok(s.patch, b.B, false) &&
+         group_ok(s.ssim, b.B, true) && group_ok(s.lpips, b.B, true) &&
+         s.lpips.n % 256 == 0 &&      // whole 16 x 16 patches: the kernel reads cnerf_lpips_bwd's NCHW gradient in place
+         (s.d_temp == nullptr) == (s.g_temp == nullptr);
+}
+
+void fill(const Batch& b, const ClossSeeds& s, ClossBwd& c) {
+  const cnerf_closs& L = *s.L;
+  c.rgb = s.rgb; c.depth = s.depth; c.tgt = L.target; c.mask = L.mask; c.prior = L.prior; c.stats = s.stats; c.g = s.g_loss;
+  c.seg_row = L.seg_row > 0 && L.seg_row < b.B ? L.seg_row : 0;
+  c.far = L.far; c.rgb_w = s.rgb_w; c.depth_w = s.depth_w; c.patch_w = s.patch_w; c.ssim_w = s.ssim_w; c.form.coef = s.coef;
+  c.patch_d = s.patch.n > 0 ? s.patch.d : nullptr; c.n_patch = s.patch.n;
+  c.ssim_d = s.ssim.n > 0 ? s.ssim.d : nullptr; c.n_ssim = s.ssim.n;
+  c.lpips_d = s.lpips.n > 0 ? s.lpips.d : nullptr; c.n_lpips = s.lpips.n;
+  c.d_temp = s.d_temp; c.g_temp = s.g_temp;
+}
+
+template <bool FORMS = false>
+int bwd_closs(const Batch& b, const ClossSeeds& s, float* d_raw, void* stream) {
+  ClossBwd c{};
+  if (!validate<FORMS>(b, s, d_raw, &c.form)) return CNERF_E_ARG;
+  fill(b, s, c);
+  return launch_bwd<FORMS>(b, {}, d_raw, MseBwd{}, c, stream);
 }
 }  // namespace
+
+extern "C" int cnerf_composite_fwd(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride, const float* noise,
+                                   int64_t B, int S, int white_bkgd, float* rgb, float* disp, float* acc, float* depth, float* weights,
+                                   void* stream) {
+  const Batch b{raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd};
+  if (!b.ok()) return CNERF_E_ARG;
+  return launch_fwd<WAVES>(b, {rgb, disp, acc, depth, weights}, cn_no_raygen(), MseFwd{}, ClossFwd{}, cn_stream(stream));
+}
+
+// compositing for the rays of a camera generated in-kernel; used by cnerf_render_fwd_cam
+int cn_composite_fwd_cam(const float* raw, int raw_ch, const float* z, const RayGenDev& cam, const float* noise, int64_t B, int S,
+                         int white_bkgd, float* rgb, float* disp, float* acc, float* depth, float* weights, hipStream_t st) {
+  const Batch b{raw, raw_ch, z, nullptr, 0, noise, B, S, white_bkgd};
+  if (!b.ok(true)) return CNERF_E_ARG;
+  return launch_fwd<WAVES>(b, {rgb, disp, acc, depth, weights}, cam, MseFwd{}, ClossFwd{}, st);
+}
+
+extern "C" int cnerf_composite_bwd(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride, const float* noise,
+                                   int64_t B, int S, int white_bkgd, const float* g_rgb, const float* g_disp, const float* g_acc,
+                                   const float* g_depth, float* d_raw, void* stream) {
+  const Batch b{raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd};
+  if (!b.ok() || !d_raw) return CNERF_E_ARG;
+  return launch_bwd(b, {g_rgb, g_disp, g_acc, g_depth}, d_raw, MseBwd{}, ClossBwd{}, stream);
+}
+
+// ---- compositing with img2mse(rgb_map, target) folded in (R:769-775): see MseFwd / MseBwd above ---------------------------------
+extern "C" int64_t cnerf_composite_mse_ws_floats(int64_t B) { return B <= 0 ? 0 : 2 * cn_div_up(B, WAVES) + 2; }
+extern "C" int64_t cnerf_composite_mse_counter_words(void) { return MSE_CTR_WORDS; }
+extern "C" int64_t cnerf_composite_mse_max_rays(void) { return (int64_t)(MSE_CTR_WORDS / MSE_CTR_STRIDE - 1) * MSE_GROUP * MSE_WAVES; }
+
+extern "C" int cnerf_composite_fwd_mse(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
+                                       const float* noise, int64_t B, int S, int white_bkgd, const float* target,
+                                       const float* loss_add, float* rgb, float* disp, float* acc, float* depth, float* weights,
+                                       float* loss, float* workspace, unsigned* counter, void* stream) {
+  const Batch b{raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd};
+  if (!b.ok() || B == 0 || !target || !rgb || !loss || !workspace || !counter || ((uintptr_t)workspace & 7) != 0) return CNERF_E_ARG;
+  if (B > cnerf_composite_mse_max_rays()) return CNERF_E_UNSUPPORTED;
+  const MseFwd m{target, reinterpret_cast<double*>(workspace), counter, loss, loss_add, 3.0 * (double)B};
+  return launch_fwd<MSE_WAVES>(b, {rgb, disp, acc, depth, weights}, cn_no_raygen(), m, ClossFwd{}, cn_stream(stream));
+}
+
+extern "C" int cnerf_composite_bwd_mse(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
+                                       const float* noise, int64_t B, int S, int white_bkgd, const float* rgb, const float* target,
+                                       const float* g_loss, float* d_raw, void* stream) {
+  const Batch b{raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd};
+  if (!b.ok() || B == 0 || !rgb || !target || !d_raw) return CNERF_E_ARG;
+  return launch_bwd(b, {}, d_raw, MseBwd{rgb, target, g_loss, (float)(2.0 / (3.0 * (double)B))}, ClossBwd{}, stream);
+}
+
+// ---- compositing with ConsistentNeRF's masked rgb / depth losses folded in (V:1645-1865): see ClossFwd / ClossBwd above ----------
+// ---- and the same with a form per kind of term (cnerf_lossform: the other live loss branches of V / VC) --------------------------
+extern "C" int64_t cnerf_closs_ws_floats(int64_t B) { return B <= 0 ? 0 : 2 * LT_MASKED_SLOTS * cn_div_up(B, MSE_WAVES); }
+extern "C" int64_t cnerf_lossform_ws_floats(int64_t B) { return B <= 0 ? 0 : 2 * CNERF_LOSSFORM_SLOTS * cn_div_up(B, MSE_WAVES); }
 
 extern "C" int cnerf_composite_fwd_closs(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
                                          const float* noise, int64_t B, int S, int white_bkgd, const cnerf_closs* L, float* rgb,
                                          float* disp, float* acc, float* depth, float* weights, float* workspace, void* stream) {
-  return composite_fwd_closs_impl<false>(raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, L, nullptr, rgb, disp, acc, depth,
-                                         weights, workspace, stream);
+  return fwd_closs<false>({raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd}, L, nullptr, {rgb, disp, acc, depth, weights},
+                          workspace, stream);
 }
-
-// ---- the same with a form per kind of term (cnerf_lossform: the other live loss branches of V / VC) ------------------------------
-extern "C" int64_t cnerf_lossform_ws_floats(int64_t B) { return B <= 0 ? 0 : 2 * CNERF_LOSSFORM_SLOTS * cn_div_up(B, MSE_WAVES); }
 
 extern "C" int cnerf_composite_fwd_lossform(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
                                             const float* noise, int64_t B, int S, int white_bkgd, const cnerf_closs* L,
                                             const cnerf_lossform* F, float* rgb, float* disp, float* acc, float* depth, float* weights,
                                             float* workspace, void* stream) {
-  return composite_fwd_closs_impl<true>(raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, L, F, rgb, disp, acc, depth,
-                                        weights, workspace, stream);
+  return fwd_closs<true>({raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd}, L, F, {rgb, disp, acc, depth, weights}, workspace,
+                         stream);
 }
-
-namespace {
-template <bool FORMS = false>
-int composite_bwd_closs_impl(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride, const float* noise,
-                             int64_t B, int S, int white_bkgd, const cnerf_closs* L, const float* rgb, const float* depth,
-                             const float* stats, const float* g_loss, float rgb_w, float depth_w, float patch_w, const float* patch_d,
-                             int64_t n_patch_rays, float ssim_w, const float* ssim_d, int64_t n_ssim_rays, float* d_raw, void* stream,
-                             const cnerf_lossform* F = nullptr, float coef = 0.f, const float* d_temp = nullptr,
-                             float* g_temp = nullptr, const float* lpips_d = nullptr, int64_t n_lpips_rays = 0) {
-  if (!raw || !z || !rays || !L || !L->target || !rgb || !stats || !d_raw || B <= 0 || S <= 0 || raw_ch < 4 || ray_stride < 6 ||
-      (L->prior && (!depth || !(L->far > 0.f))) || n_patch_rays < 0 || n_patch_rays > B || n_ssim_rays < 0 || n_ssim_rays > B ||
-      n_lpips_rays < 0 || n_lpips_rays > B || n_lpips_rays % 256 != 0)
-    return CNERF_E_ARG;
-  ClossBwd c;
-  c.lpips_d = n_lpips_rays > 0 ? lpips_d : nullptr; c.n_lpips = n_lpips_rays;
-  c.d_temp = d_temp; c.g_temp = g_temp;
-  if (FORMS && (L->seg_row != 0 || !make_form(F, L->prior != nullptr, &c.form) || (d_temp == nullptr) != (g_temp == nullptr)))
-    return CNERF_E_ARG;
-  c.form.coef = coef;
-  c.ssim_d = n_ssim_rays > 0 ? ssim_d : nullptr; c.n_ssim = n_ssim_rays; c.ssim_w = ssim_w;
-  c.rgb = rgb; c.depth = depth; c.tgt = L->target; c.mask = L->mask; c.prior = L->prior; c.stats = stats; c.g = g_loss;
-  c.seg_row = L->seg_row > 0 && L->seg_row < B ? L->seg_row : 0;
-  c.patch_d = n_patch_rays > 0 ? patch_d : nullptr; c.n_patch = n_patch_rays; c.far = L->far; c.rgb_w = rgb_w; c.depth_w = depth_w;
-  c.patch_w = patch_w;
-  return dispatch_c(S, [&](auto cc) -> int {
-    constexpr int C = decltype(cc)::value;
-    hipLaunchKernelGGL((composite_bwd_k<C, FORMS>), dim3((unsigned)cn_div_up(B, WAVES)), dim3(WAVES * 64), 0, cn_stream(stream), raw,
-                       raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, d_raw, MseBwd{}, c);
-    CN_CHECK_LAUNCH();
-    return CNERF_OK;
-  });
-}
-}  // namespace
 
 extern "C" int cnerf_composite_bwd_closs(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
                                          const float* noise, int64_t B, int S, int white_bkgd, const cnerf_closs* L, const float* rgb,
                                          const float* depth, const float* stats, const float* g_loss, float rgb_w, float depth_w,
                                          float patch_w, const float* patch_d, int64_t n_patch_rays, float* d_raw, void* stream) {
-  return composite_bwd_closs_impl(raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, L, rgb, depth, stats, g_loss, rgb_w,
-                                  depth_w, patch_w, patch_d, n_patch_rays, 0.f, nullptr, 0, d_raw, stream);
+  return bwd_closs({raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd},
+                   {L, rgb, depth, stats, g_loss, rgb_w, depth_w, patch_w, {patch_d, n_patch_rays}}, d_raw, stream);
 }
 
 extern "C" int cnerf_composite_bwd_closs_ssim(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
@@ -697,9 +697,9 @@ extern "C" int cnerf_composite_bwd_closs_ssim(const float* raw, int raw_ch, cons
                                               const float* depth, const float* stats, const float* g_loss, float rgb_w, float depth_w,
                                               float patch_w, const float* patch_d, int64_t n_patch_rays, float ssim_w, const float* ssim_d,
                                               int64_t n_ssim_rays, float* d_raw, void* stream) {
-  if (!ssim_d || n_ssim_rays <= 0) return CNERF_E_ARG;
-  return composite_bwd_closs_impl(raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, L, rgb, depth, stats, g_loss, rgb_w,
-                                  depth_w, patch_w, patch_d, n_patch_rays, ssim_w, ssim_d, n_ssim_rays, d_raw, stream);
+  return bwd_closs({raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd},
+                   {L, rgb, depth, stats, g_loss, rgb_w, depth_w, patch_w, {patch_d, n_patch_rays}, ssim_w, {ssim_d, n_ssim_rays, true}},
+                   d_raw, stream);
 }
 
 extern "C" int cnerf_composite_bwd_closs_lpips(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
@@ -708,10 +708,9 @@ extern "C" int cnerf_composite_bwd_closs_lpips(const float* raw, int raw_ch, con
                                                float patch_w, const float* patch_d, int64_t n_patch_rays, float ssim_w, const float* ssim_d,
                                                int64_t n_ssim_rays, const float* lpips_dx, int64_t n_lpips_rays, float* d_raw,
                                                void* stream) {
-  if (!lpips_dx || n_lpips_rays <= 0 || (n_ssim_rays > 0 && !ssim_d)) return CNERF_E_ARG;
-  return composite_bwd_closs_impl(raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, L, rgb, depth, stats, g_loss, rgb_w,
-                                  depth_w, patch_w, patch_d, n_patch_rays, ssim_w, ssim_d, n_ssim_rays, d_raw, stream, nullptr, 0.f,
-                                  nullptr, nullptr, lpips_dx, n_lpips_rays);
+  return bwd_closs({raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd},
+                   {L, rgb, depth, stats, g_loss, rgb_w, depth_w, patch_w, {patch_d, n_patch_rays}, ssim_w, {ssim_d, n_ssim_rays},
+                    {lpips_dx, n_lpips_rays, true}}, d_raw, stream);
 }
 
 extern "C" int cnerf_composite_bwd_lossform(const float* raw, int raw_ch, const float* z, const float* rays, int ray_stride,
@@ -720,8 +719,7 @@ extern "C" int cnerf_composite_bwd_lossform(const float* raw, int raw_ch, const 
                                             const float* g_loss, float rgb_w, float depth_w, float patch_w, float coef,
                                             const float* patch_d, int64_t n_patch_rays, float ssim_w, const float* ssim_d,
                                             int64_t n_ssim_rays, const float* d_temp2, float* g_temp2, float* d_raw, void* stream) {
-  if (n_ssim_rays > 0 && !ssim_d) return CNERF_E_ARG;
-  return composite_bwd_closs_impl<true>(raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd, L, rgb, depth, stats8, g_loss,
-                                        rgb_w, depth_w, patch_w, patch_d, n_patch_rays, ssim_w, ssim_d, n_ssim_rays, d_raw, stream, F,
-                                        coef, d_temp2, g_temp2);
+  return bwd_closs<true>({raw, raw_ch, z, rays, ray_stride, noise, B, S, white_bkgd},
+                         {L, rgb, depth, stats8, g_loss, rgb_w, depth_w, patch_w, {patch_d, n_patch_rays}, ssim_w, {ssim_d, n_ssim_rays},
+                          /* no LPIPS seeds on the forms */ {}, F, coef, d_temp2, g_temp2}, d_raw, stream);
 }

@@ -583,127 +583,123 @@ extern "C" int cnerf_patch_depth_loss(const float* depth_pred, const float* mono
   return CNERF_OK;
 }
 
+// ---- the host path of the loss tail: each of the six entry points fills a Finish and goes through finish() ----------------------
 namespace {
-struct ClossSsim {            // cnerf_closs_finish_ssim's additions (sP = 0: none)
-  int sP = 0;
-  float ssim_w = 0.f;
-  const float* rgb_last = nullptr;
-  const float* rgb_coarse = nullptr;
-  const float* target = nullptr;
-  float* ssim_d = nullptr;
-  int lP = 0;                 // cnerf_closs_finish_lpips' additions (lP = 0: none)
-  float lpips_w = 0.f;
-  const float* lpips_v = nullptr;
+struct Finish {
+  const cnerf_closs_sum* t;
+  float *terms, *stats, *patch_d;
+  struct Ssim {       // V's patch SSIM term: P patches of 16 x 16 rays = the batch's first P * 256 rays (P = 0: none)
+    int P; float w; const float *rgb_last, *rgb_coarse, *target; float* d; bool required;
+  } ssim;
+  // V's patch LPIPS term next to it: v = the [levels P] per-image values of the one batched LPIPS forward over the levels' patches
+  struct Lpips { bool on; int P; float w; const float* v; } lpips;      // (cnerf_lpips_pack_patches' order: the last level's first)
+  struct Forms { bool on; const cnerf_lossform* F[2]; float* d_temp; } forms;      // cnerf_lossform_finish: a form per level
+  int ss;             // the in-loop consistency step: 1 = its primary terms (coins), 2 = the whole step as one render (+ seg_row, counts3)
+  const int32_t* coins;
+  int64_t seg_row;
+  const float* counts3;
 };
 
-struct ClossForms {           // cnerf_lossform_finish's additions
-  const cnerf_lossform* F[2];
-  float* d_temp;
-};
-
-int closs_finish_impl(const cnerf_closs_sum* t, const int32_t* ss_coins, float* terms, float* stats, float* patch_d, void* stream,
-                      int64_t seg_row = 0, const float* counts3 = nullptr, const ClossSsim& sm = ClossSsim(),
-                      const ClossForms* fm = nullptr) {
-  if (!t || !terms || !stats || !t->ws_last || t->B <= 0 || t->P < 0 || t->P > 8 || (t->P > 0 && (t->n <= 0 || !t->mono || !t->depth_last)) ||
-      (t->P > 0 && t->ws_coarse && !t->depth_coarse) || (t->has_depth && !(t->far > 0.f)) || (int64_t)t->P * t->n > t->B ||
-      ((uintptr_t)t->ws_last & 7) != 0 || ((uintptr_t)t->ws_coarse & 7) != 0)
-    return CNERF_E_ARG;
-  ClossTail a;
-  a.part[0] = reinterpret_cast<const double*>(t->ws_last);
-  a.part[1] = reinterpret_cast<const double*>(t->ws_coarse);
-  a.nparts = (int)cn_div_up(t->B, (int64_t)CN_CLOSS_RAYS_PER_WG);
-  a.counts = t->counts; a.coef = t->coef; a.far = t->has_depth ? t->far : 1.f; a.rgb_w = t->rgb_w; a.depth_w = t->depth_w;
-  a.patch_w = t->patch_w; a.has_depth = t->has_depth;
-  a.depth[0] = t->depth_last; a.depth[1] = t->depth_coarse; a.mono = t->mono; a.P = t->P; a.n = t->n;
-  a.patch_d[0] = (patch_d && t->P > 0) ? patch_d : nullptr;
-  a.patch_d[1] = (patch_d && t->P > 0 && t->ws_coarse) ? patch_d + (int64_t)t->P * t->n : nullptr;
-  a.terms = terms; a.stats = stats;
-  a.ss = ss_coins ? (seg_row > 0 ? 2 : 1) : 0;
-  for (int k = 0; k < 4; ++k) a.coin[k] = ss_coins ? (ss_coins[k] != 0) : 0;
-  a.nparts1 = (int)(seg_row / CN_CLOSS_RAYS_PER_WG);
-  a.counts3 = counts3;
-  a.sP = sm.sP; a.ssim_w = sm.ssim_w; a.rgb[0] = sm.rgb_last; a.rgb[1] = t->ws_coarse ? sm.rgb_coarse : nullptr; a.tgt = sm.target;
-  a.ssim_d[0] = sm.ssim_d;
-  a.ssim_d[1] = (sm.ssim_d && t->ws_coarse) ? sm.ssim_d + (int64_t)sm.sP * CN_PATCH_SSIM_RAYS * 3 : nullptr;
-  a.lP = sm.lP; a.lpips_w = sm.lpips_w; a.lpips_v = sm.lpips_v;
-  if (fm) {
+// Every argument rule of the tail, once; all of them are CNERF_E_ARG.
+bool validate(const Finish& f) {
+  const cnerf_closs_sum* t = f.t;
+  if (!t || !f.terms || !f.stats || !t->ws_last || t->B <= 0 || ((uintptr_t)t->ws_last & 7) != 0 || ((uintptr_t)t->ws_coarse & 7) != 0 ||
+      (t->has_depth && !(t->far > 0.f)))
+    return false;
+  // the depth patch term: P patches of n rays inside the batch, with the monocular depths and every level's depth map
+  if (t->P < 0 || t->P > 8 || (int64_t)t->P * t->n > t->B) return false;
+  if (t->P > 0 && (t->n <= 0 || !t->mono || !t->depth_last || (t->ws_coarse && !t->depth_coarse))) return false;
+  const Finish::Ssim& s = f.ssim;
+  if (s.P < 0 || s.P > 8 || (s.required && s.P == 0)) return false;
+  if (s.P > 0 && (!s.rgb_last || !s.target || (int64_t)s.P * CN_PATCH_SSIM_RAYS > t->B || (t->ws_coarse && !s.rgb_coarse))) return false;
+  const Finish::Lpips& l = f.lpips;
+  if (l.on && (!l.v || l.P <= 0 || l.P > 8 || (int64_t)l.P * CN_PATCH_SSIM_RAYS > t->B)) return false;
+  if (f.forms.on) {
     // (no in-loop consistency segments here; a softlp / softmask normaliser is a sum of weights, which no caller all-reduces: no
     // global counts with those forms)
-    if (ss_coins || seg_row != 0 || !fm->d_temp) return CNERF_E_ARG;
+    if (f.ss || f.seg_row != 0 || !f.forms.d_temp) return false;
     for (int lv = 0; lv < (t->ws_coarse ? 2 : 1); ++lv) {
-      const cnerf_lossform* F = fm->F[lv];
-      if (!cn_lossform_ok(F, t->has_depth != 0)) return CNERF_E_ARG;
+      const cnerf_lossform* F = f.forms.F[lv];
+      if (!cn_lossform_ok(F, t->has_depth != 0)) return false;
       const bool soft = F->rgb_form != CNERF_RGB_HARDMASK || (t->has_depth && F->depth_form >= CNERF_DEPTH_SOFTLP);
-      if (soft && t->counts) return CNERF_E_ARG;
-      a.rgb_form[lv] = F->rgb_form; a.depth_form[lv] = F->depth_form; a.temp_rgb[lv] = F->temp_rgb; a.temp_depth[lv] = F->temp_depth;
+      if (soft && t->counts) return false;
     }
-    a.d_temp = fm->d_temp; a.B = (double)t->B;
-    hipLaunchKernelGGL(closs_tail_k<true>, dim3(1), dim3(T), 0, cn_stream(stream), a);
-  } else {
-    hipLaunchKernelGGL(closs_tail_k<false>, dim3(1), dim3(T), 0, cn_stream(stream), a);
   }
+  // ss: the reference's block has neither a patch term nor sharded (n1, n0).  ss == 2: ONE batch of t->B rays = [primary | warped +
+  // padding] cut at seg_row, a multiple of the 8 rays of a compositing workgroup, so that every partial belongs to one segment
+  if (f.ss && (!f.coins || t->P != 0 || t->counts)) return false;
+  return f.ss != 2 || (f.seg_row > 0 && f.seg_row < t->B && f.seg_row % CN_CLOSS_RAYS_PER_WG == 0);
+}
+
+// The kernel's arguments of a validated call: the partials' count and cut, the coarse level's slices of patch_d and ssim_d, and
+// far = 1 without a depth term.  What a term that is off would read stays null / 0.
+void fill(const Finish& f, ClossTail& a) {
+  const cnerf_closs_sum& t = *f.t;
+  const Finish::Ssim& s = f.ssim;
+  a.part[0] = reinterpret_cast<const double*>(t.ws_last);
+  a.part[1] = reinterpret_cast<const double*>(t.ws_coarse);
+  a.nparts = (int)cn_div_up(t.B, (int64_t)CN_CLOSS_RAYS_PER_WG);
+  a.nparts1 = (int)(f.seg_row / CN_CLOSS_RAYS_PER_WG);
+  a.counts = t.counts; a.counts3 = f.counts3; a.coef = t.coef; a.far = t.has_depth ? t.far : 1.f; a.has_depth = t.has_depth;
+  a.rgb_w = t.rgb_w; a.depth_w = t.depth_w; a.patch_w = t.patch_w;
+  a.depth[0] = t.depth_last; a.depth[1] = t.depth_coarse; a.mono = t.mono; a.P = t.P; a.n = t.n;
+  a.patch_d[0] = (f.patch_d && t.P > 0) ? f.patch_d : nullptr;
+  a.patch_d[1] = (a.patch_d[0] && t.ws_coarse) ? f.patch_d + (int64_t)t.P * t.n : nullptr;
+  a.terms = f.terms; a.stats = f.stats; a.ss = f.ss;
+  for (int k = 0; k < 4; ++k) a.coin[k] = f.ss ? (f.coins[k] != 0) : 0;
+  if (s.P > 0) {
+    a.sP = s.P; a.ssim_w = s.w; a.rgb[0] = s.rgb_last; a.rgb[1] = t.ws_coarse ? s.rgb_coarse : nullptr; a.tgt = s.target;
+    a.ssim_d[0] = s.d;
+    a.ssim_d[1] = (s.d && t.ws_coarse) ? s.d + (int64_t)s.P * CN_PATCH_SSIM_RAYS * 3 : nullptr;
+  }
+  a.lP = f.lpips.P; a.lpips_w = f.lpips.w; a.lpips_v = f.lpips.v;
+  for (int lv = 0; f.forms.on && lv < (t.ws_coarse ? 2 : 1); ++lv) {
+    const cnerf_lossform& F = *f.forms.F[lv];
+    a.rgb_form[lv] = F.rgb_form; a.depth_form[lv] = F.depth_form; a.temp_rgb[lv] = F.temp_rgb; a.temp_depth[lv] = F.temp_depth;
+  }
+  a.d_temp = f.forms.d_temp; a.B = (double)t.B;
+}
+
+int finish(const Finish& f, void* stream) {
+  if (!validate(f)) return CNERF_E_ARG;
+  ClossTail a{};
+  fill(f, a);
+  hipLaunchKernelGGL(f.forms.on ? closs_tail_k<true> : closs_tail_k<false>, dim3(1), dim3(T), 0, cn_stream(stream), a);
   CN_CHECK_LAUNCH();
   return CNERF_OK;
 }
 }  // namespace
 
 extern "C" int cnerf_closs_finish(const cnerf_closs_sum* t, float* terms, float* stats, float* patch_d, void* stream) {
-  return closs_finish_impl(t, nullptr, terms, stats, patch_d, stream);
+  return finish({t, terms, stats, patch_d}, stream);
 }
 
 extern "C" int cnerf_closs_finish_ss(const cnerf_closs_sum* t, const int32_t* coins4, float* terms, float* stats, void* stream) {
-  // (no patch term and no sharded counts in this mode: the reference's block has neither)
-  if (!coins4 || !t || t->P != 0 || t->counts) return CNERF_E_ARG;
-  return closs_finish_impl(t, coins4, terms, stats, nullptr, stream);
+  return finish({t, terms, stats, nullptr, {}, {}, {}, 1, coins4}, stream);
 }
 
 extern "C" int cnerf_closs_finish_ss2(const cnerf_closs_sum* t, const int32_t* coins4, int64_t seg_row, const float* counts3,
                                       float* terms12, float* stats16, void* stream) {
-  // the levels' compositing launches ran over ONE batch of t->B rays = [primary | warped + padding] cut at seg_row (a multiple of the
-  // 8 rays of a compositing workgroup, so that every partial belongs to one segment)
-  if (!coins4 || !t || t->P != 0 || t->counts || seg_row <= 0 || seg_row >= t->B || seg_row % CN_CLOSS_RAYS_PER_WG != 0) return CNERF_E_ARG;
-  return closs_finish_impl(t, coins4, terms12, stats16, nullptr, stream, seg_row, counts3);
+  return finish({t, terms12, stats16, nullptr, {}, {}, {}, 2, coins4, seg_row, counts3}, stream);
 }
 
 extern "C" int cnerf_closs_finish_ssim(const cnerf_closs_sum* t, int ssim_P, float ssim_w, const float* rgb_last, const float* rgb_coarse,
                                        const float* target, float* terms10, float* stats, float* patch_d, float* ssim_d, void* stream) {
-  // V's patch SSIM term next to the depth patch term: ssim_P patches of 16 x 16 rays = the batch's first ssim_P * 256 rays
-  if (!t || !rgb_last || !target || !terms10 || ssim_P <= 0 || ssim_P > 8 || t->B <= 0 ||
-      (int64_t)ssim_P * CN_PATCH_SSIM_RAYS > t->B || (t->ws_coarse && !rgb_coarse))
-    return CNERF_E_ARG;
-  ClossSsim sm;
-  sm.sP = ssim_P; sm.ssim_w = ssim_w; sm.rgb_last = rgb_last; sm.rgb_coarse = rgb_coarse; sm.target = target; sm.ssim_d = ssim_d;
-  return closs_finish_impl(t, nullptr, terms10, stats, patch_d, stream, 0, nullptr, sm);
+  return finish({t, terms10, stats, patch_d, {ssim_P, ssim_w, rgb_last, rgb_coarse, target, ssim_d, true}}, stream);
 }
 
 extern "C" int cnerf_closs_finish_lpips(const cnerf_closs_sum* t, int ssim_P, float ssim_w, const float* rgb_last, const float* rgb_coarse,
                                         const float* target, int lpips_P, float lpips_w, const float* lpips_v, float* terms12, float* stats,
                                         float* patch_d, float* ssim_d, void* stream) {
-  // V's patch LPIPS term next to the SSIM term (ssim_P = 0: no SSIM term): lpips_v = the [levels lpips_P] per-image values of the
-  // one batched LPIPS forward over the levels' patches (cnerf_lpips_pack_patches' order: the last level's patches first)
-  if (!t || !terms12 || !lpips_v || lpips_P <= 0 || lpips_P > 8 || t->B <= 0 || (int64_t)lpips_P * CN_PATCH_SSIM_RAYS > t->B ||
-      ssim_P < 0 || ssim_P > 8)
-    return CNERF_E_ARG;
-  ClossSsim sm;
-  if (ssim_P > 0) {
-    if (!rgb_last || !target || (int64_t)ssim_P * CN_PATCH_SSIM_RAYS > t->B || (t->ws_coarse && !rgb_coarse)) return CNERF_E_ARG;
-    sm.sP = ssim_P; sm.ssim_w = ssim_w; sm.rgb_last = rgb_last; sm.rgb_coarse = rgb_coarse; sm.target = target; sm.ssim_d = ssim_d;
-  }
-  sm.lP = lpips_P; sm.lpips_w = lpips_w; sm.lpips_v = lpips_v;
-  return closs_finish_impl(t, nullptr, terms12, stats, patch_d, stream, 0, nullptr, sm);
+  return finish({t, terms12, stats, patch_d, {ssim_P, ssim_w, rgb_last, rgb_coarse, target, ssim_d}, {true, lpips_P, lpips_w, lpips_v}},
+                stream);
 }
 
 extern "C" int cnerf_lossform_finish(const cnerf_closs_sum* t, const cnerf_lossform* F_last, const cnerf_lossform* F_coarse, int ssim_P,
                                      float ssim_w, const float* rgb_last, const float* rgb_coarse, const float* target, float* terms10,
                                      float* stats16, float* patch_d, float* ssim_d, float* d_temp4, void* stream) {
-  if (!t || !F_last || !terms10 || !stats16 || !d_temp4 || t->B <= 0 || (t->ws_coarse && !F_coarse) || ssim_P < 0 || ssim_P > 8) return CNERF_E_ARG;
-  ClossSsim sm;
-  if (ssim_P > 0) {
-    if (!rgb_last || !target || (int64_t)ssim_P * CN_PATCH_SSIM_RAYS > t->B || (t->ws_coarse && !rgb_coarse)) return CNERF_E_ARG;
-    sm.sP = ssim_P; sm.ssim_w = ssim_w; sm.rgb_last = rgb_last; sm.rgb_coarse = rgb_coarse; sm.target = target; sm.ssim_d = ssim_d;
-  }
-  const ClossForms fm = {{F_last, F_coarse}, d_temp4};
-  return closs_finish_impl(t, nullptr, terms10, stats16, patch_d, stream, 0, nullptr, sm, &fm);
+  return finish({t, terms10, stats16, patch_d, {ssim_P, ssim_w, rgb_last, rgb_coarse, target, ssim_d}, {},
+                 {true, {F_last, F_coarse}, d_temp4}}, stream);
 }
 
 // img2mse_softmask / img2mse_depth_softmask (V:50 / V:55; the `--softmask` branch of the loss, VC:1526-1528 / VC:1564-1572): every

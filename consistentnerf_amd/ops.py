@@ -44,6 +44,11 @@ def _p(t: Optional[Tensor]):
     return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
 
 
+def _addr(t: Optional[Tensor]) -> Optional[int]:
+    """Address or None: a pointer field of a ctypes struct."""
+    return None if t is None else t.data_ptr()
+
+
 def _chk(t: Optional[Tensor], name: str, dtype=torch.float32) -> Optional[Tensor]:
     if t is None:
         return None
@@ -649,12 +654,10 @@ class ClossSpec:
     def form_c(self, level: int) -> LossForm:
         """struct cnerf_lossform of a level (0 = the last / fine one, 1 = coarse)."""
         t = self.temps or (None,) * 4
-        a = lambda x: None if x is None else x.data_ptr()  # noqa: E731
-        return LossForm(int(self.rgb_form), int(self.depth_form), float(self.lp_coef), a(t[2 * level]), a(t[2 * level + 1]))
+        return LossForm(int(self.rgb_form), int(self.depth_form), float(self.lp_coef), _addr(t[2 * level]), _addr(t[2 * level + 1]))
 
     def c(self) -> Closs:
-        return Closs(self.target.data_ptr(), None if self.mask is None else self.mask.data_ptr(),
-                     None if self.prior is None else self.prior.data_ptr(), float(self.far), int(self.seg_row))
+        return Closs(self.target.data_ptr(), _addr(self.mask), _addr(self.prior), float(self.far), int(self.seg_row))
 
     def checked(self, B: int) -> "ClossSpec":
         t = _chk(self.target.reshape(-1, 3), "target")
@@ -724,9 +727,14 @@ def composite_forward_closs(raw: Tensor, z: Tensor, rays: Tensor, noise: Optiona
 
 
 class ClossFinish(NamedTuple):
-    """What the loss tail of a step leaves (closs_finish): None where the step has no such term."""
-    terms: Tensor                 # [8]; [10] with the SSIM term or a loss form; [12] with L.seg_row or the LPIPS term
-    stats: Tensor                 # per level 4 seed weights; 8 with L.seg_row ([2 segments][4]) or a loss form
+    """What the loss tail of a step leaves (closs_finish); None where the step has no such term.  The sizes per mode:
+    terms [8] = loss, then (img, depth, patch) of the last level and of the coarse one, -; [10] with the SSIM term or a loss form
+            (+ ssim_level per level); [12] with the LPIPS term (+ lpips_level per level) or L.seg_row (+ the second render's four terms)
+    stats   per level the 4 seed weights (w1, w0, wd, wd0: 0 but for a loss form) of the compositing backward; per level 8 with
+            L.seg_row ([2 segments][4]) or a loss form (+ 1 / the colour form's normaliser, 3 unused): [8] or [16] floats, both
+            levels' room whatever `levels` is"""
+    terms: Tensor
+    stats: Tensor
     patch_d: Optional[Tensor]     # [levels, P * n]
     ssim_d: Optional[Tensor]      # [levels, ssim_P * 768]
     d_temp: Optional[Tensor]      # [4] = per level (rgb_w dL_rgb / d temp_rgb, depth_w dL_depth / d temp_depth): loss forms only
@@ -761,36 +769,31 @@ def closs_finish(L: ClossSpec, B: int, ws_last: Tensor, ws_coarse: Optional[Tens
     patch_d = torch.empty(levels, L.P * L.n, device=dev) if (L.P > 0 and want_grad) else None
     ssim_d = torch.empty(levels, L.ssim_P * PATCH_SSIM_RAYS * 3, device=dev) if (L.ssim_P > 0 and want_grad) else None
     d_temp = torch.empty(4, device=dev) if L.forms else None
-    a = lambda x: None if x is None else x.data_ptr()  # noqa: E731
-    t = ClossTail(a(ws_last), a(ws_coarse), int(B), a(L.counts), L.coef, L.far, L.rgb_w, L.depth_w, L.patch_w,
-                  int(L.prior is not None), a(depth_last) if L.P > 0 else None,
-                  a(depth_coarse) if (L.P > 0 and levels == 2) else None, a(L.mono) if L.P > 0 else None, L.P, L.n)
+    t = ClossTail(_addr(ws_last), _addr(ws_coarse), int(B), _addr(L.counts), L.coef, L.far, L.rgb_w, L.depth_w, L.patch_w,
+                  int(L.prior is not None), _addr(depth_last) if L.P > 0 else None,
+                  _addr(depth_coarse) if (L.P > 0 and levels == 2) else None, _addr(L.mono) if L.P > 0 else None, L.P, L.n)
     if extra:
         rgb_last, rgb_coarse = _chk(rgb_last, "rgb"), _chk(rgb_coarse, "rgb0") if levels == 2 else None
-    lib = _lib.load()
+    # the argument groups the six entry points share, then (symbol, what follows the tail struct) by what L asks for
+    outs, grads = [_p(terms), _p(stats)], [_p(patch_d), _p(ssim_d)]
+    ssim = [int(L.ssim_P), float(L.ssim_w), _p(rgb_last), _p(rgb_coarse), _p(L.target)]
     if L.lpips_P > 0:
         if lpips_v is None or lpips_v.numel() != levels * L.lpips_P:
             raise CnerfError(f"closs_finish: the LPIPS term needs lpips_v [{levels * L.lpips_P}] (lpips_step_forward)")
-        _lib.check(lib.cnerf_closs_finish_lpips(C.byref(t), int(L.ssim_P), float(L.ssim_w), _p(rgb_last), _p(rgb_coarse), _p(L.target),
-                                                int(L.lpips_P), float(L.lpips_w), _p(_chk(lpips_v, "lpips_v")), _p(terms), _p(stats),
-                                                _p(patch_d), _p(ssim_d), _stream()), "cnerf_closs_finish_lpips")
+        lpips_v = _chk(lpips_v, "lpips_v")
+        name, args = "cnerf_closs_finish_lpips", [*ssim, int(L.lpips_P), float(L.lpips_w), _p(lpips_v), *outs, *grads]
     elif L.forms:
         f0, f1 = L.form_c(0), L.form_c(1)
-        _lib.check(lib.cnerf_lossform_finish(C.byref(t), C.byref(f0), C.byref(f1), int(L.ssim_P), float(L.ssim_w), _p(rgb_last),
-                                             _p(rgb_coarse), _p(L.target), _p(terms), _p(stats), _p(patch_d), _p(ssim_d), _p(d_temp),
-                                             _stream()), "cnerf_lossform_finish")
+        name, args = "cnerf_lossform_finish", [C.byref(f0), C.byref(f1), *ssim, *outs, *grads, _p(d_temp)]
     elif L.ssim_P > 0:
-        _lib.check(lib.cnerf_closs_finish_ssim(C.byref(t), int(L.ssim_P), float(L.ssim_w), _p(rgb_last), _p(rgb_coarse), _p(L.target),
-                                               _p(terms), _p(stats), _p(patch_d), _p(ssim_d), _stream()), "cnerf_closs_finish_ssim")
-    elif L.ss_coins is not None and L.seg_row:
-        coins = (C.c_int32 * 4)(*L.ss_coins)
-        _lib.check(lib.cnerf_closs_finish_ss2(C.byref(t), coins, int(L.seg_row), _p(L.counts3), _p(terms), _p(stats), _stream()),
-                   "cnerf_closs_finish_ss2")
+        name, args = "cnerf_closs_finish_ssim", [*ssim, *outs, *grads]
     elif L.ss_coins is not None:
         coins = (C.c_int32 * 4)(*L.ss_coins)
-        _lib.check(lib.cnerf_closs_finish_ss(C.byref(t), coins, _p(terms), _p(stats), _stream()), "cnerf_closs_finish_ss")
+        name, args = ("cnerf_closs_finish_ss2", [coins, int(L.seg_row), _p(L.counts3), *outs]) if L.seg_row else ("cnerf_closs_finish_ss",
+                                                                                                                 [coins, *outs])
     else:
-        _lib.check(lib.cnerf_closs_finish(C.byref(t), _p(terms), _p(stats), _p(patch_d), _stream()), "cnerf_closs_finish")
+        name, args = "cnerf_closs_finish", [*outs, _p(patch_d)]
+    _lib.check(getattr(_lib.load(), name)(C.byref(t), *args, _stream()), name)
     return ClossFinish(terms, stats, patch_d, ssim_d, d_temp)
 
 
@@ -812,20 +815,20 @@ def composite_backward_closs(raw, z, rays, noise, white_bkgd, L: ClossSpec, rgb,
     raw, _, _, pre, _keep = _composite_args(raw, z, rays, noise, white_bkgd)
     d_raw = torch.empty_like(raw)
     lpips_dx = _chk(lpips_dx, "lpips_dx")
-    # what the four entry points take alike (a loss form: + its struct after the batch's, + coef after the weights); stats4 = the
-    # level's 4 floats, 8 with a loss form
-    args = [*pre, *_closs_args(L, level), _p(rgb), _p(depth), _p(stats4), _p(g_loss), L.rgb_w, L.depth_w, L.patch_w,
-            *([L.coef] if L.forms else []), _p(patch_d), L.P * L.n if patch_d is not None else 0]
+    # what the four entry points take alike, then (symbol, what follows the weights); stats4 = the level's 4 floats, 8 with a loss
+    # form, which also puts its struct after the batch's (_closs_args)
+    args = [*pre, *_closs_args(L, level), _p(rgb), _p(depth), _p(stats4), _p(g_loss), L.rgb_w, L.depth_w, L.patch_w]
+    patch = [_p(patch_d), L.P * L.n if patch_d is not None else 0]
     ssim = [float(L.ssim_w), _p(ssim_d), 0 if ssim_d is None else ssim_d.numel() // 3]      # V's patch SSIM seeds
     if L.forms:
-        name, args = "cnerf_composite_bwd_lossform", args + ssim + [_p(d_temp2), _p(g_temp2)]
+        name, tail = "cnerf_composite_bwd_lossform", [L.coef, *patch, *ssim, _p(d_temp2), _p(g_temp2)]
     elif lpips_dx is not None:  # + V's patch LPIPS seeds, the level's [lpips_P, 3, 16, 16] slice of the gradient (+ the SSIM seeds)
-        name, args = "cnerf_composite_bwd_closs_lpips", args + ssim + [_p(lpips_dx), lpips_dx.shape[0] * PATCH_SSIM_RAYS]
+        name, tail = "cnerf_composite_bwd_closs_lpips", [*patch, *ssim, _p(lpips_dx), lpips_dx.shape[0] * PATCH_SSIM_RAYS]
     elif ssim_d is not None:
-        name, args = "cnerf_composite_bwd_closs_ssim", args + ssim
+        name, tail = "cnerf_composite_bwd_closs_ssim", [*patch, *ssim]
     else:
-        name = "cnerf_composite_bwd_closs"
-    _lib.check(getattr(_lib.load(), name)(*args, _p(d_raw), _stream()), name)
+        name, tail = "cnerf_composite_bwd_closs", patch
+    _lib.check(getattr(_lib.load(), name)(*args, *tail, _p(d_raw), _stream()), name)
     return d_raw
 
 

@@ -423,13 +423,12 @@ class _RenderLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, *_maps):
         raw, raw_c, z, z_c, rays, target, rgb, rgb_c = ctx.saved_tensors
-        d_raw = d_raw_c = None
+        d_raw = [None, None]
         if g_loss is not None:
-            if ctx.needs_input_grad[0]:
-                d_raw = ops.composite_backward_mse(raw, z, rays, ctx.noise, ctx.white, rgb, target, g_loss)
-            if raw_c is not None and ctx.needs_input_grad[1]:
-                d_raw_c = ops.composite_backward_mse(raw_c, z_c, rays, ctx.noise_c, ctx.white, rgb_c, target, g_loss)
-        return (d_raw, d_raw_c) + (None,) * 9
+            for lv, (r, zv, nz, c) in enumerate(((raw, z, ctx.noise, rgb), (raw_c, z_c, ctx.noise_c, rgb_c))):      # fine, then coarse
+                if r is not None and ctx.needs_input_grad[lv]:
+                    d_raw[lv] = ops.composite_backward_mse(r, zv, rays, nz, ctx.white, c, target, g_loss)
+        return tuple(d_raw) + (None,) * 9
 
 
 class _RenderClossFn(torch.autograd.Function):
@@ -468,7 +467,7 @@ class _RenderClossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, *_rest):
         raw, raw_c, z, z_c, rays, rgb, rgb_c, depth, depth_c, stats, patch_d, ssim_d, d_temp, lpips_ws = ctx.saved_tensors
-        d_raw = d_raw_c = None
+        d_raw = [None, None]
         g_temps = (None,) * ctx.n_temps
         if g_loss is not None:
             L = ctx.L
@@ -476,29 +475,26 @@ class _RenderClossFn(torch.autograd.Function):
             want_t = L.forms and any(ctx.needs_input_grad[12:])
             g_temp = torch.empty(4, device=raw.device) if want_t else None   # written by the levels' backward launches
             pair = lambda x, lv: x[2 * lv:2 * lv + 2] if want_t else None  # noqa: E731   (the level's two temperatures)
+            row = lambda x, lv: None if x is None else x[lv]  # noqa: E731                 (the level's row of a [levels, ..] tensor)
             ran = [False, False]
             lp = (None, None)
             if lpips_ws is not None and (ctx.needs_input_grad[0] or (raw_c is not None and ctx.needs_input_grad[1])):
                 dX = ops.lpips_step_backward(L, lpips_ws, 2 if raw_c is not None else 1, g_loss)
                 lp = (dX[:L.lpips_P], dX[L.lpips_P:] if raw_c is not None else None)
-            if ctx.needs_input_grad[0]:
-                d_raw = ops.composite_backward_closs(raw, z, rays, ctx.noise, ctx.white, L, rgb, depth, stats[0:w], g_loss,
-                                                     None if patch_d is None else patch_d[0], None if ssim_d is None else ssim_d[0],
-                                                     0, pair(d_temp, 0), pair(g_temp, 0), lpips_dx=lp[0])
-                ran[0] = True
-            if raw_c is not None and ctx.needs_input_grad[1]:
-                d_raw_c = ops.composite_backward_closs(raw_c, z_c, rays, ctx.noise_c, ctx.white, L, rgb_c, depth_c, stats[w:2 * w],
-                                                       g_loss, None if patch_d is None else patch_d[1],
-                                                       None if ssim_d is None else ssim_d[1], 1, pair(d_temp, 1), pair(g_temp, 1),
-                                                       lpips_dx=lp[1])
-                ran[1] = True
+            levels = ((raw, z, ctx.noise, rgb, depth), (raw_c, z_c, ctx.noise_c, rgb_c, depth_c))      # the fine level's launch first
+            for lv, (r, zv, nz, c, dp) in enumerate(levels):
+                if r is not None and ctx.needs_input_grad[lv]:
+                    d_raw[lv] = ops.composite_backward_closs(r, zv, rays, nz, ctx.white, L, c, dp, stats[lv * w:(lv + 1) * w], g_loss,
+                                                             row(patch_d, lv), row(ssim_d, lv), lv, pair(d_temp, lv), pair(g_temp, lv),
+                                                             lpips_dx=lp[lv])
+                    ran[lv] = True
             if want_t:
                 for lv in (0, 1):       # (a level whose raw takes no gradient had no launch to ride in)
                     if not ran[lv]:
                         g_temp[2 * lv:2 * lv + 2] = d_temp[2 * lv:2 * lv + 2] * g_loss
                 g_temps = tuple(g_temp[k].reshape(ctx.temp_shapes[k]) if ctx.needs_input_grad[12 + k] else None
                                 for k in range(ctx.n_temps))
-        return (d_raw, d_raw_c) + (None,) * 10 + g_temps
+        return tuple(d_raw) + (None,) * 10 + g_temps
 
 
 _ONES = {}
