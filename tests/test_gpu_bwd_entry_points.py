@@ -22,7 +22,7 @@ from test_gpu_parity import T, dev, make_model  # noqa: F401  (dev: the module's
 
 pytestmark = pytest.mark.gpu
 
-VD64, VD128, NOVD64 = (2, 64, True), (4, 128, True), (2, 64, False)
+VD64, VD128, NOVD64, VD256 = (2, 64, True), (4, 128, True), (2, 64, False), (2, 256, True)
 
 
 class _Level:
@@ -151,8 +151,13 @@ def test_bwd_live_equals_the_pair_with_first_ray_0_and_ignores_rows_outside_the_
 
 
 @pytest.mark.parametrize("accumulate", [False, True])
-@pytest.mark.parametrize("M0,M1", [(33, 128), (300, 130)])
-def test_bf16x3_pair_forms_equal_two_single_calls(dev, M0, M1, accumulate):
-    lv, sh = [_level(dev, VD128, 71, M0), _level(dev, VD128, 72, M1)], [(M0, 1), (M1, 1)]
+@pytest.mark.parametrize("arch0,arch1,M0,M1", [(VD128, VD128, 33, 128), (VD128, VD128, 300, 130),
+                                               # W = 256: the only width whose wgrad plan has wide jobs, i.e. where the bf16x3 body of
+                                               # wgrad_mixed_k runs (csrc/wgrad.hip add_net_jobs) — as one merged dgrad grid, and as
+                                               # two dgrad launches behind one wgrad grid (architectures differ)
+                                               (VD256, VD256, 129, 33), (VD256, VD128, 129, 33)],
+                         ids=["33-128", "300-130", "D2W256-D2W256-129-33", "D2W256-D4W128-129-33"])
+def test_bf16x3_pair_forms_equal_two_single_calls(dev, arch0, arch1, M0, M1, accumulate):
+    lv, sh = [_level(dev, arch0, 71, M0), _level(dev, arch1, 72, M1)], [(M0, 1), (M1, 1)]
     pair = _backward(lv, sh, True, accumulate, bf=True)
     _same(pair, [_backward([lv[i]], [sh[i]], True, accumulate, bf=True)[0] for i in range(2)])

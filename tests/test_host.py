@@ -888,3 +888,34 @@ def test_packed_weight_cache_protocol(monkeypatch):
     for pair in ((None, a), (a, None), (a, a), (a, object()), (a, b)):
         R._prepack_pair(*pair)
     assert "_cnerf_packed" not in a.__dict__ and "_cnerf_packed" not in b.__dict__
+
+
+@pytest.mark.parametrize("D,W", [(3, 128), (6, 256)])
+def test_bf16x3_float64_replay_equals_autograd(D, W):
+    """The float64 references of tests/test_gpu_bf16x3_training.py are known good before they judge a kernel: replay64 (the backward
+    from stashed activations) against torch autograd through forward64 in float64, at M = 33 — (3, 128), and (6, 256) for the skip
+    layer's column split — to 1e-12 of each tensor's max; forward64 against the oracle's forward on the same float64 weights."""
+    import _inputs as I
+    from oracle import nerf_oracle as O
+    from test_gpu_bf16x3_training import forward64, replay64
+    M = 33
+    rs = np.random.RandomState(5)
+    pts = torch.from_numpy(rs.uniform(-3, 3, size=(M, 3)))
+    dirs = rs.normal(size=(M, 3))
+    dirs = torch.from_numpy(dirs / np.linalg.norm(dirs, axis=-1, keepdims=True))
+    G = torch.from_numpy(rs.normal(size=(M, 4)))
+    sd = {k: torch.from_numpy(v).double().requires_grad_(True) for k, v in I.nerf_state_dict(D, W, 10, 4, 5, True, 11).items()}
+    x, xd = O.embed(pts, 10), O.embed(dirs, 4)
+    raw, acts = forward64(sd, x, xd, D)
+    want = O.mlp_forward(sd, x, xd, O.NetCfg(D, W, use_viewdirs=True, output_ch=5))
+    assert float((raw - want).detach().abs().max()) <= 1e-12 * float(want.detach().abs().max())
+    (raw * G).sum().backward()
+    blk = {k: v.detach() for k, v in acts.items()}
+    blk["enc"] = torch.cat([x, torch.zeros(M, 1, dtype=torch.float64)], 1)
+    blk["denc"] = torch.cat([xd, torch.zeros(M, 5, dtype=torch.float64)], 1)
+    ref = replay64({k: v.detach() for k, v in sd.items()}, blk, G, D, W)
+    assert sorted(ref) == sorted(k for k in sd if "." in k)
+    for k, r in ref.items():
+        g = sd[k].grad
+        assert float(g.abs().max()) > 0, k
+        assert float((r.reshape(g.shape) - g).abs().max()) <= 1e-12 * float(g.abs().max()), k
