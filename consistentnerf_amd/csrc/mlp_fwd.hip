@@ -15,6 +15,7 @@
 // MFMA-bound by construction: 593 920 MAC per point at D=8/W=256 incl. K padding.
 #include "mlp_common.hpp"
 #include "encode.hpp"
+#include "mlp_fwd_host.hpp"
 #include "raygen.hpp"
 
 namespace {
@@ -261,29 +262,67 @@ __global__ __launch_bounds__(64) void mlp_fwd_k(FwdArgs args_by_value) {
 
 template <int NT>
 int launch(const FwdArgs& a, hipStream_t st) {
-  const unsigned grid = (unsigned)cn_div_up(a.M, 32);
   if (a.stash != nullptr) {
     const hipError_t e = cn_zero_padding_tile_row(a.stash, a.M, a.Mp, a.g.s_rows, st);
     if (e != hipSuccess) return (int)e;
-    if (a.live != nullptr) {
-      if (a.g.viewdirs) hipLaunchKernelGGL((mlp_fwd_k<NT, true, true, true>), dim3(grid), dim3(64), 0, st, a);
-      else hipLaunchKernelGGL((mlp_fwd_k<NT, false, true, true>), dim3(grid), dim3(64), 0, st, a);
-    } else if (a.g.viewdirs) hipLaunchKernelGGL((mlp_fwd_k<NT, true, true>), dim3(grid), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((mlp_fwd_k<NT, false, true>), dim3(grid), dim3(64), 0, st, a);
-  } else {
-    if (a.live != nullptr) return CNERF_E_UNSUPPORTED;      // (the device-side row count is a training-step feature)
-    if (a.g.viewdirs) hipLaunchKernelGGL((mlp_fwd_k<NT, true, false>), dim3(grid), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((mlp_fwd_k<NT, false, false>), dim3(grid), dim3(64), 0, st, a);
   }
+  // <NT, VD, TRAIN, LIVE>: a live count comes with a stash (validate: the device-side row count is a training-step feature)
+  using K = void (*)(FwdArgs);
+  const bool vd = a.g.viewdirs;
+  const K k = a.live    ? (vd ? K(mlp_fwd_k<NT, true, true, true>) : K(mlp_fwd_k<NT, false, true, true>))
+              : a.stash ? (vd ? K(mlp_fwd_k<NT, true, true>) : K(mlp_fwd_k<NT, false, true>))
+                        : (vd ? K(mlp_fwd_k<NT, true, false>) : K(mlp_fwd_k<NT, false, false>));
+  hipLaunchKernelGGL(k, dim3((unsigned)cn_div_up(a.M, 32)), dim3(64), 0, st, a);
   CN_CHECK_LAUNCH();
   return CNERF_OK;
 }
 
-int dispatch(const FwdArgs& a, void* stream) {
+// ---- the host path: every entry point below fills a Call and goes through run(): validate -> fill -> launch.
+enum Form { ROWS, LIVE, CAMERA, EMBEDDED };
+struct Call {
+  Form form;
+  const cnerf_net* net;
+  const float* packed;
+  CnFwdSrc src;               // ROWS: points + dirs or ray rows + stride; LIVE: ray rows; CAMERA: z only; EMBEDDED: nothing
+  const RayGenDev* cam;       // CAMERA: the rays are generated in the kernel
+  const float* emb;           // EMBEDDED: [B, in_ch + dir_ch], S = 1
+  int64_t B;
+  int S;
+  float* raw;
+  float* stash;               // training (LIVE: required)
+  const int32_t* live_rays;   // LIVE
+};
+
+// Geometry first (-2 wins over -1), then every argument rule; an empty batch is held to all of them (run() answers it after this).
+int validate(const Call& c, NetGeom* g) {
+  const int rc = cn_make_geom(c.net, g);
+  if (rc) return rc;
+  if (!c.packed || !c.raw || c.B < 0 || c.S <= 0) return CNERF_E_ARG;
+  switch (c.form) {
+    case EMBEDDED: return c.emb ? CNERF_OK : CNERF_E_ARG;
+    case CAMERA: return c.src.z && (!g->viewdirs || c.cam->vd) ? CNERF_OK : CNERF_E_ARG;
+    case LIVE:   // whole 32-point tiles are live or dead: mlp_fwd_k; the plain form takes any S > 0
+      if (!c.stash || !c.live_rays || c.S % 32 != 0) return CNERF_E_ARG;
+      [[fallthrough]];
+    case ROWS: return c.src.points_ok() && (!g->viewdirs || c.src.dirs_ok()) ? CNERF_OK : CNERF_E_ARG;
+  }
+  return CNERF_E_ARG;
+}
+
+int run(const Call& c, hipStream_t st) {
+  FwdArgs a;
+  const int rc = validate(c, &a.g);
+  if (rc) return rc;
+  if (c.B == 0) return CNERF_OK;
+  a.packed = c.packed; a.pts = c.src.pts; a.rays = c.src.rays; a.dirs = c.src.dirs; a.z = c.src.z; a.emb = c.emb;
+  a.raw = c.raw; a.stash = c.stash;
+  a.M = c.B * c.S; a.Mp = cn_round_up(a.M, 32); a.S = c.S; a.rs = c.src.rs;
+  a.cam = c.cam ? *c.cam : cn_no_raygen();
+  a.live = c.live_rays;
   switch (a.g.NT) {
-    case 2: return launch<2>(a, cn_stream(stream));
-    case 4: return launch<4>(a, cn_stream(stream));
-    case 8: return launch<8>(a, cn_stream(stream));
+    case 2: return launch<2>(a, st);
+    case 4: return launch<4>(a, st);
+    case 8: return launch<8>(a, st);
   }
   return CNERF_E_UNSUPPORTED;
 }
@@ -297,65 +336,23 @@ CN_TIMING_ACCESSOR(cnerf_debug_timing)
 extern "C" int cnerf_mlp_fwd(const cnerf_net* net, const float* packed, const float* pts, const float* rays,
                              int ray_stride, const float* dirs, const float* z, int64_t B, int S, float* raw,
                              float* stash, void* stream) {
-  FwdArgs a;
-  int rc = cn_make_geom(net, &a.g);
-  if (rc) return rc;
-  if (!packed || !raw || B < 0 || S <= 0) return CNERF_E_ARG;
-  if (!pts && (!rays || !z || ray_stride < 8)) return CNERF_E_ARG;
-  if (a.g.viewdirs && !dirs && (!rays || ray_stride < 11)) return CNERF_E_ARG;
-  if (B == 0) return CNERF_OK;
-  a.packed = packed; a.pts = pts; a.rays = rays; a.dirs = dirs; a.z = z; a.emb = nullptr; a.raw = raw;
-  a.stash = stash;
-  a.M = B * S; a.Mp = cn_round_up(a.M, 32); a.S = S; a.rs = ray_stride;
-  a.cam = cn_no_raygen();
-  a.live = nullptr;
-  return dispatch(a, stream);
+  return run({ROWS, net, packed, {pts, rays, ray_stride, dirs, z}, nullptr, nullptr, B, S, raw, stash, nullptr}, cn_stream(stream));
 }
 
 // cnerf_mlp_fwd on a batch padded to a fixed capacity of B rays whose LIVE row count sits in device memory (include/cnerf.h)
 extern "C" int cnerf_mlp_fwd_live(const cnerf_net* net, const float* packed, const float* rays, int ray_stride, const float* z,
                                   int64_t B, int S, float* raw, float* stash, const int32_t* live_rays, void* stream) {
-  FwdArgs a;
-  int rc = cn_make_geom(net, &a.g);
-  if (rc) return rc;
-  if (!packed || !raw || !rays || !z || !stash || !live_rays || B < 0 || S <= 0 || S % 32 != 0 || ray_stride < 8) return CNERF_E_ARG;
-  if (a.g.viewdirs && ray_stride < 11) return CNERF_E_ARG;
-  if (B == 0) return CNERF_OK;
-  a.packed = packed; a.pts = nullptr; a.rays = rays; a.dirs = nullptr; a.z = z; a.emb = nullptr; a.raw = raw;
-  a.stash = stash;
-  a.M = B * S; a.Mp = cn_round_up(a.M, 32); a.S = S; a.rs = ray_stride;
-  a.cam = cn_no_raygen();
-  a.live = live_rays;
-  return dispatch(a, stream);
+  return run({LIVE, net, packed, {nullptr, rays, ray_stride, nullptr, z}, nullptr, nullptr, B, S, raw, stash, live_rays},
+             cn_stream(stream));
 }
 
 // the fused encoding + MLP on the rays of a camera generated in-kernel (inference); used by cnerf_render_fwd_cam
 int cn_mlp_fwd_cam(const cnerf_net* net, const float* packed, const RayGenDev& cam, const float* z, int64_t B, int S,
-                   float* raw, void* stream) {
-  FwdArgs a;
-  int rc = cn_make_geom(net, &a.g);
-  if (rc) return rc;
-  if (!packed || !raw || !z || B < 0 || S <= 0 || (a.g.viewdirs && !cam.vd)) return CNERF_E_ARG;
-  if (B == 0) return CNERF_OK;
-  a.packed = packed; a.pts = nullptr; a.rays = nullptr; a.dirs = nullptr; a.z = z; a.emb = nullptr; a.raw = raw;
-  a.stash = nullptr;
-  a.M = B * S; a.Mp = cn_round_up(a.M, 32); a.S = S; a.rs = 0;
-  a.cam = cam;
-  a.live = nullptr;
-  return dispatch(a, stream);
+                   float* raw, hipStream_t st) {
+  return run({CAMERA, net, packed, {nullptr, nullptr, 0, nullptr, z}, &cam, nullptr, B, S, raw, nullptr, nullptr}, st);
 }
 
 extern "C" int cnerf_mlp_fwd_embedded(const cnerf_net* net, const float* packed, const float* x_embedded, int64_t M,
                                       float* raw, float* stash, void* stream) {
-  FwdArgs a;
-  int rc = cn_make_geom(net, &a.g);
-  if (rc) return rc;
-  if (!packed || !x_embedded || !raw || M < 0) return CNERF_E_ARG;
-  if (M == 0) return CNERF_OK;
-  a.packed = packed; a.pts = nullptr; a.rays = nullptr; a.dirs = nullptr; a.z = nullptr; a.emb = x_embedded;
-  a.raw = raw; a.stash = stash;
-  a.M = M; a.Mp = cn_round_up(M, 32); a.S = 1; a.rs = 0;
-  a.cam = cn_no_raygen();
-  a.live = nullptr;
-  return dispatch(a, stream);
+  return run({EMBEDDED, net, packed, {}, nullptr, x_embedded, M, 1, raw, stash, nullptr}, cn_stream(stream));
 }

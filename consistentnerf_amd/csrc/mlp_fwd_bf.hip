@@ -44,6 +44,7 @@
 
 #include "encode.hpp"
 #include "mlp_common.hpp"
+#include "mlp_fwd_host.hpp"
 #include "raygen.hpp"
 
 #include "mlp_bf_common.hpp"
@@ -497,40 +498,66 @@ int launch_bfs(const BfArgs& a, hipStream_t st) {
   return CNERF_OK;
 }
 
-template <int NT>
-int launch_bf(const BfArgs& a, int NP, int fmt, hipStream_t st) {
-  // shared-panel kernel by default; the per-wave one on request (CNERF_BF_PERWAVE=1: A/B measurements) or when the
-  // encodings are not the 64- / 32-channel tiles its unrolled K-steps assume
-  const char* e = getenv("CNERF_BF_PERWAVE");
-  if (a.stash != nullptr) {   // training: the shared-panel kernel at three planes (the fp32-equivalent arithmetic) only
-    if (NP != 3 || fmt != PL_BF16 || a.g.in_chp != 64 || a.g.dir_chp != 32) return CNERF_E_UNSUPPORTED;
-    return launch_bfs<NT, 3, true>(a, st);
-  }
-  const bool shared = !(e && e[0] == '1') && a.g.in_chp == 64 && a.g.dir_chp == 32;
-  if (fmt == PL_F16) {        // two fp16 planes: the same choice between the two kernels
-    if (NP != 2) return CNERF_E_ARG;
-    if (shared) return launch_bfs<NT, CNERF_PLANES_FP16X2, false>(a, st);
-    hipLaunchKernelGGL((mlp_fwd_bf_k<NT, CNERF_PLANES_FP16X2>), dim3((unsigned)cn_div_up(a.M, 32)), dim3(64), 0, st, a);
-    CN_CHECK_LAUNCH();
-    return CNERF_OK;
-  }
-  if (shared) {
-    switch (NP) {
-      case 1: return launch_bfs<NT, 1, false>(a, st);
-      case 2: return launch_bfs<NT, 2, false>(a, st);
-      case 3: return launch_bfs<NT, 3, false>(a, st);
-      default: return CNERF_E_ARG;
-    }
-  }
-  const unsigned grid = (unsigned)cn_div_up(a.M, 32);
-  switch (NP) {
-    case 1: hipLaunchKernelGGL((mlp_fwd_bf_k<NT, 1>), dim3(grid), dim3(64), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((mlp_fwd_bf_k<NT, 2>), dim3(grid), dim3(64), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((mlp_fwd_bf_k<NT, 3>), dim3(grid), dim3(64), 0, st, a); break;
-    default: return CNERF_E_ARG;
-  }
+// One plane mode on the kernel chosen in launch_bf
+template <int NT, int MODE>
+int launch_mode(const BfArgs& a, bool shared, hipStream_t st) {
+  if (shared) return launch_bfs<NT, MODE, false>(a, st);
+  hipLaunchKernelGGL((mlp_fwd_bf_k<NT, MODE>), dim3((unsigned)cn_div_up(a.M, 32)), dim3(64), 0, st, a);
   CN_CHECK_LAUNCH();
   return CNERF_OK;
+}
+
+template <int NT>
+int launch_bf(const BfArgs& a, int planes, hipStream_t st) {
+  // shared-panel kernel by default; the per-wave one on request (CNERF_BF_PERWAVE=1: A/B measurements) or when the
+  // encodings are not the 64- / 32-channel tiles its unrolled K-steps assume.  Training (three planes, the fp32-equivalent
+  // arithmetic: run()) exists on the shared-panel kernel only.
+  const char* e = getenv("CNERF_BF_PERWAVE");
+  const bool tiles = a.g.in_chp == 64 && a.g.dir_chp == 32;
+  if (a.stash != nullptr) return tiles ? launch_bfs<NT, 3, true>(a, st) : CNERF_E_UNSUPPORTED;
+  const bool shared = tiles && !(e && e[0] == '1');
+  switch (planes) {
+    case 1: return launch_mode<NT, 1>(a, shared, st);
+    case 2: return launch_mode<NT, 2>(a, shared, st);
+    case 3: return launch_mode<NT, 3>(a, shared, st);
+    case CNERF_PLANES_FP16X2: return launch_mode<NT, CNERF_PLANES_FP16X2>(a, shared, st);
+  }
+  return CNERF_E_ARG;
+}
+
+// ---- the host path of the two forward entry points: validate -> fill -> launch.  Training is planes = 3 plus a required stash.
+struct Call {
+  const cnerf_net* net;
+  const void* packed_bf;
+  int planes;
+  CnFwdSrc src;
+  int64_t B;
+  int S;
+  float* raw;
+  float* stash;
+  bool train;
+};
+
+int run(const Call& c, void* stream) {
+  BfArgs a;
+  int rc = cn_make_geom(c.net, &a.g);
+  if (rc) return rc;
+  int NP, fmt;
+  if (!bf_mode(c.planes, &NP, &fmt)) return CNERF_E_UNSUPPORTED;
+  if ((rc = make_bf_geom(a.g, NP, &a.b))) return rc;
+  if (!c.packed_bf || !c.raw || (c.train && !c.stash) || c.B < 0 || c.S <= 0) return CNERF_E_ARG;
+  // (view directions are asked for whatever the network says: make_bf_geom has refused a network without a view branch)
+  if (!c.src.points_ok() || !c.src.dirs_ok()) return CNERF_E_ARG;
+  if (c.B == 0) return CNERF_OK;
+  a.pk = static_cast<const unsigned char*>(c.packed_bf);
+  a.pts = c.src.pts; a.rays = c.src.rays; a.dirs = c.src.dirs; a.z = c.src.z; a.raw = c.raw; a.stash = c.stash;
+  a.M = c.B * c.S; a.S = c.S; a.rs = c.src.rs;
+  a.cam = cn_no_raygen();
+  switch (a.g.NT) {
+    case 4: return launch_bf<4>(a, c.planes, cn_stream(stream));
+    case 8: return launch_bf<8>(a, c.planes, cn_stream(stream));
+  }
+  return CNERF_E_UNSUPPORTED;
 }
 
 }  // namespace
@@ -606,45 +633,11 @@ extern "C" int cnerf_pack_weights_bf(const cnerf_net* net, const cnerf_ptrs* par
 extern "C" int cnerf_mlp_fwd_bf(const cnerf_net* net, const void* packed_bf, int planes, const float* pts,
                                 const float* rays, int ray_stride, const float* dirs, const float* z, int64_t B, int S,
                                 float* raw, void* stream) {
-  BfArgs a;
-  int rc = cn_make_geom(net, &a.g);
-  if (rc) return rc;
-  int NP, fmt;
-  if (!bf_mode(planes, &NP, &fmt)) return CNERF_E_UNSUPPORTED;
-  if ((rc = make_bf_geom(a.g, NP, &a.b))) return rc;
-  if (!packed_bf || !raw || B < 0 || S <= 0) return CNERF_E_ARG;
-  if (!pts && (!rays || !z || ray_stride < 8)) return CNERF_E_ARG;
-  if (!dirs && (!rays || ray_stride < 11)) return CNERF_E_ARG;
-  if (B == 0) return CNERF_OK;
-  a.pk = static_cast<const unsigned char*>(packed_bf);
-  a.pts = pts; a.rays = rays; a.dirs = dirs; a.z = z; a.raw = raw; a.stash = nullptr;
-  a.M = B * S; a.S = S; a.rs = ray_stride;
-  a.cam = cn_no_raygen();
-  switch (a.g.NT) {
-    case 4: return launch_bf<4>(a, NP, fmt, cn_stream(stream));
-    case 8: return launch_bf<8>(a, NP, fmt, cn_stream(stream));
-  }
-  return CNERF_E_UNSUPPORTED;
+  return run({net, packed_bf, planes, {pts, rays, ray_stride, dirs, z}, B, S, raw, nullptr, false}, stream);
 }
 
 extern "C" int cnerf_mlp_fwd_bf_train(const cnerf_net* net, const void* packed_bf, const float* pts, const float* rays,
                                       int ray_stride, const float* dirs, const float* z, int64_t B, int S, float* raw,
                                       float* stash, void* stream) {
-  BfArgs a;
-  int rc = cn_make_geom(net, &a.g);
-  if (rc) return rc;
-  if ((rc = make_bf_geom(a.g, 3, &a.b))) return rc;
-  if (!packed_bf || !raw || !stash || B < 0 || S <= 0) return CNERF_E_ARG;
-  if (!pts && (!rays || !z || ray_stride < 8)) return CNERF_E_ARG;
-  if (!dirs && (!rays || ray_stride < 11)) return CNERF_E_ARG;
-  if (B == 0) return CNERF_OK;
-  a.pk = static_cast<const unsigned char*>(packed_bf);
-  a.pts = pts; a.rays = rays; a.dirs = dirs; a.z = z; a.raw = raw; a.stash = stash;
-  a.M = B * S; a.S = S; a.rs = ray_stride;
-  a.cam = cn_no_raygen();
-  switch (a.g.NT) {
-    case 4: return launch_bf<4>(a, 3, PL_BF16, cn_stream(stream));
-    case 8: return launch_bf<8>(a, 3, PL_BF16, cn_stream(stream));
-  }
-  return CNERF_E_UNSUPPORTED;
+  return run({net, packed_bf, 3, {pts, rays, ray_stride, dirs, z}, B, S, raw, stash, true}, stream);
 }

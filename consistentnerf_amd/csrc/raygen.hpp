@@ -75,3 +75,13 @@ static inline RayGenDev cn_no_raygen() {
   RayGenDev g = {};
   return g;
 }
+
+// The three consumers on the rays of a camera (sampling.hip, mlp_fwd.hip, composite.hip), strung together by
+// cnerf_render_fwd_cam (render.hip).  Library-internal: same checks and launches as the public forms on ray rows.
+int cn_coarse_z_cam(const RayGenDev& cam, int64_t B, int Nc, const float* t_vals, const float* t_rand, int lindisp, float* z,
+                    hipStream_t st);
+int cn_mlp_fwd_cam(const cnerf_net* net, const float* packed, const RayGenDev& cam, const float* z, int64_t B, int S,
+                   float* raw, hipStream_t st);
+int cn_composite_fwd_cam(const float* raw, int raw_ch, const float* z, const RayGenDev& cam, const float* noise, int64_t B,
+                         int S, int white_bkgd, float* rgb, float* disp, float* acc, float* depth, float* weights,
+                         hipStream_t st);

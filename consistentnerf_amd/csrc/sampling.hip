@@ -1,7 +1,7 @@
 // Sample placement along rays: stratified coarse depths, inverse-CDF resampling, sorted merge.
 // Replaces render_rays R:355-382 / R:395-399,415 and sample_pdf H:206-250 of the reference.
 // One wave64 per ray for the scan/search/sort parts; everything a ray needs lives in LDS/registers.
-#include "common.hpp"
+#include "raygen.hpp"
 #include "rng.hpp"
 
 namespace {
@@ -266,29 +266,49 @@ __global__ __launch_bounds__(WAVES * 64) void resample_k(const float* __restrict
   }
 }
 
-}  // namespace
-
-extern "C" int cnerf_coarse_z(const float* rays, int ray_stride, int64_t B, int Nc, const float* t_vals,
-                              const float* t_rand, int lindisp, float* z, void* stream) {
-  if (!rays || !t_vals || !z || B < 0 || Nc <= 0 || ray_stride < 8) return CNERF_E_ARG;
+// ---- one launcher per kernel: the entry points below check what is theirs (the ray rows, or u / rng) and come here.
+// rays == nullptr: the rays of a camera (near / far are its constants).  Jitter: t_rand, or the in-kernel stream rng, or none.
+int launch_coarse_z(const float* rays, int rs, float near, float far, int64_t B, int Nc, const float* t_vals, const float* t_rand,
+                    const cnerf_rng* rng, int lindisp, float* z, hipStream_t st) {
+  if (!t_vals || !z || B < 0 || Nc <= 0) return CNERF_E_ARG;
   if (B == 0) return CNERF_OK;
-  int64_t n = B * Nc;
-  hipLaunchKernelGGL(coarse_z_k, dim3((unsigned)cn_div_up(n, 256)), dim3(256), 0, cn_stream(stream), rays, ray_stride,
-                     B, Nc, t_vals, t_rand, lindisp, z, 0.f, 0.f, 0, CnRngK{});
+  hipLaunchKernelGGL(coarse_z_k, dim3((unsigned)cn_div_up(B * Nc, 256)), dim3(256), 0, st, rays, rs, B, Nc, t_vals, t_rand,
+                     lindisp, z, near, far, rng ? 1 : 0, rng ? cn_rng_arg(rng) : CnRngK{});
   CN_CHECK_LAUNCH();
   return CNERF_OK;
 }
 
-// coarse depths for the rays of a camera (near / far are its constants); used by cnerf_render_fwd_cam
-int cn_coarse_z_cam(float near, float far, int64_t B, int Nc, const float* t_vals, const float* t_rand, int lindisp,
-                    float* z, hipStream_t st) {
-  if (!t_vals || !z || B < 0 || Nc <= 0) return CNERF_E_ARG;
+// u: the tensor [B or 1, Nf] (row stride u_row_stride), or the in-kernel stream rng
+int launch_resample(const float* z, const float* weights, const float* u, int64_t u_row_stride, const cnerf_rng* rng, int64_t B,
+                    int Nc, int Nf, float* z_fine, float* z_std, float* samples, int64_t* inds, void* stream) {
+  if (!z || !weights || !z_fine || !z_std || B < 0 || Nc < 3 || Nf <= 0) return CNERF_E_ARG;
+  if (Nc - 1 > MAX_NB || Nc + Nf > MAX_ALL) return CNERF_E_UNSUPPORTED;
   if (B == 0) return CNERF_OK;
-  int64_t n = B * Nc;
-  hipLaunchKernelGGL(coarse_z_k, dim3((unsigned)cn_div_up(n, 256)), dim3(256), 0, st, (const float*)nullptr, 0, B, Nc,
-                     t_vals, t_rand, lindisp, z, near, far, 0, CnRngK{});
+  hipLaunchKernelGGL(resample_k, dim3((unsigned)cn_div_up(B, WAVES)), dim3(WAVES * 64), 0, cn_stream(stream), z, weights, u,
+                     u_row_stride, B, Nc, Nf, z_fine, z_std, samples, inds, rng ? 1 : 0, rng ? cn_rng_arg(rng) : CnRngK{});
   CN_CHECK_LAUNCH();
   return CNERF_OK;
+}
+
+}  // namespace
+
+extern "C" int cnerf_coarse_z(const float* rays, int ray_stride, int64_t B, int Nc, const float* t_vals,
+                              const float* t_rand, int lindisp, float* z, void* stream) {
+  if (!rays || ray_stride < 8) return CNERF_E_ARG;
+  return launch_coarse_z(rays, ray_stride, 0.f, 0.f, B, Nc, t_vals, t_rand, nullptr, lindisp, z, cn_stream(stream));
+}
+
+// the same with the jitter generated in-kernel (rng.hpp)
+extern "C" int cnerf_coarse_z_rng(const float* rays, int ray_stride, int64_t B, int Nc, const float* t_vals, const cnerf_rng* rng,
+                                  int lindisp, float* z, void* stream) {
+  if (!rays || !rng || ray_stride < 8) return CNERF_E_ARG;
+  return launch_coarse_z(rays, ray_stride, 0.f, 0.f, B, Nc, t_vals, nullptr, rng, lindisp, z, cn_stream(stream));
+}
+
+// coarse depths for the rays of a camera; used by cnerf_render_fwd_cam
+int cn_coarse_z_cam(const RayGenDev& cam, int64_t B, int Nc, const float* t_vals, const float* t_rand, int lindisp, float* z,
+                    hipStream_t st) {
+  return launch_coarse_z(nullptr, 0, cam.near, cam.far, B, Nc, t_vals, t_rand, nullptr, lindisp, z, st);
 }
 
 extern "C" int cnerf_sample_pdf(const float* bins, const float* weights, const float* u, int64_t u_row_stride,
@@ -305,16 +325,17 @@ extern "C" int cnerf_sample_pdf(const float* bins, const float* weights, const f
 extern "C" int cnerf_resample(const float* z, const float* weights, const float* u, int64_t u_row_stride, int64_t B,
                               int Nc, int Nf, float* z_fine, float* z_std, float* samples, int64_t* inds,
                               void* stream) {
-  if (!z || !weights || !u || !z_fine || !z_std || B < 0 || Nc < 3 || Nf <= 0) return CNERF_E_ARG;
-  if (Nc - 1 > MAX_NB || Nc + Nf > MAX_ALL) return CNERF_E_UNSUPPORTED;
-  if (B == 0) return CNERF_OK;
-  hipLaunchKernelGGL(resample_k, dim3((unsigned)cn_div_up(B, WAVES)), dim3(WAVES * 64), 0, cn_stream(stream), z,
-                     weights, u, u_row_stride, B, Nc, Nf, z_fine, z_std, samples, inds, 0, CnRngK{});
-  CN_CHECK_LAUNCH();
-  return CNERF_OK;
+  if (!u) return CNERF_E_ARG;
+  return launch_resample(z, weights, u, u_row_stride, nullptr, B, Nc, Nf, z_fine, z_std, samples, inds, stream);
 }
 
-// ---- the same two entry points with the uniform streams generated in-kernel (rng.hpp) -----------------------------------------
+// the same with u generated in-kernel (rng.hpp)
+extern "C" int cnerf_resample_rng(const float* z, const float* weights, const cnerf_rng* rng, int64_t B, int Nc, int Nf,
+                                  float* z_fine, float* z_std, float* samples, int64_t* inds, void* stream) {
+  if (!rng) return CNERF_E_ARG;
+  return launch_resample(z, weights, nullptr, 0, rng, B, Nc, Nf, z_fine, z_std, samples, inds, stream);
+}
+
 namespace {
 __global__ void uniform_rng_k(CnRngK rngk, int64_t rows, int cols, float* __restrict__ out) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -329,27 +350,6 @@ extern "C" int cnerf_uniform_rng(const cnerf_rng* rng, int64_t rows, int cols, f
   if (rows == 0) return CNERF_OK;
   hipLaunchKernelGGL(uniform_rng_k, dim3((unsigned)cn_div_up(rows * cols, 256)), dim3(256), 0, cn_stream(stream), cn_rng_arg(rng),
                      rows, cols, out);
-  CN_CHECK_LAUNCH();
-  return CNERF_OK;
-}
-
-extern "C" int cnerf_coarse_z_rng(const float* rays, int ray_stride, int64_t B, int Nc, const float* t_vals, const cnerf_rng* rng,
-                                  int lindisp, float* z, void* stream) {
-  if (!rays || !t_vals || !z || !rng || B < 0 || Nc <= 0 || ray_stride < 8) return CNERF_E_ARG;
-  if (B == 0) return CNERF_OK;
-  hipLaunchKernelGGL(coarse_z_k, dim3((unsigned)cn_div_up(B * Nc, 256)), dim3(256), 0, cn_stream(stream), rays, ray_stride, B, Nc,
-                     t_vals, (const float*)nullptr, lindisp, z, 0.f, 0.f, 1, cn_rng_arg(rng));
-  CN_CHECK_LAUNCH();
-  return CNERF_OK;
-}
-
-extern "C" int cnerf_resample_rng(const float* z, const float* weights, const cnerf_rng* rng, int64_t B, int Nc, int Nf,
-                                  float* z_fine, float* z_std, float* samples, int64_t* inds, void* stream) {
-  if (!z || !weights || !rng || !z_fine || !z_std || B < 0 || Nc < 3 || Nf <= 0) return CNERF_E_ARG;
-  if (Nc - 1 > MAX_NB || Nc + Nf > MAX_ALL) return CNERF_E_UNSUPPORTED;
-  if (B == 0) return CNERF_OK;
-  hipLaunchKernelGGL(resample_k, dim3((unsigned)cn_div_up(B, WAVES)), dim3(WAVES * 64), 0, cn_stream(stream), z, weights,
-                     (const float*)nullptr, (int64_t)0, B, Nc, Nf, z_fine, z_std, samples, inds, 1, cn_rng_arg(rng));
   CN_CHECK_LAUNCH();
   return CNERF_OK;
 }

@@ -235,13 +235,10 @@ def coarse_z(rays: Tensor, Nc: int, t_rand: Optional[Tensor], lindisp: bool, rng
     B = rays.shape[0]
     t_rand = _chk(t_rand, "t_rand")
     z = torch.empty(B, Nc, device=rays.device, dtype=torch.float32)
-    if rng is not None:        # jitter generated in the kernel: stream offset + 0
-        r = rng.c(0)
-        _lib.check(_lib.load().cnerf_coarse_z_rng(_p(rays), rays.shape[1], B, Nc, _p(_t_vals(Nc, rays.device)), C.byref(r),
-                                                  int(lindisp), _p(z), _stream()), "cnerf_coarse_z_rng")
-        return z
-    _lib.check(_lib.load().cnerf_coarse_z(_p(rays), rays.shape[1], B, Nc, _p(_t_vals(Nc, rays.device)), _p(t_rand),
-                                          int(lindisp), _p(z), _stream()), "cnerf_coarse_z")
+    # the jitter: generated in the kernel (stream offset + 0), or t_rand (None: no jitter)
+    name, jitter = ("cnerf_coarse_z_rng", C.byref(rng.c(0))) if rng is not None else ("cnerf_coarse_z", _p(t_rand))
+    _lib.check(getattr(_lib.load(), name)(_p(rays), rays.shape[1], B, Nc, _p(_t_vals(Nc, rays.device)), jitter, int(lindisp), _p(z),
+                                          _stream()), name)
     return z
 
 
@@ -268,13 +265,11 @@ def resample(z: Tensor, weights: Tensor, u: Optional[Tensor], want_samples: bool
     samples = torch.empty(B, Nf, device=z.device, dtype=torch.float32) if want_samples else None
     inds = torch.empty(B, Nf, device=z.device, dtype=torch.int64) if want_samples else None
     if rng is not None:        # u generated in the kernel: stream offset + 1
-        r = rng.c(1)
-        _lib.check(_lib.load().cnerf_resample_rng(_p(z), _p(weights), C.byref(r), B, Nc, Nf, _p(z_fine), _p(z_std), _p(samples),
-                                                  _p(inds), _stream()), "cnerf_resample_rng")
+        name, source = "cnerf_resample_rng", [C.byref(rng.c(1))]
     else:
-        stride = 0 if u.dim() == 1 or u.shape[0] == 1 else Nf
-        _lib.check(_lib.load().cnerf_resample(_p(z), _p(weights), _p(u), stride, B, Nc, Nf, _p(z_fine), _p(z_std),
-                                              _p(samples), _p(inds), _stream()), "cnerf_resample")
+        name, source = "cnerf_resample", [_p(u), 0 if u.dim() == 1 or u.shape[0] == 1 else Nf]
+    _lib.check(getattr(_lib.load(), name)(_p(z), _p(weights), *source, B, Nc, Nf, _p(z_fine), _p(z_std), _p(samples), _p(inds), _stream()),
+               name)
     return (z_fine, z_std, samples, inds) if want_samples else (z_fine, z_std)
 
 
@@ -288,15 +283,31 @@ def embed(x: Tensor, L: int) -> Tensor:
     return out.reshape(*lead, 3 + 6 * L)
 
 
-def _mlp_forward_setup(spec: NetSpec, dev, shape, want_stash: bool, pts=None, rays=None, z=None, dirs=None):
-    """The preamble the forward wrappers share -> (lib, net, raw[*shape, raw_ch], stash or None, ray stride, the checked inputs)."""
-    lib, net = _lib.load(), spec.c()
-    pts, rays, z, dirs = _chk(pts, "pts"), _chk(rays, "rays"), _chk(z, "z"), _chk(dirs, "dirs")
-    raw = torch.empty(*shape, spec.raw_ch, device=dev, dtype=torch.float32)
-    stash = None
+# form of a forward -> (entry point, its arguments between (net, packed) and the stream, by the names _mlp_forward gathers)
+_FWD_ENTRY = {
+    "fp32": ("cnerf_mlp_fwd", ("pts", "rays", "rs", "dirs", "z", "B", "S", "raw", "stash")),
+    "live": ("cnerf_mlp_fwd_live", ("rays", "rs", "z", "B", "S", "raw", "stash", "live")),
+    "bf": ("cnerf_mlp_fwd_bf", ("planes", "pts", "rays", "rs", "dirs", "z", "B", "S", "raw")),
+    "bf_train": ("cnerf_mlp_fwd_bf_train", ("pts", "rays", "rs", "dirs", "z", "B", "S", "raw", "stash")),
+    "embedded": ("cnerf_mlp_fwd_embedded", ("x", "B", "raw", "stash")),
+}
+_FWD_INTS = ("rs", "B", "S", "planes")
+
+
+def _mlp_forward(form, profile, spec: NetSpec, packed, shape, want_stash: bool, pts=None, rays=None, z=None, dirs=None, **more):
+    """The one call of the forward wrappers: checks the inputs, allocates raw[*shape, raw_ch] (and the stash) and issues the entry point
+    of `form` under the profile name -> (raw, stash or None).  `more`: what only one form takes (planes, live, x)."""
+    lib, net, units = _lib.load(), spec.c(), int(np.prod(shape))
+    a = dict(more, pts=_chk(pts, "pts"), rays=_chk(rays, "rays"), z=_chk(z, "z"), dirs=_chk(dirs, "dirs"), B=shape[0], S=shape[-1])
+    a["rs"] = a["rays"].shape[1] if rays is not None else 0
+    a["raw"] = torch.empty(*shape, spec.raw_ch, device=packed.device, dtype=torch.float32)
+    a["stash"] = None
     if want_stash:
-        stash = torch.empty(lib.cnerf_mlp_stash_floats(C.byref(net), int(np.prod(shape))), device=dev, dtype=torch.float32)
-    return lib, net, raw, stash, rays.shape[1] if rays is not None else 0, pts, rays, z, dirs
+        a["stash"] = torch.empty(lib.cnerf_mlp_stash_floats(C.byref(net), units), device=packed.device, dtype=torch.float32)
+    name, names = _FWD_ENTRY[form]
+    with _timed(profile, units):
+        _lib.check(getattr(lib, name)(C.byref(net), _p(packed), *[a[k] if k in _FWD_INTS else _p(a[k]) for k in names], _stream()), name)
+    return a["raw"], a["stash"]
 
 
 def mlp_forward(spec: NetSpec, packed: Tensor, B: int, S: int, *, pts: Optional[Tensor] = None,
@@ -304,19 +315,12 @@ def mlp_forward(spec: NetSpec, packed: Tensor, B: int, S: int, *, pts: Optional[
                 want_stash: bool = False, live: Optional[Tensor] = None):
     """`live` (device int32 [1], training + rays form only): the batch is padded to the capacity B and only its first live[0] rays
     are real (cnerf_mlp_fwd_live): the launch is sized for B, tiles past the count leave zero raw outputs."""
-    lib, net, raw, stash, rs, pts, rays, z, dirs = _mlp_forward_setup(spec, packed.device, (B, S), want_stash, pts, rays, z, dirs)
-    if live is not None:
-        if not want_stash or rays is None or pts is not None or dirs is not None or live.dtype != torch.int32 or not live.is_cuda:
-            raise CnerfError("mlp_forward(live=...) is the training forward on ray rows (no explicit points / directions); "
-                             "live must be a device int32 tensor")
-        with _timed("mlp_fwd_train", B * S):
-            _lib.check(lib.cnerf_mlp_fwd_live(C.byref(net), _p(packed), _p(rays), rs, _p(z), B, S, _p(raw), _p(stash), _p(live),
-                                              _stream()), "cnerf_mlp_fwd_live")
-        return raw, stash
-    with _timed("mlp_fwd_train" if want_stash else "mlp_fwd", B * S):
-        _lib.check(lib.cnerf_mlp_fwd(C.byref(net), _p(packed), _p(pts), _p(rays), rs, _p(dirs), _p(z), B, S,
-                                     _p(raw), _p(stash), _stream()), "cnerf_mlp_fwd")
-    return raw, stash
+    if live is None:
+        return _mlp_forward("fp32", "mlp_fwd_train" if want_stash else "mlp_fwd", spec, packed, (B, S), want_stash, pts, rays, z, dirs)
+    if not want_stash or rays is None or pts is not None or dirs is not None or live.dtype != torch.int32 or not live.is_cuda:
+        raise CnerfError("mlp_forward(live=...) is the training forward on ray rows (no explicit points / directions); "
+                         "live must be a device int32 tensor")
+    return _mlp_forward("live", "mlp_fwd_train", spec, packed, (B, S), True, rays=rays, z=z, live=live)
 
 
 # NeRF.inference_precision -> the `planes` argument of cnerf_packed_bf_bytes / cnerf_pack_weights_bf / cnerf_mlp_fwd_bf
@@ -349,33 +353,21 @@ def pack_weights_bf(spec: NetSpec, params: Sequence[Tensor], planes: int, out: O
 def mlp_forward_bf(spec: NetSpec, packed_bf: Tensor, planes: int, B: int, S: int, *, pts: Optional[Tensor] = None,
                    rays: Optional[Tensor] = None, z: Optional[Tensor] = None, dirs: Optional[Tensor] = None) -> Tensor:
     """cnerf_mlp_fwd_bf: inference forward on the bf16 / f16 matrix cores (opt-in); `planes` as packed."""
-    lib, net, raw, _, rs, pts, rays, z, dirs = _mlp_forward_setup(spec, packed_bf.device, (B, S), False, pts, rays, z, dirs)
-    with _timed(_BF_PROFILE.get(int(planes), "mlp_fwd_bf%d" % planes), B * S):
-        _lib.check(lib.cnerf_mlp_fwd_bf(C.byref(net), _p(packed_bf), int(planes), _p(pts), _p(rays), rs, _p(dirs), _p(z), B, S,
-                                        _p(raw), _stream()), "cnerf_mlp_fwd_bf")
-    return raw
+    return _mlp_forward("bf", _BF_PROFILE.get(int(planes), "mlp_fwd_bf%d" % planes), spec, packed_bf, (B, S), False, pts, rays, z, dirs,
+                        planes=int(planes))[0]
 
 
 def mlp_forward_bf_train(spec: NetSpec, packed_bf: Tensor, B: int, S: int, *, pts: Optional[Tensor] = None,
                          rays: Optional[Tensor] = None, z: Optional[Tensor] = None, dirs: Optional[Tensor] = None):
     """cnerf_mlp_fwd_bf_train: the OPT-IN bf16x3 training forward (three bf16 planes per operand, fp32 accumulation) ->
     (raw, stash); the stash is the fp32 kernel's (cnerf_mlp_dgrad / cnerf_mlp_wgrad consume it unchanged)."""
-    lib, net, raw, stash, rs, pts, rays, z, dirs = _mlp_forward_setup(spec, packed_bf.device, (B, S), True, pts, rays, z, dirs)
-    with _timed("mlp_fwd_train_bf3", B * S):
-        _lib.check(lib.cnerf_mlp_fwd_bf_train(C.byref(net), _p(packed_bf), _p(pts), _p(rays), rs, _p(dirs), _p(z), B, S,
-                                              _p(raw), _p(stash), _stream()), "cnerf_mlp_fwd_bf_train")
-    return raw, stash
+    return _mlp_forward("bf_train", "mlp_fwd_train_bf3", spec, packed_bf, (B, S), True, pts, rays, z, dirs)
 
 
 def mlp_forward_embedded(spec: NetSpec, packed: Tensor, x: Tensor, want_stash: bool = False):
     """NeRF.forward on pre-embedded inputs x[M, in_ch + in_ch_views]."""
     x = _chk(x, "x")
-    M = x.shape[0]
-    lib, net, raw, stash, *_ = _mlp_forward_setup(spec, x.device, (M,), want_stash)
-    with _timed("mlp_fwd_train" if want_stash else "mlp_fwd", M):
-        _lib.check(lib.cnerf_mlp_fwd_embedded(C.byref(net), _p(packed), _p(x), M, _p(raw), _p(stash), _stream()),
-                   "cnerf_mlp_fwd_embedded")
-    return raw, stash
+    return _mlp_forward("embedded", "mlp_fwd_train" if want_stash else "mlp_fwd", spec, packed, (x.shape[0],), want_stash, x=x)
 
 
 # (pair, live, bf) -> the calls of one backward as (stage, entry point, profile name): the two halves where they exist (bench.py's

@@ -4,7 +4,7 @@
 returns and of every parameter gradient it leaves.  A change of host code only (run_nerf.py, run_nerf_view.py, ops.py) must leave
 the file this writes identical: run it on the commit before and on the commit after, and compare.  It uses nothing but API that
 predates it.  Shapes: 64 x 64 views, D = 2 / W = 64 networks with view directions, 32 + 32 samples, 512 rays (two 16 x 16 patches),
-chunk 4096.
+chunk 4096.  The plane forwards (ops.mlp_forward_bf*) run on a D = 2 / W = 128 network: W = 64 is outside their envelope.
 
 usage: python scripts/step_fingerprint.py OUT.json                  (every route)
        python scripts/step_fingerprint.py --sequences OUT.json      (tests/golden/entry_sequences.json: the entry-point lists of the
@@ -65,10 +65,10 @@ def digest(x, out, path):
     # (anything else — modules, PackedRays — is no result of the route)
 
 
-def model(seed, dev):
+def model(seed, dev, width=64):
     from consistentnerf_amd.run_nerf_helpers import NeRF
-    sd = I.nerf_state_dict(2, 64, 10, 4, 5, True, seed)
-    m = NeRF(D=2, W=64, input_ch=63, output_ch=5, skips=[4], input_ch_views=27, use_viewdirs=True)
+    sd = I.nerf_state_dict(2, width, 10, 4, 5, True, seed)
+    m = NeRF(D=2, W=width, input_ch=63, output_ch=5, skips=[4], input_ch_views=27, use_viewdirs=True)
     m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()}, strict=True)
     return m.to(dev)
 
@@ -96,7 +96,7 @@ def scene(dev):
     return dict(dev=dev, K=K, poses=poses, img=[t(x) for x in images], dep=[t(x) for x in depths],
                 rays=torch.stack([t(ro.reshape(-1, 3)[pix]), t(rd.reshape(-1, 3)[pix])], 0), target=t(images[0].reshape(-1, 3)[pix]),
                 prior=t(depths[0].reshape(-1)[pix]), mask=t(rs.uniform(size=pix.size) < 0.55), mono=t(1.0 / depths[0].reshape(-1)[pix]),
-                coarse=coarse, fine=fine, kw=kw, kw1=dict(kw, N_importance=0, network_fine=None),
+                coarse=coarse, fine=fine, wide=model(73, dev, 128), kw=kw, kw1=dict(kw, N_importance=0, network_fine=None),
                 lp=LPIPS(net="vgg", weights=_lpips_ref.package_state_dict(_lpips_ref.make_weights(0))).to(dev))
 
 
@@ -234,6 +234,59 @@ def routes(sc):
         return None, [ops.resample(z, w, u), ops.resample(z, w, u, want_samples=True), ops.resample(z, w, u[:1]),
                       ops.resample(z, w, None, rng=rng, Nf=NF), ops.resample(z, w, None, want_samples=True, rng=rng, Nf=NF)]
     r["ops.resample"] = resample
+
+    # ---- the forward entry points one by one (ops.mlp_forward*, coarse_z, sample_pdf)
+    def points():
+        r11 = rows()
+        z = ops.coarse_z(r11, NC, None, False)
+        return r11, z, (r11[:, None, :3] + r11[:, None, 3:6] * z[..., None]).reshape(-1, 3), r11[:, 8:].repeat_interleave(NC, 0).contiguous()
+
+    def mlp_forward():
+        r11, z, pts, dirs = points()
+        spec, pk = coarse.spec(), R._packed(coarse)
+        return None, [ops.mlp_forward(spec, pk, 512 * NC, 1, pts=pts, dirs=dirs),
+                      ops.mlp_forward(spec, pk, 512, NC, rays=r11[:, :8].contiguous(), z=z, dirs=r11[:, 8:].contiguous()),
+                      ops.mlp_forward(spec, pk, 512, NC, rays=r11, z=z),
+                      ops.mlp_forward(spec, pk, 512, NC, rays=r11, z=z, want_stash=True),
+                      ops.mlp_forward(spec, pk, 512 * NC, 1, pts=pts, dirs=dirs, want_stash=True)]
+    r["ops.mlp_forward"] = mlp_forward
+
+    def mlp_forward_embedded():
+        _, _, pts, dirs = points()
+        x = torch.cat([ops.embed(pts, 10), ops.embed(dirs, 4)], -1)
+        return None, [ops.mlp_forward_embedded(coarse.spec(), R._packed(coarse), x, want_stash=ws) for ws in (False, True)]
+    r["ops.mlp_forward_embedded"] = mlp_forward_embedded
+
+    def planes(perwave):
+        def run():
+            r11, z, pts, dirs = points()
+            spec, params = sc["wide"].spec(), [p.detach() for p in sc["wide"].kernel_tensors()]
+            if perwave:
+                os.environ["CNERF_BF_PERWAVE"] = "1"
+            try:
+                out = []
+                for n in (1, 2, 3, ops.PLANES_FP16X2):
+                    pk = ops.pack_weights_bf(spec, params, n)
+                    out += [ops.mlp_forward_bf(spec, pk, n, 512, NC, rays=r11, z=z), ops.mlp_forward_bf(spec, pk, n, 512 * NC, 1, pts=pts, dirs=dirs)]
+                pk = ops.pack_weights_bf(spec, params, 3)
+                return None, out + [ops.mlp_forward_bf_train(spec, pk, 512, NC, rays=r11, z=z)]
+            finally:
+                os.environ.pop("CNERF_BF_PERWAVE", None)
+        return run
+    r["ops.mlp_forward_bf.shared_panel"] = planes(False)
+    r["ops.mlp_forward_bf.per_wave"] = planes(True)
+
+    def coarse_z():
+        t = torch.rand(512, NC, device=dev)
+        return None, [ops.coarse_z(rows(), NC, t, False), ops.coarse_z(rows(), NC, None, False), ops.coarse_z(rows(), NC, t, True),
+                      ops.coarse_z(rows(), NC, None, False, rng=ops.rng_draw(dev))]
+    r["ops.coarse_z"] = coarse_z
+
+    def sample_pdf():
+        bins = torch.sort(torch.rand(512, NC, device=dev), -1)[0]
+        w, u = torch.rand(512, NC - 1, device=dev), torch.rand(512, NF, device=dev)
+        return None, [ops.sample_pdf(bins, w, u), ops.sample_pdf(bins, w, u, want_inds=True), ops.sample_pdf(bins, w, u[:1])]
+    r["ops.sample_pdf"] = sample_pdf
     return r
 
 

@@ -60,8 +60,8 @@ BASE = {
 # in run()); cnerf_composite_bwd_lossform takes coef right after the three weights, which is where dict() puts it above.
 
 
-def _variants(entry, base):
-    """{case suffix: {path: value}} for one entry point: every pointer (struct fields included) nulled in turn, then the edges."""
+def null_variants(base):
+    """{"valid": {}} and one variant per pointer of the call, struct fields included, with that pointer null."""
     v = {"valid": {}}
     for k, x in base.items():
         if x == P_ or (isinstance(x, tuple)):
@@ -70,6 +70,12 @@ def _variants(entry, base):
             for fk, fx in x[1].items():
                 if fx == P_:
                     v[f"null.{k}.{fk}"] = {f"{k}.{fk}": None}
+    return v
+
+
+def _variants(entry, base):
+    """{case suffix: {path: value}} for one entry point: every pointer (struct fields included) nulled in turn, then the edges."""
+    v = null_variants(base)
     fin = "t" in base
     bname = "t.B" if fin else "B"
     v["B.neg"], v["B.zero"] = {bname: -1}, {bname: 0}
@@ -175,13 +181,16 @@ def _materialise(L, base, change, ptr, max_rays, keep):
     return args
 
 
-def run(lib_path=None):
-    """{case name: return code} of every case against the library at lib_path (None: the package's own).  Raises where a device is visible."""
+def run(lib_path=None, M=None):
+    """{case name: return code} of every case of the cases module M (None: this one; tests/_fwd_rule_cases.py is the other) against the
+    library at lib_path (None: the package's own).  Raises where a device is visible.  A change named "$VARIABLE" is no argument: that
+    environment variable holds the value during the call."""
+    M = M or sys.modules[__name__]
     if ROOT not in sys.path:
         sys.path.insert(0, ROOT)
     from consistentnerf_amd import _lib as L
     lib = C.CDLL(lib_path or L.LIB_PATH)
-    for n in list(BASE) + ["cnerf_device_info", "cnerf_composite_mse_max_rays"]:
+    for n in list(M.BASE) + ["cnerf_device_info", "cnerf_composite_mse_max_rays"]:
         f = getattr(lib, n)
         f.restype, f.argtypes = L.SIGNATURES[n]
     name, cus, mem = C.create_string_buffer(256), C.c_int(0), C.c_int(0)
@@ -192,9 +201,15 @@ def run(lib_path=None):
     assert ptr % 8 == 0
     max_rays = lib.cnerf_composite_mse_max_rays()
     out, keep = {}, []
-    for cname, entry, base, change in cases():
-        args = _materialise(L, base, change, ptr, max_rays, keep)
+    for cname, entry, base, change in M.cases():
+        env = {k[1:]: x for k, x in change.items() if k.startswith("$")}
+        args = _materialise(L, base, {k: x for k, x in change.items() if not k.startswith("$")}, ptr, max_rays, keep)
         assert len(args) == len(L.SIGNATURES[entry][1]), (entry, len(args))
         assert cname not in out, cname
-        out[cname] = int(getattr(lib, entry)(*args))
+        os.environ.update(env)
+        try:
+            out[cname] = int(getattr(lib, entry)(*args))
+        finally:
+            for k in env:
+                del os.environ[k]
     return out
