@@ -12,8 +12,8 @@
 // fp16 plane carries 11 significand bits, so x = h + l with h = fp16(x), l = fp16(x - h) carries 22 and the three products
 // w_h x_h + w_h x_l + w_l x_h reach the bf16x3 tier at the MFMA count, panel bytes and ring traffic of bf16x2 — the ring, the DMA,
 // the panel layout and the k order are the two-plane bf16 ones, unchanged.  fp16 has 5 exponent bits (normal range 2^-14 ..
-// 65504), so every operand carries an EXACT power-of-two factor (mlp_bf_common.hpp: F16_SW = 8, F16_SX = 4), chosen so that the
-// result does not depend on the matrix pipe honouring fp16 subnormals:
+// 65504), so every operand carries an EXACT power-of-two factor (mlp_bf_common.hpp: F16_SW = 8, F16_SX = 4), chosen so that on
+// ordinary networks the result does not depend on fp16 subnormals being honoured (a cold layer does depend on it: see RANGE):
 //     weights      packed as planes of w * 2^8                       biases packed * 2^12, sigma / rgb head weights * 2^-12
 //     encodings    split as planes of gamma * 2^4
 //     accumulators hold 2^12 * (the true pre-activation), fp32       (fp32 range: no concern)
@@ -25,7 +25,9 @@
 // (65504 / 2^4).  Resolution: an operand keeps 22 bits down to 2^-3 in scaled units (|w| >= 2^-11, |a| >= 2^-7); below that its
 // low plane is an fp16 subnormal and keeps absolute steps of 2^-24 scaled if the pipe honours subnormals, and is dropped if it
 // flushes them — an absolute error of at most 2^-14 scaled = 2^-22 per weight, 2^-18 per activation, which is what the CPU
-// restatement (tests/test_fp16x2_cpu.py, worst case "flush") bounds end to end.
+// restatement (tests/test_fp16x2_cpu.py, worst case "flush") bounds end to end.  On a layer whose weights and activations sit
+// 2^6 .. 2^9 below the usual that absolute error is 5-12x the tier; conversion, residual and matrix pipe all KEEP subnormals on
+// gfx950, which tests/test_gpu_plane_inference.py::test_stated_range_vs_float64 holds the whole path to.
 // OUTSIDE the range a conversion overflows to fp16 infinity and the accumulators of that point take inf / NaN; the following
 // ReLU (v_max_f32) turns NaN into 0, so the caller may see non-finite OR finite-but-wrong raw values for the affected points
 // (every point, when it is a weight that is out of range).  Nothing detects this: networks that can leave the range use bf16x3.

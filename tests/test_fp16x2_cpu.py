@@ -15,95 +15,20 @@ import pytest
 import torch
 
 import _inputs as I
+import _planes_ref as P
 from conftest import golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-D = 8
-
-
-def _planes_f16(x, flush):
-    out = []
-    for _ in range(2):
-        h = x.to(torch.float16).to(torch.float32)
-        if flush:
-            h = torch.where(h.abs() < 2.0 ** -14, torch.zeros_like(h), h)
-        out.append(h)
-        x = x - h          # exact in fp32 (flushed values stay in the residual, and are lost with the last plane)
-    return out
-
-
-def _planes_bf16(x):
-    out = []
-    for _ in range(2):
-        h = x.to(torch.bfloat16).to(torch.float32)
-        out.append(h)
-        x = x - h
-    return out
-
-
-def _embed(x, L):
-    out = [x]
-    for i in range(L):
-        out += [torch.sin(x * 2.0 ** i), torch.cos(x * 2.0 ** i)]
-    return torch.cat(out, -1)
+CFG = (8, 256, 10, 4, 4)
 
 
 def _forward(sd, pts, dirs, mode, flush=True):
-    """The network as the kernel computes it.  fp16x2: accumulators in units of 2^(SW + SX), biases pre-scaled by that factor,
-    head weights by its inverse, activations re-scaled by 2^-SW at the split.  bf16x2: the same structure without scaling."""
-    from consistentnerf_amd import ops
-    if mode == "fp16x2":
-        sw, sx = ops.FP16X2_WEIGHT_SHIFT, ops.FP16X2_ACT_SHIFT
-        wplanes = lambda w: _planes_f16(w * 2.0 ** sw, flush)                 # noqa: E731  (pack: scale, then split)
-        enc = lambda x: _planes_f16(x * 2.0 ** sx, flush)                     # noqa: E731
-        act = lambda a: _planes_f16(a * 2.0 ** -sw, flush)                    # noqa: E731  (accumulator -> 2^sx * activation)
-        acc_scale = 2.0 ** (sw + sx)
-    else:
-        wplanes = _planes_bf16
-        enc = act = _planes_bf16
-        acc_scale = 1.0
-    g = lambda k: torch.as_tensor(sd[k]).float()                             # noqa: E731
-
-    def gemm(wp, xp):      # the three cross terms, exact products, wide accumulation
-        return xp[0].double() @ wp[0].double().T + xp[1].double() @ wp[0].double().T + xp[0].double() @ wp[1].double().T
-
-    ex, ed = _embed(pts, 10), _embed(dirs, 4)
-    w0 = g("pts_linears.0.weight")
-    acc = (gemm(wplanes(w0), enc(ex)) + (g("pts_linears.0.bias") * acc_scale).double()).float()
-    amax = 0.0
-    for l in range(1, D):
-        w = g(f"pts_linears.{l}.weight")
-        h = torch.relu(acc)
-        amax = max(amax, float(h.abs().max()) / acc_scale)
-        if l == 5:         # the skip layer: its input is cat([gamma(x), h])
-            a = gemm(wplanes(w[:, 63:].contiguous()), act(h)) + gemm(wplanes(w[:, :63].contiguous()), enc(ex))
-        else:
-            a = gemm(wplanes(w), act(h))
-        acc = (a + (g(f"pts_linears.{l}.bias") * acc_scale).double()).float()
-    h = torch.relu(acc)
-    amax = max(amax, float(h.abs().max()) / acc_scale)
-    sig = (h.double() @ (g("alpha_linear.weight") / acc_scale).double().T).float() + g("alpha_linear.bias")
-    feat = (gemm(wplanes(g("feature_linear.weight")), act(h)) + (g("feature_linear.bias") * acc_scale).double()).float()
-    amax = max(amax, float(feat.abs().max()) / acc_scale)
-    wv = g("views_linears.0.weight")
-    v = (gemm(wplanes(wv[:, :256].contiguous()), act(feat)) + gemm(wplanes(wv[:, 256:].contiguous()), enc(ed))
-         + (g("views_linears.0.bias") * acc_scale).double()).float()
-    rgb = (torch.relu(v).double() @ (g("rgb_linear.weight") / acc_scale).double().T).float() + g("rgb_linear.bias")
-    return torch.cat([rgb, sig], -1), amax
+    """The network as the kernel computes it (tests/_planes_ref.py) -> (raw, the largest activation)."""
+    return P.forward_planes(sd, pts, dirs, CFG, mode, flush=flush)
 
 
 def _ref64(sd, pts, dirs):
-    s = {k: torch.as_tensor(v).double() for k, v in sd.items()}
-    ex, ed = _embed(pts.double(), 10), _embed(dirs.double(), 4)
-    h = ex
-    for l in range(D):
-        h = torch.relu(h @ s[f"pts_linears.{l}.weight"].T + s[f"pts_linears.{l}.bias"])
-        if l == 4:
-            h = torch.cat([ex, h], -1)
-    sig = h @ s["alpha_linear.weight"].T + s["alpha_linear.bias"]
-    feat = h @ s["feature_linear.weight"].T + s["feature_linear.bias"]
-    v = torch.relu(torch.cat([feat, ed], -1) @ s["views_linears.0.weight"].T + s["views_linears.0.bias"])
-    return torch.cat([v @ s["rgb_linear.weight"].T + s["rgb_linear.bias"], sig], -1)
+    return P.forward64(sd, pts, dirs, CFG)
 
 
 def _nets():
