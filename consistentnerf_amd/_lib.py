@@ -220,6 +220,10 @@ SIGNATURES = {
     "cnerf_depthvis": (_i, [_vp, _vp, _i64, _i64, _i64, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "cnerf_eval_prep_ws_bytes": (_i64, [_i64, _i64, _i64]),
     "cnerf_eval_prep": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cnerf_mlp_input_grad": (_i, [_NetP, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cnerf_rays_input_grad": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _i, _vp]),
+    "cnerf_composite_norm_grad": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i64, _i, _vp, _i, _vp]),
+    "cnerf_pack_rays_bwd": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

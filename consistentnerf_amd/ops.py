@@ -382,16 +382,23 @@ _BWD_ENTRY = {
 }
 
 
-def _mlp_backward(levels, accumulate, bf, live, first=()):
+def mlp_bwd_workspace(spec: NetSpec, B: int, S: int, device) -> Tensor:
+    """The caller-owned workspace of one level's backward (cnerf_mlp_bwd_ws_floats): dZ of every layer, then the wgrad partials."""
+    net = spec.c()
+    return torch.empty(_lib.load().cnerf_mlp_bwd_ws_floats(C.byref(net), B * S), device=device, dtype=torch.float32)
+
+
+def _mlp_backward(levels, accumulate, bf, live, first=(), ws=None):
     """One backward over `levels`, one or two of (spec, packed, d_raw, B, S, stash, grads) with `packed` the buffer of the chosen
     arithmetic.  `units` of the profile records is the launch CAPACITY (with `live` the point count is on the device: the bench
-    rescales by the step's live rows)."""
+    rescales by the step's live rows).  `ws` (one level): the workspace to run in, for a caller that reads dZ afterwards."""
     lib = _lib.load()
     dgrad, wgrad, units, keep = [], [], 0, []
     for i, (spec, packed, d_raw, B, S, stash, grads) in enumerate(levels):
         net, ptrs = spec.c(), _ptrs(grads)
         d_raw = _chk(d_raw, "d_raw" if len(levels) == 1 else "d_raw%d" % i)
-        ws = torch.empty(lib.cnerf_mlp_bwd_ws_floats(C.byref(net), B * S), device=packed.device, dtype=torch.float32)
+        if ws is None or i > 0:
+            ws = mlp_bwd_workspace(spec, B, S, packed.device)
         dgrad.append([C.byref(net), _p(packed), _p(d_raw), B, S, _p(stash), _p(ws)])
         wgrad.append([C.byref(net), B, S, _p(stash), _p(ws), C.byref(ptrs)])
         units += B * S
@@ -407,17 +414,71 @@ def _mlp_backward(levels, accumulate, bf, live, first=()):
 
 def mlp_backward(spec: NetSpec, packed: Tensor, d_raw: Tensor, B: int, S: int, stash: Tensor,
                  grads: Optional[List[Tensor]] = None, accumulate: bool = False, packed_bf: Optional[Tensor] = None,
-                 live: Optional[Tensor] = None) -> List[Tensor]:
+                 live: Optional[Tensor] = None, ws: Optional[Tensor] = None) -> List[Tensor]:
     """packed_bf (the three-plane buffer of pack_weights_bf): the dgrad and wgrad run in the opt-in bf16x3 arithmetic.
-    live: the forward ran through mlp_forward(live=...) — the backward stops at the same device-side row count (exact fp32)."""
+    live: the forward ran through mlp_forward(live=...) — the backward stops at the same device-side row count (exact fp32).
+    ws (mlp_bwd_workspace): run in this workspace, for a caller that reads dZ afterwards (mlp_input_grad)."""
     if grads is None:
         grads = [torch.empty(s, device=packed.device, dtype=torch.float32) for s in spec.tensor_shapes()]
         accumulate = False
     bf = packed_bf is not None
     if live is not None and bf:
         raise CnerfError("mlp_backward(live=...) is an exact-fp32 path")
-    _mlp_backward([(spec, packed_bf if bf else packed, d_raw, B, S, stash, grads)], accumulate, bf, live)
+    _mlp_backward([(spec, packed_bf if bf else packed, d_raw, B, S, stash, grads)], accumulate, bf, live, ws=ws)
     return grads
+
+
+def mlp_dgrad(spec: NetSpec, packed: Tensor, d_raw: Tensor, B: int, S: int, stash: Tensor, ws: Tensor,
+              packed_bf: Optional[Tensor] = None) -> Tensor:
+    """cnerf_mlp_dgrad (packed_bf: cnerf_mlp_dgrad_bf) on its own: dZ of every layer into `ws` (mlp_bwd_workspace), no parameter
+    gradients — the backward of a frozen network whose inputs take a gradient (mlp_input_grad reads `ws`)."""
+    net, d_raw = spec.c(), _chk(d_raw, "d_raw")
+    name, profile, pk = ("cnerf_mlp_dgrad_bf", "mlp_dgrad_bf3", packed_bf) if packed_bf is not None else ("cnerf_mlp_dgrad", "mlp_dgrad", packed)
+    with _timed(profile, B * S):
+        _lib.check(getattr(_lib.load(), name)(C.byref(net), _p(pk), _p(d_raw), B, S, _p(stash), _p(ws), _stream()), name)
+    return ws
+
+
+def mlp_input_grad(spec: NetSpec, packed: Tensor, B: int, S: int, stash: Tensor, ws: Tensor, want_dirs: bool = False):
+    """cnerf_mlp_input_grad, behind the dgrad of the same level in `ws` (mlp_backward(ws=...) or mlp_dgrad) ->
+    (d_pts [B*S, 3], d_dirs_pt [B*S, 3] | None): the gradient w.r.t. every sample position and, per point, w.r.t. its ray's view
+    direction (rays_input_grad sums those per ray).  `packed`: the fp32 panels, also behind a bf16x3 dgrad."""
+    net = spec.c()
+    d_pts = torch.empty(B * S, 3, device=packed.device, dtype=torch.float32)
+    d_dirs = torch.empty(B * S, 3, device=packed.device, dtype=torch.float32) if want_dirs else None
+    with _timed("mlp_input_grad", B * S):
+        _lib.check(_lib.load().cnerf_mlp_input_grad(C.byref(net), _p(packed), B, S, _p(stash), _p(ws), _p(d_pts), _p(d_dirs), _stream()),
+                   "cnerf_mlp_input_grad")
+    return d_pts, d_dirs
+
+
+def rays_input_grad(d_pts: Optional[Tensor], d_dirs_pt: Optional[Tensor], z: Optional[Tensor], B: int, S: int,
+                    ray_stride: Optional[int] = None) -> Tensor:
+    """cnerf_rays_input_grad.  ray_stride None -> d_viewdirs [B, 3] = the per-ray sum of d_dirs_pt (the points form).  Otherwise ->
+    the gradient of the [B, ray_stride] ray rows the level read: columns 0:3 = sum_s d_pts, 3:6 = sum_s z d_pts, and with d_dirs_pt
+    the last three columns = its per-ray sum; every other column zero."""
+    lib = _lib.load()
+    if ray_stride is None:
+        out = torch.empty(B, 3, device=d_dirs_pt.device, dtype=torch.float32)
+        _lib.check(lib.cnerf_rays_input_grad(None, _p(d_dirs_pt), None, B, S, None, None, _p(out), 3, _stream()), "cnerf_rays_input_grad")
+        return out
+    z = _chk(z, "z")
+    out = torch.zeros(B, ray_stride, device=d_pts.device, dtype=torch.float32)
+    _lib.check(lib.cnerf_rays_input_grad(_p(d_pts), _p(d_dirs_pt), _p(z), B, S, _p(out), _p(out[:, 3:]),
+                                         _p(out[:, ray_stride - 3:]) if d_dirs_pt is not None else None, ray_stride, _stream()),
+               "cnerf_rays_input_grad")
+    return out
+
+
+def composite_norm_grad(d_raw: Tensor, raw: Tensor, noise: Optional[Tensor], rays: Tensor) -> Tensor:
+    """cnerf_composite_norm_grad: the gradient of raw2outputs w.r.t. the ray rows, which enter through dists * |rays_d| only (R:283),
+    from the d_raw of composite_backward -> [B, ray_stride], columns 3:6 filled."""
+    d_raw, raw, noise, rays = _chk(d_raw, "d_raw"), _chk(raw, "raw"), _chk(noise, "noise"), _chk(rays, "rays")
+    B, S = raw.shape[0], raw.shape[1]
+    out = torch.zeros_like(rays)
+    _lib.check(_lib.load().cnerf_composite_norm_grad(_p(d_raw), _p(raw), raw.shape[-1], _p(noise), _p(rays), rays.shape[1], B, S,
+                                                     _p(out[:, 3:]), rays.shape[1], _stream()), "cnerf_composite_norm_grad")
+    return out
 
 
 def mlp_backward_pair(spec0: NetSpec, packed0: Tensor, d_raw0: Tensor, B0: int, S0: int, stash0: Tensor, grads0: List[Tensor],
@@ -473,6 +534,9 @@ def render_forward(spec_c: NetSpec, packed_c: Tensor, spec_f: Optional[NetSpec],
                    white_bkgd: bool = False, train: bool = False, retraw: bool = False):
     """cnerf_render_fwd: render_rays (R:311-421 / V:441-551) of one ray batch in one C call.  Returns (dict with the
     reference's keys + depth maps, RenderState for render_backward)."""
+    if train and rays.requires_grad and torch.is_grad_enabled():
+        raise CnerfError("render_forward / render_backward (the one-call cnerf_render_fwd / cnerf_render_bwd): gradients w.r.t. rays "
+                         "are not implemented (parameter gradients only; run_nerf.render(rays=...) has them)")
     rays, t_rand, u = _chk(rays, "rays"), _chk(t_rand, "t_rand"), _chk(u, "u")
     noise0, noise1 = _chk(noise0, "noise0"), _chk(noise1, "noise1")
     B, dev = rays.shape[0], rays.device
@@ -863,6 +927,19 @@ def pack_rays(rays_o: Tensor, rays_d: Tensor, near: float, far: float, use_viewd
                                            int(ndc), float(ndc_coef[0]), float(ndc_coef[1]), _p(rays), _stream()),
                "cnerf_pack_rays")
     return rays
+
+
+def pack_rays_bwd(g: Tensor, rays_d: Tensor, use_viewdirs: bool):
+    """cnerf_pack_rays_bwd: the gradient of the non-NDC pack_rays rows g [B, 8 | 11] -> (d_rays_o [B, 3], d_rays_d [B, 3])."""
+    g, rays_d = _chk(g, "g"), _chk(rays_d.reshape(-1, 3), "rays_d")
+    B = rays_d.shape[0]
+    if g.shape != (B, 11 if use_viewdirs else 8):
+        raise CnerfError(f"pack_rays_bwd: g is {tuple(g.shape)}, the pack has {(B, 11 if use_viewdirs else 8)}")
+    d_o, d_d = torch.empty_like(rays_d), torch.empty_like(rays_d)
+    if B > 0:
+        _lib.check(_lib.load().cnerf_pack_rays_bwd(_p(g), _p(rays_d), B, int(use_viewdirs), _p(d_o), _p(d_d), _stream()),
+                   "cnerf_pack_rays_bwd")
+    return d_o, d_d
 
 
 def sample_pixels(H: int, W: int, K, c2w, near: float, far: float, use_viewdirs: bool, ndc: bool, ndc_coef, crop, patch_starts,

@@ -5,7 +5,8 @@
 
 Same signatures, kwargs dictionaries and return structures; the bodies launch the gfx950 kernels of
 libcnerf_hip.so (include/cnerf.h).  Autograd is wired with two torch.autograd.Function nodes (fused
-encoding+MLP, compositing); sampling carries no gradient, exactly like the reference (R:397).
+encoding+MLP, compositing); sampling carries no gradient, exactly like the reference (R:397).  Sample points, view directions
+and the rays of render(rays=(rays_o, rays_d), ndc=False) take gradients too (csrc/mlp_igrad.hip, behind the same backward).
 
 `run_nerf_view.py` of this package layers the ConsistentNeRF additions (depth outputs, warp, hard masks,
 masked losses) on top of this module.
@@ -244,6 +245,8 @@ def _link_levels(raw_coarse, raw_fine):
         return
     if getattr(nc, "stash", None) is None or getattr(nf, "stash", None) is None or nc.model is nf.model:
         return
+    if getattr(nc, "igrad", False) or getattr(nf, "igrad", False):      # a level whose inputs take a gradient runs on its own
+        return                                                          # (_MlpFn._input_grads)
     nc.pair = nf.pair = _LevelPair(nc, nf)
 
 
@@ -312,12 +315,19 @@ class _MlpFn(torch.autograd.Function):
     def forward(ctx, model, B, S, pts, rays, z, dirs, emb, live, skip, *params):
         spec = model.spec()
         packed, gen = _PanelCache.get(model)
-        if any(ctx.needs_input_grad[3:8]):
-            # fail loudly rather than return silently-missing gradients: the reference never differentiates through the
-            # sample positions (z is detached at R:397, rays come from the data), and the dgrad kernel stops at layer 0
-            raise ops.CnerfError("gradients w.r.t. sample positions / rays / view directions / pre-embedded inputs are "
-                                 "not implemented (only w.r.t. the network parameters)")
-        train = any(ctx.needs_input_grad[10:])
+        need_pts, need_rays, need_z, need_dirs, need_emb = ctx.needs_input_grad[3:8]
+        # fail loudly rather than return silently-missing gradients
+        if need_emb:
+            raise ops.CnerfError("gradients w.r.t. pre-embedded inputs (NeRF.forward(x) with x.requires_grad) are not implemented: "
+                                 "run_network(pts, viewdirs, ...) differentiates w.r.t. the points and view directions themselves")
+        if need_z:
+            raise ops.CnerfError("gradients w.r.t. z_vals are not implemented (the sample depths are detached, R:397)")
+        # gradients w.r.t. sample positions / ray rows / view directions: the stash is kept and the backward runs this level alone,
+        # dgrad (+ wgrad when parameters take gradients too), then cnerf_mlp_input_grad on the same workspace
+        igrad = need_pts or need_rays or need_dirs
+        if igrad and live is not None:
+            raise ops.CnerfError("input gradients of a `live` batch (a batch padded to a fixed capacity) are not implemented")
+        train = any(ctx.needs_input_grad[10:]) or igrad
         packed_bf = bf_gen = use_live = None
         if emb is not None:      # NeRF.forward(x) on pre-embedded inputs
             raw, stash = ops.mlp_forward_embedded(spec, packed, emb, want_stash=train)
@@ -338,7 +348,11 @@ class _MlpFn(torch.autograd.Function):
             ctx.packed_bf, ctx.packed_bf_gen, ctx.live, ctx.pair = packed_bf, bf_gen, use_live, None    # (pair: _link_levels sets it)
             # `skip` (with live): this level's first `skip` rays will get zero seeds — the merged backward leaves them out
             ctx.skip = int(skip) if (use_live is not None and skip) else 0
-            if hasattr(model, "_cnerf_pending"):     # distributed.GradReducer counts this network's backward nodes
+            ctx.igrad = igrad
+            if igrad:       # what the input-gradient launches need beside the stash: the sample depths and the form of the inputs
+                ctx.z, ctx.ray_stride, ctx.dirs_given = z, (rays.shape[1] if rays is not None else None), dirs is not None
+            # distributed.GradReducer counts this network's backward nodes (those that produce parameter gradients)
+            if hasattr(model, "_cnerf_pending") and any(ctx.needs_input_grad[10:]):
                 model._cnerf_pending += 1
         return raw
 
@@ -351,6 +365,8 @@ class _MlpFn(torch.autograd.Function):
         if ctx.packed_bf is not None and not _still_valid(ctx.model, ctx.packed_bf_gen, ctx.packed_bf, planes=3):
             raise ops.CnerfError("the network's weights were updated twice between this bf16x3 forward pass and its backward "
                                  "(the bf16-plane copy it used has been re-packed)")
+        if ctx.igrad:
+            return _MlpFn._input_grads(ctx, g_raw)
         # Parameters owned by FusedAdam carry their .grad as a view into the flat gradient buffer: under loss.backward()
         # the wgrad reduction accumulates straight into it (what AccumulateGrad would do with ~50 add/copy launches per
         # step) and autograd gets no per-tensor gradients back.  Anything else — plain nn.Parameters, and
@@ -379,14 +395,45 @@ class _MlpFn(torch.autograd.Function):
         ctx.stash = ctx.packed = ctx.params = ctx.model = None
         return nret if direct else (None,) * 10 + tuple(grads)
 
+    @staticmethod
+    def _input_grads(ctx, g_raw):
+        """The backward of a level whose sample positions / ray rows / view directions take a gradient: this level alone (never
+        parked or paired), the full backward when parameters take gradients too and the dgrad alone when they do not, then
+        cnerf_mlp_input_grad on the workspace the dgrad wrote and the per-ray sums."""
+        params, needs = ctx.params, ctx.needs_input_grad
+        job = _LevelJob(ctx, g_raw)
+        ws = ops.mlp_bwd_workspace(job.spec, job.B, job.S, job.packed.device)
+        grads, direct = None, False
+        if any(needs[10:]):
+            direct = _direct_ok(needs[10:], params) and _engine_accumulates(params[0])
+            grads = ops.mlp_backward(job.spec, job.packed, job.d_raw, job.B, job.S, job.stash, grads=[p.grad for p in params] if direct else None,
+                                     accumulate=direct and not _take_dropped(params), packed_bf=job.packed_bf, ws=ws)
+            _report_ready([job.model], direct)
+        else:
+            ops.mlp_dgrad(job.spec, job.packed, job.d_raw, job.B, job.S, job.stash, ws, packed_bf=job.packed_bf)
+        need_pts, need_rays, _, need_dirs = needs[3:7]
+        vd = bool(job.spec.use_viewdirs)
+        dirs_in_rows = vd and not ctx.dirs_given          # the view directions are the last three columns of the ray rows (R:350)
+        d_pts, d_dirs_pt = ops.mlp_input_grad(job.spec, job.packed, job.B, job.S, job.stash, ws,
+                                              want_dirs=vd and (need_dirs or (need_rays and dirs_in_rows)))
+        g_pts = d_pts if need_pts else None
+        g_rays = g_dirs = None
+        if need_rays:
+            g_rays = ops.rays_input_grad(d_pts, d_dirs_pt if dirs_in_rows else None, ctx.z, job.B, job.S, ray_stride=ctx.ray_stride)
+        if need_dirs and vd:
+            g_dirs = ops.rays_input_grad(None, d_dirs_pt, None, job.B, job.S)
+        ctx.stash = ctx.packed = ctx.params = ctx.model = ctx.z = None
+        return (None, None, None, g_pts, g_rays, None, g_dirs, None, None, None) + (tuple(grads) if grads is not None and not direct
+                                                                                     else (None,) * len(params))
+
 
 class _CompositeFn(torch.autograd.Function):
     """raw2outputs (R:265-308) and its backward."""
 
     @staticmethod
     def forward(ctx, raw, z_vals, rays, noise, white_bkgd):
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:   # (z is detached in the reference, R:397; rays are data)
-            raise ops.CnerfError("raw2outputs: gradients w.r.t. z_vals / rays are not implemented (only w.r.t. raw)")
+        if ctx.needs_input_grad[1]:   # (z is detached in the reference, R:397)
+            raise ops.CnerfError("raw2outputs: gradients w.r.t. z_vals are not implemented (only w.r.t. raw and rays_d)")
         rgb, disp, acc, weights, depth = ops.composite_forward(raw, z_vals, rays, noise, white_bkgd)
         ctx.save_for_backward(raw, z_vals, rays)
         ctx.noise, ctx.white = noise, white_bkgd
@@ -398,7 +445,31 @@ class _CompositeFn(torch.autograd.Function):
     def backward(ctx, g_rgb, g_disp, g_acc, g_weights, g_depth):
         raw, z_vals, rays = ctx.saved_tensors
         d_raw = ops.composite_backward(raw, z_vals, rays, ctx.noise, ctx.white, g_rgb, g_disp, g_acc, g_depth)
-        return d_raw, None, None, None, None
+        # the rays enter through dists * |rays_d| only (R:283): that gradient follows from d_raw
+        g_rays = ops.composite_norm_grad(d_raw, raw, ctx.noise, rays) if ctx.needs_input_grad[2] else None
+        return d_raw, None, g_rays, None, None
+
+
+class _PackRaysFn(torch.autograd.Function):
+    """The non-NDC [B, 8|11] pack of render(rays=(rays_o, rays_d)) (R:97-125) when the rays take a gradient (a learnable pose):
+    rows [o, d, near, far (, d / |d|)]; near and far are Python floats there and take none."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, near, far, use_viewdirs):
+        ctx.save_for_backward(rays_d)
+        ctx.use_viewdirs, ctx.shape_o = use_viewdirs, rays_o.shape
+        return ops.pack_rays(rays_o, rays_d, near, far, use_viewdirs, False)
+
+    @staticmethod
+    def backward(ctx, g):
+        rays_d, = ctx.saved_tensors
+        d_o, d_d = ops.pack_rays_bwd(g, rays_d, ctx.use_viewdirs)
+        return (d_o.reshape(ctx.shape_o) if ctx.needs_input_grad[0] else None,
+                d_d.reshape(rays_d.shape) if ctx.needs_input_grad[1] else None, None, None, None)
+
+
+def _needs_grad(*ts):
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in ts)
 
 
 class _RenderLossFn(torch.autograd.Function):
@@ -659,6 +730,9 @@ def render_loss(H, W, K, target_s, chunk=1024 * 32, rays=None, **kwargs):
     compositing launches (_RenderLossFn).  -> (loss, rgb, disp, acc, extras); the same values and, after loss.backward() (or
     run_nerf.backward(loss): no seed fill), the same parameter gradients bit for bit as the lines above, from 6 launches fewer.
     The maps are detached.  Batches larger than `chunk`, or an empty one, take the lines above literally."""
+    if rays is not None and _needs_grad(rays[0], rays[1]):
+        raise ops.CnerfError("render_loss: gradients w.r.t. rays are not implemented on the folded-loss route (the loss leaves the "
+                             "compositing launches); use render(rays=...) + img2mse")
     n = rays[0].reshape(-1, 3).shape[0] if rays is not None else 0
     tgt = target_s.reshape(-1, 3) if torch.is_tensor(target_s) else None
     if (rays is None or n == 0 or n > min(chunk, ops.composite_mse_max_rays()) or tgt is None or not tgt.is_cuda or tgt.dtype != torch.float32 or tgt.shape[0] != n
@@ -694,7 +768,14 @@ def _ray_batch(H, W, K, rays, c2w, ndc, near, far, use_viewdirs, c2w_staticcam, 
             return pk.rows, (pk.rows.shape[0],)
         rays_o, rays_d = rays
         sh = tuple(rays_d.shape[:-1])
-        batch = ops.pack_rays(rays_o.to(device), rays_d.to(device), near_s, far_s, use_viewdirs, ndc, coef)
+        if _needs_grad(rays_o, rays_d):      # rays of a learnable pose: the pack as an autograd node
+            if ndc:
+                raise ops.CnerfError("render(rays=..., ndc=True): gradients w.r.t. rays through the NDC warp are not implemented "
+                                     "(ndc=False has them)")
+            batch = _PackRaysFn.apply(rays_o.to(device=device, dtype=torch.float32), rays_d.to(device=device, dtype=torch.float32),
+                                      near_s, far_s, bool(use_viewdirs))
+        else:
+            batch = ops.pack_rays(rays_o.to(device), rays_d.to(device), near_s, far_s, use_viewdirs, ndc, coef)
     if torch.is_tensor(near):
         batch[:, 6] = near.reshape(-1).to(batch)
     if torch.is_tensor(far):
@@ -810,6 +891,11 @@ def _render_camera(H, W, K, chunk, c2w, ndc, near, far, use_viewdirs, with_depth
 def _render(H, W, K, chunk, rays, c2w, ndc, near, far, use_viewdirs, c2w_staticcam, with_depth, kwargs):
     net = kwargs.get("network_fn")
     device = next(net.parameters()).device if net is not None else _default_device()
+    if _needs_grad(c2w):
+        raise ops.CnerfError("render(c2w=...) with c2w requiring grad: gradients w.r.t. a camera pose are not implemented — build "
+                             "the rays from the pose with get_rays and pass render(rays=(rays_o, rays_d), ndc=False)")
+    if _needs_grad(c2w_staticcam):
+        raise ops.CnerfError("render(c2w_staticcam=...) requiring grad: gradients w.r.t. the static camera are not implemented")
     if _camera_path_ok(rays, c2w, near, far, use_viewdirs, c2w_staticcam, kwargs):
         kw = {k: v for k, v in kwargs.items()}
         all_ret = _render_camera(H, W, K, chunk, c2w, ndc, near, far, use_viewdirs, with_depth, kw)
@@ -1049,6 +1135,9 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     valid dummy rays whose loss weight is 0): the MLP training kernels stop at the count, which never visits the host."""
     rays = ray_batch if ray_batch.is_contiguous() else ray_batch.contiguous()
     N_rays, dev = rays.shape[0], rays.device
+    if _needs_grad(rays) and (_target is not None or _live is not None):
+        raise ops.CnerfError("render_rays: gradients w.r.t. rays are not implemented on the folded-loss routes (render_loss, "
+                             "ss_step_loss) or for a `live` batch; use render(rays=...) and form the loss from its maps")
     two = N_importance > 0
     if N_rays == 0:   # nothing to launch (the reference's batchify_rays raises on an empty batch; here: empty maps)
         last = network_fn if (network_fine is None or not two) else network_fine

@@ -33,6 +33,8 @@ extern "C" {
                                 * cnerf_lpips_seeds, cnerf_composite_bwd_closs_lpips); append-only.
                                 * 6: + the standard-normal stream beside the uniform one: cnerf_normal_rng, and cnerf_density_noise_rng (the density
                                 * noise R:287-288 of both levels of a render_rays call as one launch); append-only.
+                                * 6: + input gradients behind the existing backward: cnerf_mlp_input_grad, cnerf_rays_input_grad,
+                                * cnerf_composite_norm_grad, cnerf_pack_rays_bwd; append-only.
                                 * 6: + the in-loop consistency step as ONE render whose row count lives on the device: cnerf_ss_batch (the combined
                                 * batch + its live-row count), cnerf_mlp_fwd_live / cnerf_mlp_bwd_live / cnerf_mlp_bwd_pair_live (launches of a fixed
                                 * capacity that stop at a device-side count), cnerf_closs_finish_ss2 (the two-segment loss tail); cnerf_closs gains
@@ -775,6 +777,26 @@ int cnerf_depthvis(const float* disp, const float* acc, int64_t N, int64_t H, in
 int64_t cnerf_eval_prep_ws_bytes(int64_t N, int64_t H, int64_t W);
 int cnerf_eval_prep(const float* pred, const float* gt, const float* mask, int64_t N, int64_t H, int64_t W, float* ssim_pred,
                     float* ssim_gt, float* lpips_pred, float* lpips_gt, double* sums, void* workspace, void* stream);
+
+/* ---- input gradients: sample points, view directions and rays (autograd of R:37-52 w.r.t. its inputs, of R:97-125 / R:384 / R:283
+ * w.r.t. rays_o, rays_d) ----------------------------------------------------------------------------------------------------------- */
+/* After cnerf_mlp_dgrad[_bf] (or cnerf_mlp_bwd) of the same level, on the same stream, workspace and stash; `packed` = the fp32
+ * buffer of cnerf_pack_weights.  d_pts [B*S, 3] = d loss / d sample position, d_dirs_pt [B*S, 3] (nullable; view-direction networks
+ * only) = the per-point gradient w.r.t. the ray's view direction.  The encoding Jacobian uses the stashed sin / cos values.  Exact
+ * fp32 MFMA, no atomics.  B, S > 0. */
+int cnerf_mlp_input_grad(const cnerf_net* net, const float* packed, int64_t B, int S, const float* stash, const float* workspace,
+                         float* d_pts, float* d_dirs_pt, void* stream);
+/* Per-ray sums of the above, one wave per ray in a fixed order, written at out_stride floats per ray: d_o = sum_s d_pts and
+ * d_d = sum_s z[b, s] d_pts (both or neither; x = o + d z, R:384), d_viewdirs = sum_s d_dirs_pt (nullable).  At least one. */
+int cnerf_rays_input_grad(const float* d_pts, const float* d_dirs_pt, const float* z, int64_t B, int S, float* d_o, float* d_d,
+                          float* d_viewdirs, int out_stride, void* stream);
+/* Gradient of raw2outputs w.r.t. rays_d through dists * |rays_d| (R:283), from the d_raw of cnerf_composite_bwd:
+ * d_d [B rows of out_stride floats] = (d / n) (1 / n) sum_s d_raw[b, s, 3] max(raw[b, s, 3] + noise[b, s], 0), n = |d|.  noise nullable. */
+int cnerf_composite_norm_grad(const float* d_raw, const float* raw, int raw_ch, const float* noise, const float* rays, int ray_stride,
+                              int64_t B, int S, float* d_d, int out_stride, void* stream);
+/* Backward of the non-NDC cnerf_pack_rays: g [B, 8 | 11] -> d_o [B, 3] = g[:, 0:3], d_d [B, 3] = g[:, 3:6] (+ the Jacobian of
+ * viewdirs = d / |d| applied to g[:, 8:11] with use_viewdirs).  The near / far columns carry nothing. */
+int cnerf_pack_rays_bwd(const float* g, const float* rays_d, int64_t B, int use_viewdirs, float* d_o, float* d_d, void* stream);
 
 #ifdef __cplusplus
 }
