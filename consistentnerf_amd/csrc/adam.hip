@@ -6,12 +6,17 @@
 #include "common.hpp"
 
 namespace {
+// clip_grad_value_ is clamp_(-clip, clip), which keeps NaN: fminf / fmaxf return their other operand for one, which would turn a
+// NaN gradient into -clip and let the step go on.  Two compares and selects: NaN fails both and passes through; +-inf clip to
+// +-clip; every other input gives fminf(fmaxf(g, -clip), clip)'s bits.
+__device__ __forceinline__ float clamp_keep_nan(float g, float clip) { return g < -clip ? -clip : (g > clip ? clip : g); }
+
 __global__ void adam_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                        float* __restrict__ v, int64_t n, float w1, float beta2, float w2, float step_size,
                        float bc2_sqrt, float eps, float clip, float gscale) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float gi = g[i] * gscale;
-    if (clip > 0.f) gi = fminf(fmaxf(gi, -clip), clip);
+    if (clip > 0.f) gi = clamp_keep_nan(gi, clip);
     const float mi = m[i] + w1 * (gi - m[i]);               // exp_avg.lerp_(grad, 1-beta1)
     const float vi = v[i] * beta2 + w2 * (gi * gi);         // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1-beta2)
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
@@ -28,7 +33,7 @@ __global__ void adam_dev_k(float* __restrict__ p, const float* __restrict__ g, f
               gscale = hyp[7];
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float gi = g[i] * gscale;
-    if (clip > 0.f) gi = fminf(fmaxf(gi, -clip), clip);
+    if (clip > 0.f) gi = clamp_keep_nan(gi, clip);
     const float mi = m[i] + w1 * (gi - m[i]);
     const float vi = v[i] * beta2 + w2 * (gi * gi);
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
