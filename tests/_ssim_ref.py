@@ -7,7 +7,10 @@ import torch.nn.functional as F
 MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 
 
-def window(win_size=11, win_sigma=1.5, dtype=torch.float64):
+def window(win_size=11, win_sigma=1.5, dtype=torch.float64, taps=None):
+    """taps (optional): the window as given numbers (the library's fp32 taps, say), cast to dtype instead of being computed in it."""
+    if taps is not None:
+        return torch.as_tensor(taps).to(dtype)
     coords = torch.arange(win_size, dtype=dtype) - win_size // 2
     g = torch.exp(-(coords ** 2) / (2 * win_sigma ** 2))
     return g / g.sum()
@@ -24,10 +27,10 @@ def gfilter(x, g):
     return x
 
 
-def maps(X, Y, data_range=255, win_size=11, win_sigma=1.5, K=(0.01, 0.03)):
-    """-> (ssim_map, cs_map) with single-pass variances."""
-    g = window(win_size, win_sigma, X.dtype)
-    C1, C2 = (K[0] * data_range) ** 2, (K[1] * data_range) ** 2
+def maps(X, Y, data_range=255, win_size=11, win_sigma=1.5, K=(0.01, 0.03), taps=None, consts=None):
+    """-> (ssim_map, cs_map) with single-pass variances.  taps: see window(); consts (optional) = (C1, C2) as given numbers."""
+    g = window(win_size, win_sigma, X.dtype, taps)
+    C1, C2 = ((K[0] * data_range) ** 2, (K[1] * data_range) ** 2) if consts is None else consts
     mu1, mu2 = gfilter(X, g), gfilter(Y, g)
     mu1_sq, mu2_sq, mu1_mu2 = mu1.pow(2), mu2.pow(2), mu1 * mu2
     s11 = gfilter(X * X, g) - mu1_sq
