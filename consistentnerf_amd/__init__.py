@@ -6,4 +6,4 @@ CnerfError if it is missing (there is no CPU fallback)."""
 from ._lib import CnerfError  # noqa: F401
 from .ops import NetSpec  # noqa: F401
 
-__all__ = ["CnerfError", "NetSpec", "run_nerf", "run_nerf_view", "run_nerf_helpers", "ops", "optim", "distributed"]
+__all__ = ["CnerfError", "NetSpec", "run_nerf", "run_nerf_view", "run_nerf_helpers", "ops", "optim", "distributed", "pose"]

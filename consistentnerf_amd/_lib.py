@@ -224,6 +224,11 @@ SIGNATURES = {
     "cnerf_rays_input_grad": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _i, _vp]),
     "cnerf_composite_norm_grad": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i64, _i, _vp, _i, _vp]),
     "cnerf_pack_rays_bwd": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "cnerf_gen_rays_at": (_i, [_i, _i, _f, _f, _f, _f, _vp, _i, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "cnerf_gen_rays_at_bwd_ws_floats": (_i64, [_i64, _i]),
+    "cnerf_gen_rays_at_bwd": (_i, [_i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp, _i64, _i64, _vp, _vp, _i, _vp]),
+    "cnerf_pose_compose": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "cnerf_pose_compose_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -942,6 +942,85 @@ def pack_rays_bwd(g: Tensor, rays_d: Tensor, use_viewdirs: bool):
     return d_o, d_d
 
 
+def _rays_at_args(who: str, H: int, W: int, n_views: int, coords: Optional[Tensor], view: Optional[Tensor], first: int, B: Optional[int]):
+    """(coords, view, B) of a cnerf_gen_rays_at[_bwd] call: int64 device tensors or None, B from coords / view / the caller.  The VALUES
+    of coords and view are not checked (a check would be a device-to-host sync): in range is the caller's duty, as for select_inds."""
+    coords, view = _chk(coords, "coords", dtype=torch.int64), _chk(view, "view", dtype=torch.int64)
+    if coords is not None:
+        if coords.dim() != 2 or coords.shape[1] != 2:
+            raise CnerfError(f"{who}: coords must be [B, 2] (row, col), got {tuple(coords.shape)}")
+        if B is not None and B != coords.shape[0]:
+            raise CnerfError(f"{who}: B = {B} but coords has {coords.shape[0]} rows")
+        B = coords.shape[0]
+    elif B is None:
+        B = H * W - first if view is None else view.numel()
+    if view is not None and tuple(view.shape) != (B,):
+        raise CnerfError(f"{who}: view must be [{B}], got {tuple(view.shape)}")
+    if B <= 0 or n_views <= 0 or (coords is None and (first < 0 or first + B > H * W)):
+        raise CnerfError(f"{who}: B = {B}, n_views = {n_views}, first = {first} on a {H} x {W} image")
+    return coords, view, B
+
+
+def gen_rays_at(H: int, W: int, K, c2w: Tensor, coords: Optional[Tensor] = None, view: Optional[Tensor] = None, first: int = 0,
+                B: Optional[int] = None):
+    """cnerf_gen_rays_at: (rays_o [B, 3], rays_d [B, 3]) of H:164-173 from poses c2w [n_views, 12] (row-major 3 x 4 each) that stay
+    in device memory.  coords: int64 [B, 2] = (row, col), or None: the B row-major pixels from `first` on; view: int64 [B] or None
+    (view 0)."""
+    c2w = _chk(c2w, "c2w")
+    if c2w.dim() != 2 or c2w.shape[1] != 12:
+        raise CnerfError(f"gen_rays_at: c2w must be [n_views, 12], got {tuple(c2w.shape)}")
+    coords, view, B = _rays_at_args("gen_rays_at", H, W, c2w.shape[0], coords, view, first, B)
+    o, d = torch.empty(B, 3, device=c2w.device), torch.empty(B, 3, device=c2w.device)
+    _lib.check(_lib.load().cnerf_gen_rays_at(H, W, *_intrinsics(K), _p(c2w), c2w.shape[0], _p(coords), _p(view), first, B, _p(o), _p(d),
+                                             _stream()), "cnerf_gen_rays_at")
+    return o, d
+
+
+def gen_rays_at_bwd(d_rays_o: Tensor, d_rays_d: Tensor, H: int, W: int, K, n_views: int, coords: Optional[Tensor] = None,
+                    view: Optional[Tensor] = None, first: int = 0, grid: int = 0) -> Tensor:
+    """cnerf_gen_rays_at_bwd: d_c2w [n_views, 12] from (d_rays_o, d_rays_d) [B, 3] of the gen_rays_at call with the same coords, view
+    and first.  The same bits call after call and for every `grid` (workgroups of the first launch, 0 = chosen by the library)."""
+    d_o, d_d = _chk(d_rays_o.reshape(-1, 3), "d_rays_o"), _chk(d_rays_d.reshape(-1, 3), "d_rays_d")
+    if d_o.shape != d_d.shape:
+        raise CnerfError(f"gen_rays_at_bwd: d_rays_o is {tuple(d_o.shape)}, d_rays_d {tuple(d_d.shape)}")
+    coords, view, B = _rays_at_args("gen_rays_at_bwd", H, W, n_views, coords, view, first, d_o.shape[0])
+    lib = _lib.load()
+    ws = torch.empty(lib.cnerf_gen_rays_at_bwd_ws_floats(B, n_views) // 2, device=d_o.device, dtype=torch.float64)
+    d_c2w = torch.empty(n_views, 12, device=d_o.device)
+    _lib.check(lib.cnerf_gen_rays_at_bwd(H, W, *_intrinsics(K), _p(d_o), _p(d_d), n_views, _p(coords), _p(view), first, B, _p(d_c2w),
+                                         _p(ws), int(grid), _stream()), "cnerf_gen_rays_at_bwd")
+    return d_c2w
+
+
+def _pose_args(who: str, c2w0: Tensor, rot: Tensor, more: Tensor, more_name: str, more_cols: int):
+    c2w0, rot, more = _chk(c2w0, "c2w0"), _chk(rot, "rot"), _chk(more, more_name)
+    N = rot.shape[0] if rot.dim() == 2 else -1
+    if N <= 0 or rot.shape[1] != 3 or c2w0.numel() != N * 12 or more.numel() != N * more_cols:
+        raise CnerfError(f"{who}: c2w0 {tuple(c2w0.shape)}, rot {tuple(rot.shape)}, {more_name} {tuple(more.shape)} are not "
+                         f"[N, 3, 4], [N, 3], [N, {more_cols}]")
+    return c2w0, rot, more, N
+
+
+def pose_compose(c2w0: Tensor, rot: Tensor, trans: Tensor) -> Tensor:
+    """cnerf_pose_compose: c2w [N, 3, 4] = [Exp(rot[n]) R0_n | t0_n + trans[n]] from c2w0 [N, 3, 4], rot (axis-angle) and trans [N, 3]."""
+    c2w0, rot, trans, N = _pose_args("pose_compose", c2w0, rot, trans, "trans", 3)
+    c2w = torch.empty(N, 3, 4, device=rot.device)
+    _lib.check(_lib.load().cnerf_pose_compose(_p(c2w0), _p(rot), _p(trans), N, _p(c2w), _stream()), "cnerf_pose_compose")
+    return c2w
+
+
+def pose_compose_bwd(c2w0: Tensor, rot: Tensor, d_c2w: Tensor, want_rot: bool = True, want_trans: bool = True):
+    """cnerf_pose_compose_bwd: d_c2w [N, 3, 4] (or [N, 12]) -> (d_rot [N, 3] | None, d_trans [N, 3] | None)."""
+    c2w0, rot, d_c2w, N = _pose_args("pose_compose_bwd", c2w0, rot, d_c2w, "d_c2w", 12)
+    if not (want_rot or want_trans):
+        return None, None
+    d_rot = torch.empty(N, 3, device=rot.device) if want_rot else None
+    d_trans = torch.empty(N, 3, device=rot.device) if want_trans else None
+    _lib.check(_lib.load().cnerf_pose_compose_bwd(_p(c2w0), _p(rot), _p(d_c2w), N, _p(d_rot), _p(d_trans), _stream()),
+               "cnerf_pose_compose_bwd")
+    return d_rot, d_trans
+
+
 def sample_pixels(H: int, W: int, K, c2w, near: float, far: float, use_viewdirs: bool, ndc: bool, ndc_coef, crop, patch_starts,
                   patch_size: int, n_rand: int, select_inds: Optional[Tensor], rng: Optional[RngStream], image: Tensor,
                   extras: Sequence[Tensor] = (), want_rows: bool = True, want_od: bool = True, want_coords: bool = True):

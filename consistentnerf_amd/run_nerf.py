@@ -20,7 +20,7 @@ import torch
 
 from . import ops
 from .optim import FusedAdam
-from .run_nerf_helpers import (NeRF, get_embedder, get_rays, img2mse, mse2psnr, ndc_coefficients,  # noqa: F401
+from .run_nerf_helpers import (NeRF, get_embedder, get_rays, get_rays_at, img2mse, mse2psnr, ndc_coefficients,  # noqa: F401
                                get_rays_np, ndc_rays, pytest_uniform, sample_pdf, sample_u, to8b)
 
 DEBUG = False

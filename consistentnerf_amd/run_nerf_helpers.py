@@ -190,10 +190,57 @@ def _dev(t=None):
     return torch.device("cuda", torch.cuda.current_device())
 
 
+class _RaysAtFn(torch.autograd.Function):
+    """H:164-173 from poses that stay on the device (ops.gen_rays_at), differentiable in the poses (ops.gen_rays_at_bwd: a
+    deterministic two-stage fp64 reduction over the rays).  c2w: [3,4] | [4,4] | [N,3,4] | [N,4,4]; the bottom row of a 4 x 4 pose
+    gets a zero gradient."""
+
+    @staticmethod
+    def forward(ctx, c2w, H, W, K, coords, view, first, B):
+        top = c2w.detach()[..., :3, :4]
+        c12 = top.reshape(-1, 12)
+        ctx.meta = (H, W, K, c12.shape[0], first, tuple(c2w.shape))
+        ctx.save_for_backward(coords, view)
+        return ops.gen_rays_at(H, W, K, c12, coords, view, first, B)
+
+    @staticmethod
+    def backward(ctx, g_o, g_d):      # (autograd hands zeros for a ray half the loss does not reach)
+        H, W, K, n_views, first, shape = ctx.meta
+        coords, view = ctx.saved_tensors
+        d = ops.gen_rays_at_bwd(g_o, g_d, H, W, K, n_views, coords, view, first)
+        if shape[-2] == 3:
+            return (d.reshape(shape),) + (None,) * 7
+        full = torch.zeros(shape, device=d.device, dtype=d.dtype)
+        full[..., :3, :] = d.reshape(shape[:-2] + (3, 4))
+        return (full,) + (None,) * 7
+
+
+def _pose_tensor(c2w, who):
+    if not (torch.is_tensor(c2w) and c2w.is_cuda):
+        raise ops.CnerfError(f"{who}: c2w must be a tensor on the GPU (the pose is read in device memory)")
+    if c2w.dim() not in (2, 3) or c2w.shape[-1] != 4 or c2w.shape[-2] not in (3, 4) or c2w.dtype != torch.float32:
+        raise ops.CnerfError(f"{who}: c2w must be float32 [3,4], [4,4], [N,3,4] or [N,4,4], got {c2w.dtype} {tuple(c2w.shape)}")
+    return c2w
+
+
 def get_rays(H, W, K, c2w):
-    """H:164-173 -> (rays_o [H,W,3], rays_d [H,W,3]) on the GPU."""
+    """H:164-173 -> (rays_o [H,W,3], rays_d [H,W,3]) on the GPU.  A device pose that requires grad (with grad mode on) keeps its
+    graph: the same values, from the pose in device memory, and `c2w.grad` after a backward through the rays."""
+    if torch.is_tensor(c2w) and c2w.is_cuda and c2w.requires_grad and torch.is_grad_enabled():
+        if _pose_tensor(c2w, "get_rays").dim() != 2:
+            raise ops.CnerfError("get_rays takes one pose ([3,4] or [4,4]); get_rays_at takes [N,3,4] with a view per ray")
+        o, d = _RaysAtFn.apply(c2w, H, W, K, None, None, 0, H * W)
+        return o.reshape(H, W, 3), d.reshape(H, W, 3)
     rays = ops.gen_rays(H, W, K, c2w, 0., 1., False, False, _dev(c2w))
     return rays[:, 0:3].reshape(H, W, 3), rays[:, 3:6].reshape(H, W, 3)
+
+
+def get_rays_at(H, W, K, c2w, coords, view=None):
+    """The get_rays pair of chosen pixels only: (rays_o [B,3], rays_d [B,3]) for coords [B,2] = (row, col) (what raybank /
+    ops.sample_pixels(want_coords=True) return, the reference's select_coords R:744-747), from device poses c2w [3,4] | [4,4] |
+    [N,3,4] | [N,4,4] with view [B] (int64; None = pose 0) naming each ray's pose.  Differentiable in c2w; the pose never leaves
+    the device.  In-range coords and view are the caller's duty (not checked: that would be a host sync)."""
+    return _RaysAtFn.apply(_pose_tensor(c2w, "get_rays_at"), H, W, K, coords, view, 0, None)
 
 
 def get_rays_np(H, W, K, c2w):

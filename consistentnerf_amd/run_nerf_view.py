@@ -23,7 +23,7 @@ import torch
 from . import ops
 from . import run_nerf as _R
 from .run_nerf import (batchify, batchify_rays, raw2outputs, run_network)  # noqa: F401
-from .run_nerf_helpers import (NeRF, get_embedder, get_rays, get_rays_np, img2mse, mse2psnr, ndc_coefficients,  # noqa: F401
+from .run_nerf_helpers import (NeRF, get_embedder, get_rays, get_rays_at, get_rays_np, img2mse, mse2psnr, ndc_coefficients,  # noqa: F401
                                ndc_rays, sample_pdf, to8b)
 
 

@@ -35,6 +35,9 @@ extern "C" {
                                 * noise R:287-288 of both levels of a render_rays call as one launch); append-only.
                                 * 6: + input gradients behind the existing backward: cnerf_mlp_input_grad, cnerf_rays_input_grad,
                                 * cnerf_composite_norm_grad, cnerf_pack_rays_bwd; append-only.
+                                * 6: + camera pose gradients: cnerf_gen_rays_at / cnerf_gen_rays_at_bwd (+ cnerf_gen_rays_at_bwd_ws_floats), the rays of
+                                * chosen pixels from poses in device memory and their backward, and cnerf_pose_compose / cnerf_pose_compose_bwd;
+                                * append-only.
                                 * 6: + the in-loop consistency step as ONE render whose row count lives on the device: cnerf_ss_batch (the combined
                                 * batch + its live-row count), cnerf_mlp_fwd_live / cnerf_mlp_bwd_live / cnerf_mlp_bwd_pair_live (launches of a fixed
                                 * capacity that stop at a device-side count), cnerf_closs_finish_ss2 (the two-segment loss tail); cnerf_closs gains
@@ -797,6 +800,35 @@ int cnerf_composite_norm_grad(const float* d_raw, const float* raw, int raw_ch, 
 /* Backward of the non-NDC cnerf_pack_rays: g [B, 8 | 11] -> d_o [B, 3] = g[:, 0:3], d_d [B, 3] = g[:, 3:6] (+ the Jacobian of
  * viewdirs = d / |d| applied to g[:, 8:11] with use_viewdirs).  The near / far columns carry nothing. */
 int cnerf_pack_rays_bwd(const float* g, const float* rays_d, int64_t B, int use_viewdirs, float* d_o, float* d_d, void* stream);
+
+/* ---- camera pose gradients: get_rays (H:164-173) from poses in device memory, w.r.t. the poses ------------------------------------ */
+/* H:164-173 for B chosen pixels: rays_o [B, 3] = c2w[:3, -1] and rays_d [B, 3] (pre-NDC, not normalised: what cnerf_pack_rays makes
+ * rows from) of the view's pose, the same bits as cnerf_gen_rays for the same pose and pixel.  c2w: DEVICE [n_views, 12], each view a
+ * row-major 3 x 4 pose; nothing is copied to the host and nothing synchronises.  coords: device int64 [B, 2] = (row, col), as
+ * cnerf_sample_pixels writes them; NULL: ray b is row-major pixel first + b (0 <= first, first + B <= H W; `first` is ignored with
+ * coords).  view: device int64 [B]; NULL: every ray uses view 0.  Values of coords outside the image and of view outside
+ * [0, n_views) are the CALLER's duty (as for select_inds): they are not checked, and an out-of-range view reads outside c2w.
+ * B, n_views, H, W > 0, fx, fy != 0. */
+int cnerf_gen_rays_at(int H, int W, float fx, float fy, float cx, float cy, const float* c2w, int n_views, const int64_t* coords,
+                      const int64_t* view, int64_t first, int64_t B, float* rays_o, float* rays_d, void* stream);
+/* Autograd of the above w.r.t. c2w (H:170, H:172): d_c2w [n_views, 12], d_R[r][k] = sum_b d_rays_d[b][r] dirs_b[k] with dirs_b =
+ * ((col - cx) / fx, -(row - cy) / fy, -1) recomputed, d_t[r] = sum_b d_rays_o[b][r], each over the rays of that view; a view without a
+ * ray gets zeros (a view value outside [0, n_views) contributes nowhere).  Every element of d_c2w is written.  Two launches: fp64
+ * sums of fixed chunks of 64 rays, then one wave per view over the chunks in order, rounded to fp32 once — no atomics, the same bits
+ * call after call and for every grid.  workspace = cnerf_gen_rays_at_bwd_ws_floats(B, n_views) floats (0 for B or n_views <= 0),
+ * 8-byte aligned.  grid: workgroups of the first launch, 0 = chosen here. */
+int64_t cnerf_gen_rays_at_bwd_ws_floats(int64_t B, int n_views);
+int cnerf_gen_rays_at_bwd(int H, int W, float fx, float fy, float cx, float cy, const float* d_rays_o, const float* d_rays_d, int n_views,
+                          const int64_t* coords, const int64_t* view, int64_t first, int64_t B, float* d_c2w, float* workspace, int grid,
+                          void* stream);
+/* (No reference lines: the reference optimises no pose.)  c2w [n_views, 12] = [Exp(rot[n]) R0_n | t0_n + trans[n]] from c2w0
+ * [n_views, 12], rot [n_views, 3] (axis-angle, Rodrigues' formula) and trans [n_views, 3], one launch for all views; at rot = 0 the
+ * rotation is R0's own bits.  cnerf_pose_compose_bwd: d_c2w [n_views, 12] -> d_rot, d_trans [n_views, 3] (either nullable, not both);
+ * at rot = 0 d_rot is the three generators applied to R0.  Small angles lose no digits in value or gradient (series below
+ * theta = 1, half-angle forms above: csrc/rays_grad.hip). */
+int cnerf_pose_compose(const float* c2w0, const float* rot, const float* trans, int n_views, float* c2w, void* stream);
+int cnerf_pose_compose_bwd(const float* c2w0, const float* rot, const float* d_c2w, int n_views, float* d_rot, float* d_trans,
+                           void* stream);
 
 #ifdef __cplusplus
 }
