@@ -229,6 +229,10 @@ SIGNATURES = {
     "cnerf_gen_rays_at_bwd": (_i, [_i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp, _i64, _i64, _vp, _vp, _i, _vp]),
     "cnerf_pose_compose": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "cnerf_pose_compose_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "cnerf_camera_rows": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp, _i64, _i64, _f, _f, _i, _i, _vp, _vp]),
+    "cnerf_camera_rows_bwd_ws_floats": (_i64, [_i64, _i]),
+    "cnerf_camera_rows_bwd": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "cnerf_ndc_rays_bwd": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _vp, _vp, _vp]),
 }
 
 _lib = None

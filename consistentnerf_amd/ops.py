@@ -1021,6 +1021,77 @@ def pose_compose_bwd(c2w0: Tensor, rot: Tensor, d_c2w: Tensor, want_rot: bool = 
     return d_rot, d_trans
 
 
+def _camera_intrinsics(who: str, K, ndc_coef):
+    """(fx, fy, cx, cy, ax, ay, K_dev) of a cnerf_camera_rows[_bwd] call.  A float32 [3, 3] tensor on the GPU is handed over as a
+    pointer and read in the kernel (no copy to the host; the six floats are placeholders it overrides); anything else is a host
+    3 x 3 whose floats go in, with the two NDC coefficients the caller formed."""
+    if torch.is_tensor(K) and K.is_cuda:
+        if K.dtype != torch.float32 or tuple(K.shape) != (3, 3):
+            raise CnerfError(f"{who}: a device K must be float32 [3, 3], got {K.dtype} {tuple(K.shape)}")
+        return (1.0, 1.0, 0.0, 0.0, 0.0, 0.0), K.detach().contiguous()
+    return _intrinsics(K) + (float(ndc_coef[0]), float(ndc_coef[1])), None
+
+
+def _camera_c2w(who: str, c2w: Tensor) -> Tensor:
+    c2w = _chk(c2w, "c2w")
+    if c2w.dim() != 2 or c2w.shape[1] != 12:
+        raise CnerfError(f"{who}: c2w must be [n_views, 12], got {tuple(c2w.shape)}")
+    return c2w
+
+
+def camera_rows(H: int, W: int, K, c2w: Tensor, coords: Optional[Tensor] = None, view: Optional[Tensor] = None, near: float = 0.,
+                far: float = 1., use_viewdirs: bool = False, ndc: bool = True, ndc_coef=(0.0, 0.0), first: int = 0,
+                B: Optional[int] = None) -> Tensor:
+    """cnerf_camera_rows: the finished rows [B, 8 | 11] = [o, d, near, far (, viewdirs)] of render()'s batch (H:164-173, R:103-116,
+    H:186-202) in one launch, from poses c2w [n_views, 12] in device memory; coords / view / first / B as gen_rays_at.  K: a host
+    3 x 3 (with ndc_coef = the two coefficients of H:193-199), or a float32 [3, 3] tensor on the GPU, read there (ndc_coef is then
+    ignored: the kernel forms the coefficients from K[0][0])."""
+    c2w = _camera_c2w("camera_rows", c2w)
+    coords, view, B = _rays_at_args("camera_rows", H, W, c2w.shape[0], coords, view, first, B)
+    intr, K_dev = _camera_intrinsics("camera_rows", K, ndc_coef)
+    rows = torch.empty(B, 11 if use_viewdirs else 8, device=c2w.device)
+    _lib.check(_lib.load().cnerf_camera_rows(H, W, *intr, _p(K_dev), _p(c2w), c2w.shape[0], _p(coords), _p(view), first, B, float(near),
+                                             float(far), int(use_viewdirs), int(ndc), _p(rows), _stream()), "cnerf_camera_rows")
+    return rows
+
+
+def camera_rows_bwd(g: Tensor, H: int, W: int, K, c2w: Tensor, coords: Optional[Tensor] = None, view: Optional[Tensor] = None,
+                    use_viewdirs: bool = False, ndc: bool = True, ndc_coef=(0.0, 0.0), first: int = 0, want_c2w: bool = True,
+                    want_K: bool = True, grid: int = 0):
+    """cnerf_camera_rows_bwd: the row gradient g [B, 8 | 11] of the camera_rows call with the same arguments -> (d_c2w [n_views, 12]
+    | None, d_K [3, 3] | None).  The same bits call after call and for every `grid` (workgroups of the first launch, 0 = chosen by
+    the library)."""
+    c2w, g = _camera_c2w("camera_rows_bwd", c2w), _chk(g, "g")
+    cols = 11 if use_viewdirs else 8
+    if g.dim() != 2 or g.shape[1] != cols:
+        raise CnerfError(f"camera_rows_bwd: g must be [B, {cols}], got {tuple(g.shape)}")
+    n_views = c2w.shape[0]
+    coords, view, B = _rays_at_args("camera_rows_bwd", H, W, n_views, coords, view, first, g.shape[0])
+    if not (want_c2w or want_K):
+        return None, None
+    intr, K_dev = _camera_intrinsics("camera_rows_bwd", K, ndc_coef)
+    lib = _lib.load()
+    ws = torch.empty(lib.cnerf_camera_rows_bwd_ws_floats(B, n_views) // 2, device=g.device, dtype=torch.float64)
+    d_c2w = torch.empty(n_views, 12, device=g.device) if want_c2w else None
+    d_K = torch.empty(3, 3, device=g.device) if want_K else None
+    _lib.check(lib.cnerf_camera_rows_bwd(H, W, *intr, _p(K_dev), _p(c2w), n_views, _p(coords), _p(view), first, B, int(use_viewdirs),
+                                         int(ndc), _p(g), _p(d_c2w), _p(d_K), _p(ws), int(grid), _stream()), "cnerf_camera_rows_bwd")
+    return d_c2w, d_K
+
+
+def ndc_rays_bwd(g_o: Tensor, g_d: Tensor, rays_o: Tensor, rays_d: Tensor, ndc_coef):
+    """cnerf_ndc_rays_bwd: the gradients (g_o, g_d) [B, 3] of ndc_rays' outputs and its inputs (rays_o, rays_d) [B, 3] ->
+    (d_rays_o, d_rays_d) [B, 3]."""
+    ts = [_chk(t.reshape(-1, 3), n) for t, n in ((g_o, "g_o"), (g_d, "g_d"), (rays_o, "rays_o"), (rays_d, "rays_d"))]
+    B = ts[0].shape[0]
+    if B <= 0 or any(t.shape[0] != B for t in ts):
+        raise CnerfError(f"ndc_rays_bwd: g_o, g_d, rays_o, rays_d are {[tuple(t.shape) for t in ts]}, not four [B, 3] with B > 0")
+    d_o, d_d = torch.empty_like(ts[2]), torch.empty_like(ts[3])
+    _lib.check(_lib.load().cnerf_ndc_rays_bwd(*map(_p, ts), B, float(ndc_coef[0]), float(ndc_coef[1]), _p(d_o), _p(d_d), _stream()),
+               "cnerf_ndc_rays_bwd")
+    return d_o, d_d
+
+
 def sample_pixels(H: int, W: int, K, c2w, near: float, far: float, use_viewdirs: bool, ndc: bool, ndc_coef, crop, patch_starts,
                   patch_size: int, n_rand: int, select_inds: Optional[Tensor], rng: Optional[RngStream], image: Tensor,
                   extras: Sequence[Tensor] = (), want_rows: bool = True, want_od: bool = True, want_coords: bool = True):

@@ -771,7 +771,8 @@ def _ray_batch(H, W, K, rays, c2w, ndc, near, far, use_viewdirs, c2w_staticcam, 
         if _needs_grad(rays_o, rays_d):      # rays of a learnable pose: the pack as an autograd node
             if ndc:
                 raise ops.CnerfError("render(rays=..., ndc=True): gradients w.r.t. rays through the NDC warp are not implemented "
-                                     "(ndc=False has them)")
+                                     "here (ndc=False has them) — build the NDC rows from the pose with pose.camera_rows(..., "
+                                     "ndc=True) and pass them to batchify_rays")
             batch = _PackRaysFn.apply(rays_o.to(device=device, dtype=torch.float32), rays_d.to(device=device, dtype=torch.float32),
                                       near_s, far_s, bool(use_viewdirs))
         else:
@@ -893,9 +894,11 @@ def _render(H, W, K, chunk, rays, c2w, ndc, near, far, use_viewdirs, c2w_staticc
     device = next(net.parameters()).device if net is not None else _default_device()
     if _needs_grad(c2w):
         raise ops.CnerfError("render(c2w=...) with c2w requiring grad: gradients w.r.t. a camera pose are not implemented — build "
-                             "the rays from the pose with get_rays and pass render(rays=(rays_o, rays_d), ndc=False)")
+                             "the rays from the pose with get_rays and pass render(rays=(rays_o, rays_d), ndc=False), or, with "
+                             "ndc=True or a learnable K, the rows with pose.camera_rows and pass them to batchify_rays")
     if _needs_grad(c2w_staticcam):
-        raise ops.CnerfError("render(c2w_staticcam=...) requiring grad: gradients w.r.t. the static camera are not implemented")
+        raise ops.CnerfError("render(c2w_staticcam=...) requiring grad: gradients w.r.t. the static camera are not implemented — "
+                             "pose.camera_rows + batchify_rays take a pose that requires grad")
     if _camera_path_ok(rays, c2w, near, far, use_viewdirs, c2w_staticcam, kwargs):
         kw = {k: v for k, v in kwargs.items()}
         all_ret = _render_camera(H, W, K, chunk, c2w, ndc, near, far, use_viewdirs, with_depth, kw)

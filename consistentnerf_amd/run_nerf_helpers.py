@@ -223,9 +223,55 @@ def _pose_tensor(c2w, who):
     return c2w
 
 
+class _CameraRowsFn(torch.autograd.Function):
+    """Pixel -> finished ray row [o, d, near, far (, viewdirs)] (H:164-173, R:103-116, H:186-202) as ONE node over the poses and the
+    camera matrix (ops.camera_rows / ops.camera_rows_bwd: one launch forward, two backward).  c2w as _RaysAtFn; K: a host 3 x 3, or
+    a float32 [3,3] tensor on the GPU, which is read there and takes a gradient."""
+
+    @staticmethod
+    def forward(ctx, c2w, K, H, W, coords, view, near, far, use_viewdirs, ndc, first, B):
+        c12 = c2w.detach()[..., :3, :4].reshape(-1, 12)
+        k_dev = torch.is_tensor(K) and K.is_cuda
+        coef = (0., 0.) if k_dev or not ndc else ndc_coefficients(H, W, K[0][0])
+        ctx.meta = (H, W, None if k_dev else K, coef, bool(use_viewdirs), bool(ndc), first, tuple(c2w.shape))
+        ctx.save_for_backward(c12, K.detach() if k_dev else None, coords, view)
+        return ops.camera_rows(H, W, K, c12, coords, view, near, far, use_viewdirs, ndc, coef, first, B)
+
+    @staticmethod
+    def backward(ctx, g):
+        H, W, K_host, coef, use_viewdirs, ndc, first, shape = ctx.meta
+        c12, K_dev, coords, view = ctx.saved_tensors
+        d, d_K = ops.camera_rows_bwd(g, H, W, K_host if K_dev is None else K_dev, c12, coords, view, use_viewdirs, ndc, coef, first,
+                                     want_c2w=ctx.needs_input_grad[0], want_K=K_dev is not None and ctx.needs_input_grad[1])
+        if d is not None and shape[-2] == 3:
+            d = d.reshape(shape)
+        elif d is not None:      # the bottom row of a 4 x 4 pose gets zeros
+            full = torch.zeros(shape, device=d.device, dtype=d.dtype)
+            full[..., :3, :] = d.reshape(shape[:-2] + (3, 4))
+            d = full
+        return (d, d_K) + (None,) * 10
+
+
+def _k_needs_grad(K):
+    return torch.is_tensor(K) and K.is_cuda and K.requires_grad and torch.is_grad_enabled()
+
+
+def _device_pose(c2w, K):
+    """The pose as a float32 tensor on K's device (the camera_rows kernels read it there)."""
+    if torch.is_tensor(c2w):
+        return c2w.to(device=K.device, dtype=torch.float32)
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(c2w, dtype=np.float32))).to(K.device)
+
+
 def get_rays(H, W, K, c2w):
     """H:164-173 -> (rays_o [H,W,3], rays_d [H,W,3]) on the GPU.  A device pose that requires grad (with grad mode on) keeps its
-    graph: the same values, from the pose in device memory, and `c2w.grad` after a backward through the rays."""
+    graph: the same values, from the pose in device memory, and `c2w.grad` after a backward through the rays.  So does a float32
+    [3,3] K tensor on the GPU that requires grad (`K.grad`, and the pose's if it requires grad too)."""
+    if _k_needs_grad(K):
+        if _pose_tensor(_device_pose(c2w, K), "get_rays").dim() != 2:
+            raise ops.CnerfError("get_rays takes one pose ([3,4] or [4,4]); get_rays_at takes [N,3,4] with a view per ray")
+        rows = _CameraRowsFn.apply(_device_pose(c2w, K), K, H, W, None, None, 0., 1., False, False, 0, H * W)
+        return rows[:, 0:3].reshape(H, W, 3), rows[:, 3:6].reshape(H, W, 3)
     if torch.is_tensor(c2w) and c2w.is_cuda and c2w.requires_grad and torch.is_grad_enabled():
         if _pose_tensor(c2w, "get_rays").dim() != 2:
             raise ops.CnerfError("get_rays takes one pose ([3,4] or [4,4]); get_rays_at takes [N,3,4] with a view per ray")
@@ -239,7 +285,11 @@ def get_rays_at(H, W, K, c2w, coords, view=None):
     """The get_rays pair of chosen pixels only: (rays_o [B,3], rays_d [B,3]) for coords [B,2] = (row, col) (what raybank /
     ops.sample_pixels(want_coords=True) return, the reference's select_coords R:744-747), from device poses c2w [3,4] | [4,4] |
     [N,3,4] | [N,4,4] with view [B] (int64; None = pose 0) naming each ray's pose.  Differentiable in c2w; the pose never leaves
-    the device.  In-range coords and view are the caller's duty (not checked: that would be a host sync)."""
+    the device.  In-range coords and view are the caller's duty (not checked: that would be a host sync).  A float32 [3,3] K tensor
+    on the GPU that requires grad is read there and gets `K.grad` as well."""
+    if _k_needs_grad(K):
+        rows = _CameraRowsFn.apply(_pose_tensor(c2w, "get_rays_at"), K, H, W, coords, view, 0., 1., False, False, 0, None)
+        return rows[:, 0:3], rows[:, 3:6]
     return _RaysAtFn.apply(_pose_tensor(c2w, "get_rays_at"), H, W, K, coords, view, 0, None)
 
 
@@ -257,11 +307,40 @@ def ndc_coefficients(H, W, focal):
     return -1. / (W / (2. * focal)), -1. / (H / (2. * focal))
 
 
+class _NdcRaysFn(torch.autograd.Function):
+    """ndc_rays (H:186-202, near plane 1) when the rays take a gradient: the forward is the cnerf_pack_rays call of the no-grad
+    route (the same bits), the backward ops.ndc_rays_bwd.  The coefficients are Python floats and take none."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, coef):
+        ctx.save_for_backward(rays_o, rays_d)
+        ctx.coef = coef
+        r = ops.pack_rays(rays_o, rays_d, 0., 1., False, True, coef)
+        return r[:, 0:3].reshape(rays_d.shape).contiguous(), r[:, 3:6].reshape(rays_d.shape).contiguous()
+
+    @staticmethod
+    def backward(ctx, g_o, g_d):      # (autograd hands zeros for a half the loss does not reach)
+        rays_o, rays_d = ctx.saved_tensors
+        d_o, d_d = ops.ndc_rays_bwd(g_o, g_d, rays_o, rays_d, ctx.coef)
+        return (d_o.reshape(rays_o.shape) if ctx.needs_input_grad[0] else None,
+                d_d.reshape(rays_d.shape) if ctx.needs_input_grad[1] else None, None)
+
+
 def ndc_rays(H, W, focal, near, rays_o, rays_d):
-    """H:186-202 (near plane 1, the only value render() passes, R:116)."""
+    """H:186-202 (near plane 1, the only value render() passes, R:116).  Rays that require grad (with grad mode on) keep their
+    graph: the same values, and their gradients from cnerf_ndc_rays_bwd.  A focal length that requires grad does not pass through
+    here (the coefficients are host floats): pose.camera_rows takes K as a device tensor and returns its gradient."""
     if float(near) != 1.0:
         raise NotImplementedError("ndc_rays is compiled for the near plane render() uses (1.0)")
+    if torch.is_tensor(focal) and focal.requires_grad and torch.is_grad_enabled():
+        raise ops.CnerfError("ndc_rays: a focal length that requires grad would lose its graph here (the two coefficients are host "
+                             "floats) — use pose.camera_rows(H, W, K, c2w, ..., ndc=True) with K a [3,3] tensor on the GPU")
     sh = rays_d.shape
+    if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (rays_o, rays_d)):
+        dev = _dev(rays_d if rays_d.is_cuda else rays_o)
+        rays_o, rays_d = (t.to(device=dev, dtype=torch.float32).expand(sh) for t in (rays_o, rays_d))
+        coef = tuple(float(c) for c in ndc_coefficients(H, W, focal))
+        return _NdcRaysFn.apply(rays_o, rays_d, coef)
     r = ops.pack_rays(rays_o, rays_d, 0., 1., False, True, ndc_coefficients(H, W, focal))
     return r[:, 0:3].reshape(sh), r[:, 3:6].reshape(sh)
 

@@ -38,6 +38,9 @@ extern "C" {
                                 * 6: + camera pose gradients: cnerf_gen_rays_at / cnerf_gen_rays_at_bwd (+ cnerf_gen_rays_at_bwd_ws_floats), the rays of
                                 * chosen pixels from poses in device memory and their backward, and cnerf_pose_compose / cnerf_pose_compose_bwd;
                                 * append-only.
+                                * 6: + NDC and intrinsics gradients: cnerf_camera_rows / cnerf_camera_rows_bwd (+ cnerf_camera_rows_bwd_ws_floats), the
+                                * finished ray rows of chosen pixels from poses and K in device memory and their backward w.r.t. both, and
+                                * cnerf_ndc_rays_bwd; append-only.
                                 * 6: + the in-loop consistency step as ONE render whose row count lives on the device: cnerf_ss_batch (the combined
                                 * batch + its live-row count), cnerf_mlp_fwd_live / cnerf_mlp_bwd_live / cnerf_mlp_bwd_pair_live (launches of a fixed
                                 * capacity that stop at a device-side count), cnerf_closs_finish_ss2 (the two-segment loss tail); cnerf_closs gains
@@ -829,6 +832,38 @@ int cnerf_gen_rays_at_bwd(int H, int W, float fx, float fy, float cx, float cy, 
 int cnerf_pose_compose(const float* c2w0, const float* rot, const float* trans, int n_views, float* c2w, void* stream);
 int cnerf_pose_compose_bwd(const float* c2w0, const float* rot, const float* d_c2w, int n_views, float* d_rot, float* d_trans,
                            void* stream);
+
+/* ---- NDC and intrinsics gradients: pixel -> finished ray row, w.r.t. the poses and the camera matrix ------------------------------- */
+/* H:164-173 + R:103-116 + H:186-202 for B chosen pixels in ONE launch: rows [B, 8 | 11] = [o(3), d(3), near, far (, viewdirs(3))], the
+ * batch render() hands to batchify_rays — get_rays of the pixel, viewdirs = d / |d| of the PRE-NDC direction (use_viewdirs), then the
+ * NDC warp with near plane 1 (ndc) — the same bits as cnerf_gen_rays(..., use_viewdirs, ndc, ndc_ax, ndc_ay) for the same pose and
+ * pixel.  c2w, n_views, coords, view, first, B: as cnerf_gen_rays_at (DEVICE poses [n_views, 12]; values of coords / view are the
+ * caller's duty).  Intrinsics: the host floats fx, fy, cx, cy and the two coefficients of H:193-199, or — K != NULL, which overrides
+ * them — a DEVICE row-major float K[3][3] of which K[0][0], K[1][1], K[0][2], K[1][2] are read in the kernel (no host copy, no
+ * synchronisation); the coefficients then are -1.f / ((float)W / (2.f * K[0][0])) and -1.f / ((float)H / (2.f * K[0][0])) in fp32,
+ * as the reference's tensor arithmetic forms them (H:193-199 uses K[0][0] for both axes).  B, n_views, H, W > 0; fx, fy != 0 on
+ * the host source. */
+int cnerf_camera_rows(int H, int W, float fx, float fy, float cx, float cy, float ndc_ax, float ndc_ay, const float* K, const float* c2w,
+                      int n_views, const int64_t* coords, const int64_t* view, int64_t first, int64_t B, float near, float far,
+                      int use_viewdirs, int ndc, float* rows, void* stream);
+/* Autograd of the above: g [B, 8 | 11] (the near / far columns carry nothing) -> d_c2w [n_views, 12] and d_K [9] (row-major 3 x 3:
+ * only the four entries read are non-zero), either nullable, not both.  Per ray the pixel direction, the pre-NDC ray and the warp are
+ * recomputed in fp64; the gradient goes back through the viewdirs normalisation, the warp (o'_z and d'_z are constants: the
+ * derivative is written simplified, csrc/camera_grad.hpp), rays_d = R dir, rays_o = t and dir = ((col - cx) / fx, -(row - cy) / fy, -1).
+ * With K != NULL and ndc the two coefficients are functions of K[0][0] and their gradients are added to d_K[0]; with host intrinsics
+ * the coefficients are arguments of their own.  d_c2w: over the rays of each view, zeros for a view without a ray (a view value
+ * outside [0, n_views) contributes nowhere); d_K: over all views.  Two launches: fp64 sums of fixed chunks of 64 rays, then one
+ * wave per view (and one for K) over the chunks in order, rounded to fp32 once — no atomics, the same bits call after call and for
+ * every grid.  workspace = cnerf_camera_rows_bwd_ws_floats(B, n_views) floats (0 for B or n_views <= 0), 8-byte aligned.  grid:
+ * workgroups of the first launch, 0 = chosen here. */
+int64_t cnerf_camera_rows_bwd_ws_floats(int64_t B, int n_views);
+int cnerf_camera_rows_bwd(int H, int W, float fx, float fy, float cx, float cy, float ndc_ax, float ndc_ay, const float* K, const float* c2w,
+                          int n_views, const int64_t* coords, const int64_t* view, int64_t first, int64_t B, int use_viewdirs, int ndc,
+                          const float* g, float* d_c2w, float* d_K, float* workspace, int grid, void* stream);
+/* Autograd of ndc_rays (H:186-202, near plane 1; its forward is cnerf_pack_rays with ndc): (g_o, g_d) [B, 3] of the warped rays and
+ * the pre-NDC (rays_o, rays_d) [B, 3] -> (d_rays_o, d_rays_d) [B, 3], one thread per ray, through the same device function. */
+int cnerf_ndc_rays_bwd(const float* g_o, const float* g_d, const float* rays_o, const float* rays_d, int64_t B, float ndc_ax, float ndc_ay,
+                       float* d_rays_o, float* d_rays_d, void* stream);
 
 #ifdef __cplusplus
 }
