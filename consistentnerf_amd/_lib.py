@@ -223,6 +223,10 @@ SIGNATURES = {
     "cnerf_mlp_input_grad": (_i, [_NetP, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     "cnerf_rays_input_grad": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _i, _vp]),
     "cnerf_composite_norm_grad": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i64, _i, _vp, _i, _vp]),
+    # (declared last in include/cnerf.h: the header order is the ABI, not this dict's)
+    "cnerf_mlp_input_grad_pair": (_i, [_NetP, _vp, _i64, _i, _vp, _vp, _vp, _vp, _NetP, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cnerf_rays_input_grad_pair": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _vp, _i, _vp]),
+    "cnerf_composite_norm_grad_pair": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _vp]),
     "cnerf_pack_rays_bwd": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "cnerf_gen_rays_at": (_i, [_i, _i, _f, _f, _f, _f, _vp, _i, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "cnerf_gen_rays_at_bwd_ws_floats": (_i64, [_i64, _i]),

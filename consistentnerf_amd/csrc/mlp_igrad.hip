@@ -10,6 +10,10 @@
 //   3. composite_norm_k: one wave per ray, the gradient of raw2outputs w.r.t. rays_d through dists * |rays_d| (R:283), from the
 //      d_raw that cnerf_composite_bwd already produced.
 //   4. pack_rays_bwd_k: one thread per ray, the backward of the non-NDC cnerf_pack_rays (viewdirs = d / |d|).
+// The camera chain on the folded training step runs the first three for BOTH levels of one ray batch in one grid each
+// (mlp_igrad_pair_k, rays_igrad_pair_k, composite_norm_pair_k): the per-level arithmetic is the single kernels' (the same __device__
+// bodies), the two levels' per-ray results are added in fp32 after each was rounded, and every column of the [B, ray_stride] row
+// gradient is written (no fill launch in front).
 // No atomics anywhere: every sum has a fixed order, results are identical from run to run.
 #include "mlp_common.hpp"
 
@@ -126,12 +130,11 @@ __device__ __forceinline__ void igrad_x(const CN_CONST IgradArgs& a, rsrc_t wrs,
   enc_jacobian<NCT>(acc, srs, g.s_enc, g.in_ch, lane, valid, d);
 }
 
-__global__ __launch_bounds__(64) void mlp_igrad_k(IgradArgs args_by_value) {
-  (void)args_by_value;   // read in place from the kernarg segment (scalar loads next to their use)
-  const CN_CONST IgradArgs& a = *(const CN_CONST IgradArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+// One wave64: the 32 points of tile `tile` of the level `a` (read in place from the kernarg segment).
+__device__ __forceinline__ void igrad_tile(const CN_CONST IgradArgs& a, unsigned tile) {
   const CN_CONST NetGeom& g = a.g;
   const int lane = threadIdx.x, m = lane & 31, hh = lane >> 5;
-  const int64_t p0 = (int64_t)blockIdx.x * 32;
+  const int64_t p0 = (int64_t)tile * 32;
   const int64_t p = p0 + m;
   const bool valid = p < a.M;
   // this tile's rows of the gradient workspace and of the stash; lanes of padding points address out of range (zeros)
@@ -156,17 +159,36 @@ __global__ __launch_bounds__(64) void mlp_igrad_k(IgradArgs args_by_value) {
   }
 }
 
-// one wave per ray: lane l sums samples l, l + 64, .. in order, then the xor butterfly (a fixed order)
-__global__ __launch_bounds__(256) void rays_igrad_k(const float* __restrict__ d_pts, const float* __restrict__ d_dirs,
-                                                    const float* __restrict__ z, int64_t B, int S, float* __restrict__ d_o,
-                                                    float* __restrict__ d_d, float* __restrict__ d_v, int os) {
-  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (b >= B) return;
-  float so[3] = {0.f, 0.f, 0.f}, sd[3] = {0.f, 0.f, 0.f}, sv[3] = {0.f, 0.f, 0.f};
+__global__ __launch_bounds__(64) void mlp_igrad_k(IgradArgs args_by_value) {
+  (void)args_by_value;   // read in place from the kernarg segment (scalar loads next to their use)
+  igrad_tile(*(const CN_CONST IgradArgs*)__builtin_amdgcn_kernarg_segment_ptr(), blockIdx.x);
+}
+
+// Two levels in one grid: workgroups [0, nb0) walk the tiles of lv[0], the rest those of lv[1] (the level is picked by blockIdx.x:
+// uniform across the wave, each level with its own geometry, sample count and ragged last tile).
+struct IgradPairArgs {
+  IgradArgs lv[2];
+  unsigned nb0;
+};
+
+__global__ __launch_bounds__(64) void mlp_igrad_pair_k(IgradPairArgs args_by_value) {
+  (void)args_by_value;
+  const CN_CONST IgradPairArgs& args = *(const CN_CONST IgradPairArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  const unsigned nb0 = args.nb0;
+  const bool second = blockIdx.x >= nb0;
+  igrad_tile(args.lv[second ? 1 : 0], blockIdx.x - (second ? nb0 : 0u));
+}
+
+// One ray of one level: lane l sums samples l, l + 64, .. in order, then the xor butterfly (a fixed order).  pts: so = sum_s d_pts,
+// sd = sum_s z d_pts; dirs: sv = sum_s d_dirs.
+__device__ __forceinline__ void rays_level_sums(const float* __restrict__ d_pts, const float* __restrict__ d_dirs,
+                                                const float* __restrict__ z, int64_t b, int S, int lane, bool pts, bool dirs,
+                                                float (&so)[3], float (&sd)[3], float (&sv)[3]) {
+#pragma unroll
+  for (int j = 0; j < 3; ++j) so[j] = sd[j] = sv[j] = 0.f;
   for (int s = lane; s < S; s += 64) {
     const int64_t q = b * S + s;
-    if (d_o != nullptr) {
+    if (pts) {
       const float zz = z[q];
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
@@ -175,7 +197,7 @@ __global__ __launch_bounds__(256) void rays_igrad_k(const float* __restrict__ d_
         sd[j] += zz * gx;
       }
     }
-    if (d_v != nullptr)
+    if (dirs)
 #pragma unroll
       for (int j = 0; j < 3; ++j) sv[j] += d_dirs[q * 3 + j];
   }
@@ -183,6 +205,17 @@ __global__ __launch_bounds__(256) void rays_igrad_k(const float* __restrict__ d_
   for (int j = 0; j < 3; ++j) {
     so[j] = wave_sum(so[j]); sd[j] = wave_sum(sd[j]); sv[j] = wave_sum(sv[j]);
   }
+}
+
+// one wave per ray
+__global__ __launch_bounds__(256) void rays_igrad_k(const float* __restrict__ d_pts, const float* __restrict__ d_dirs,
+                                                    const float* __restrict__ z, int64_t B, int S, float* __restrict__ d_o,
+                                                    float* __restrict__ d_d, float* __restrict__ d_v, int os) {
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= B) return;
+  float so[3], sd[3], sv[3];
+  rays_level_sums(d_pts, d_dirs, z, b, S, lane, d_o != nullptr, d_v != nullptr, so, sd, sv);
   if (lane == 0) {
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
@@ -192,15 +225,39 @@ __global__ __launch_bounds__(256) void rays_igrad_k(const float* __restrict__ d_
   }
 }
 
-// one wave per ray: alpha_s = 1 - exp(-relu(sigma_s + noise_s) dist_s n), n = |rays_d| (R:283, R:296-298), so
-// dL/dn = (1/n) sum_s d_raw[s, sigma] * relu(sigma_s + noise_s) and d rays_d = (rays_d / n) dL/dn.  (A 1e10 tail sample whose
-// sigma is positive has alpha = 1 exactly and d_raw[s, sigma] = 0 already.)
-__global__ __launch_bounds__(256) void composite_norm_k(const float* __restrict__ d_raw, const float* __restrict__ raw, int ch,
-                                                        const float* __restrict__ noise, const float* __restrict__ rays, int rs,
-                                                        int64_t B, int S, float* __restrict__ d_d, int os) {
+// One wave per ray, both levels of one ray batch: each level's sums as above (rounded to fp32), then level 0 + level 1, into EVERY
+// column of the [B, rs] row gradient: origins 0:3, directions 3:6, zeros up to the last three columns, which hold the per-ray
+// view-direction sum when the levels carry one (d_dirs0 / d_dirs1: both or neither) and zeros otherwise.
+__global__ __launch_bounds__(256) void rays_igrad_pair_k(const float* __restrict__ d_pts0, const float* __restrict__ d_dirs0,
+                                                         const float* __restrict__ z0, int S0, const float* __restrict__ d_pts1,
+                                                         const float* __restrict__ d_dirs1, const float* __restrict__ z1, int S1,
+                                                         int64_t B, float* __restrict__ out, int rs) {
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (b >= B) return;
+  const bool dirs = d_dirs0 != nullptr;
+  float so0[3], sd0[3], sv0[3], so1[3], sd1[3], sv1[3];
+  rays_level_sums(d_pts0, d_dirs0, z0, b, S0, lane, true, dirs, so0, sd0, sv0);
+  rays_level_sums(d_pts1, d_dirs1, z1, b, S1, lane, true, dirs, so1, sd1, sv1);
+  if (lane == 0) {
+    float* r = out + b * rs;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      r[j] = so0[j] + so1[j];
+      r[3 + j] = sd0[j] + sd1[j];
+    }
+    for (int c = 6; c < rs; ++c) r[c] = 0.f;
+    if (dirs)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) r[rs - 3 + j] = sv0[j] + sv1[j];
+  }
+}
+
+// One ray of one level: alpha_s = 1 - exp(-relu(sigma_s + noise_s) dist_s n), n = |rays_d| (R:283, R:296-298), so
+// dL/dn = (1/n) sum_s d_raw[s, sigma] * relu(sigma_s + noise_s) and d rays_d = (rays_d / n) dL/dn.  (A 1e10 tail sample whose
+// sigma is positive has alpha = 1 exactly and d_raw[s, sigma] = 0 already.)  -> sum_s d_raw[s, sigma] * relu(..) in every lane.
+__device__ __forceinline__ float norm_level_sum(const float* __restrict__ d_raw, const float* __restrict__ raw, int ch,
+                                                const float* __restrict__ noise, int64_t b, int S, int lane) {
   float acc = 0.f;
   for (int s = lane; s < S; s += 64) {
     const int64_t q = b * S + s;
@@ -208,13 +265,47 @@ __global__ __launch_bounds__(256) void composite_norm_k(const float* __restrict_
     if (noise != nullptr) sg = sg + noise[q];
     acc += d_raw[q * ch + 3] * (sg > 0.f ? sg : 0.f);
   }
-  acc = wave_sum(acc);
+  return wave_sum(acc);
+}
+
+// one wave per ray
+__global__ __launch_bounds__(256) void composite_norm_k(const float* __restrict__ d_raw, const float* __restrict__ raw, int ch,
+                                                        const float* __restrict__ noise, const float* __restrict__ rays, int rs,
+                                                        int64_t B, int S, float* __restrict__ d_d, int os) {
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= B) return;
+  const float acc = norm_level_sum(d_raw, raw, ch, noise, b, S, lane);
   if (lane == 0) {
     const float* r = rays + b * rs;
     const float dx = r[3], dy = r[4], dz = r[5];
     const float n = sqrtf(dx * dx + dy * dy + dz * dz);
     const float gn = acc / n;
     d_d[b * os + 0] = dx / n * gn; d_d[b * os + 1] = dy / n * gn; d_d[b * os + 2] = dz / n * gn;
+  }
+}
+
+// One wave per ray, both levels of one ray batch (the same rows): each level's term as above, rounded, then level 0 + level 1 into
+// columns 3:6 of the [B, rs] row gradient; every other column is written zero.
+__global__ __launch_bounds__(256) void composite_norm_pair_k(const float* __restrict__ d_raw0, const float* __restrict__ raw0, int ch0,
+                                                             const float* __restrict__ noise0, int S0,
+                                                             const float* __restrict__ d_raw1, const float* __restrict__ raw1, int ch1,
+                                                             const float* __restrict__ noise1, int S1,
+                                                             const float* __restrict__ rays, int rs, int64_t B, float* __restrict__ out) {
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= B) return;
+  const float acc0 = norm_level_sum(d_raw0, raw0, ch0, noise0, b, S0, lane);
+  const float acc1 = norm_level_sum(d_raw1, raw1, ch1, noise1, b, S1, lane);
+  if (lane == 0) {
+    const float* r = rays + b * rs;
+    const float dx = r[3], dy = r[4], dz = r[5];
+    const float n = sqrtf(dx * dx + dy * dy + dz * dz);
+    const float gn0 = acc0 / n, gn1 = acc1 / n;
+    float* o = out + b * rs;
+    for (int c = 0; c < rs; ++c)
+      if (c < 3 || c >= 6) o[c] = 0.f;
+    o[3] = dx / n * gn0 + dx / n * gn1; o[4] = dy / n * gn0 + dy / n * gn1; o[5] = dz / n * gn0 + dz / n * gn1;
   }
 }
 
@@ -283,6 +374,50 @@ extern "C" int cnerf_pack_rays_bwd(const float* g, const float* rays_d, int64_t 
   if (!g || !rays_d || !d_o || !d_d || B <= 0) return CNERF_E_ARG;
   hipLaunchKernelGGL(pack_rays_bwd_k, dim3((unsigned)cn_div_up(B, 256)), dim3(256), 0, cn_stream(stream), g, use_viewdirs ? 11 : 8,
                      rays_d, B, use_viewdirs ? 1 : 0, d_o, d_d);
+  CN_CHECK_LAUNCH();
+  return CNERF_OK;
+}
+
+// ---- both levels of one ray batch in one grid each (the camera chain on the folded training step) ---------------------------------
+extern "C" int cnerf_mlp_input_grad_pair(const cnerf_net* net0, const float* packed0, int64_t B0, int S0, const float* stash0,
+                                         const float* workspace0, float* d_pts0, float* d_dirs_pt0, const cnerf_net* net1,
+                                         const float* packed1, int64_t B1, int S1, const float* stash1, const float* workspace1,
+                                         float* d_pts1, float* d_dirs_pt1, void* stream) {
+  IgradPairArgs a;
+  int rc = cn_make_geom(net0, &a.lv[0].g);
+  if (rc || (rc = cn_make_geom(net1, &a.lv[1].g))) return rc;
+  if (!packed0 || !stash0 || !workspace0 || !d_pts0 || B0 <= 0 || S0 <= 0) return CNERF_E_ARG;
+  if (!packed1 || !stash1 || !workspace1 || !d_pts1 || B1 <= 0 || S1 <= 0) return CNERF_E_ARG;
+  if ((d_dirs_pt0 && !a.lv[0].g.viewdirs) || (d_dirs_pt1 && !a.lv[1].g.viewdirs)) return CNERF_E_ARG;
+  a.lv[0].packed = packed0; a.lv[0].stash = stash0; a.lv[0].G = workspace0; a.lv[0].d_pts = d_pts0; a.lv[0].d_dirs = d_dirs_pt0;
+  a.lv[1].packed = packed1; a.lv[1].stash = stash1; a.lv[1].G = workspace1; a.lv[1].d_pts = d_pts1; a.lv[1].d_dirs = d_dirs_pt1;
+  a.lv[0].M = B0 * S0;
+  a.lv[1].M = B1 * S1;
+  a.nb0 = (unsigned)cn_div_up(a.lv[0].M, 32);
+  hipLaunchKernelGGL(mlp_igrad_pair_k, dim3(a.nb0 + (unsigned)cn_div_up(a.lv[1].M, 32)), dim3(64), 0, cn_stream(stream), a);
+  CN_CHECK_LAUNCH();
+  return CNERF_OK;
+}
+
+extern "C" int cnerf_rays_input_grad_pair(const float* d_pts0, const float* d_dirs_pt0, const float* z0, int S0, const float* d_pts1,
+                                          const float* d_dirs_pt1, const float* z1, int S1, int64_t B, float* d_rays, int ray_stride,
+                                          void* stream) {
+  if (!d_pts0 || !z0 || !d_pts1 || !z1 || !d_rays || B <= 0 || S0 <= 0 || S1 <= 0 || ray_stride < 8) return CNERF_E_ARG;
+  if ((d_dirs_pt0 != nullptr) != (d_dirs_pt1 != nullptr)) return CNERF_E_ARG;
+  if (d_dirs_pt0 && ray_stride < 11) return CNERF_E_ARG;       // (the view directions are the last three columns, behind near / far)
+  hipLaunchKernelGGL(rays_igrad_pair_k, dim3((unsigned)cn_div_up(B, 4)), dim3(256), 0, cn_stream(stream), d_pts0, d_dirs_pt0, z0, S0,
+                     d_pts1, d_dirs_pt1, z1, S1, B, d_rays, ray_stride);
+  CN_CHECK_LAUNCH();
+  return CNERF_OK;
+}
+
+extern "C" int cnerf_composite_norm_grad_pair(const float* d_raw0, const float* raw0, int raw_ch0, const float* noise0, int S0,
+                                              const float* d_raw1, const float* raw1, int raw_ch1, const float* noise1, int S1,
+                                              const float* rays, int ray_stride, int64_t B, float* d_rays, void* stream) {
+  if (!d_raw0 || !raw0 || !d_raw1 || !raw1 || !rays || !d_rays || B <= 0 || S0 <= 0 || S1 <= 0) return CNERF_E_ARG;
+  if (raw_ch0 < 4 || raw_ch1 < 4 || ray_stride < 8) return CNERF_E_ARG;
+  hipLaunchKernelGGL(composite_norm_pair_k, dim3((unsigned)cn_div_up(B, 4)), dim3(256), 0, cn_stream(stream), d_raw0, raw0, raw_ch0,
+                     noise0, S0, d_raw1, raw1, raw_ch1, noise1, S1, rays, ray_stride, B, d_rays);
   CN_CHECK_LAUNCH();
   return CNERF_OK;
 }

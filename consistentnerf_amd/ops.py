@@ -391,14 +391,17 @@ def mlp_bwd_workspace(spec: NetSpec, B: int, S: int, device) -> Tensor:
 def _mlp_backward(levels, accumulate, bf, live, first=(), ws=None):
     """One backward over `levels`, one or two of (spec, packed, d_raw, B, S, stash, grads) with `packed` the buffer of the chosen
     arithmetic.  `units` of the profile records is the launch CAPACITY (with `live` the point count is on the device: the bench
-    rescales by the step's live rows).  `ws` (one level): the workspace to run in, for a caller that reads dZ afterwards."""
+    rescales by the step's live rows).  `ws`: the workspace(s) to run in, for a caller that reads dZ afterwards — one tensor (one
+    level) or a tuple with one per level (mlp_input_grad / mlp_input_grad_pair); otherwise allocated here and dropped."""
     lib = _lib.load()
     dgrad, wgrad, units, keep = [], [], 0, []
+    own = ws if isinstance(ws, (tuple, list)) else (ws,) + (None,) * (len(levels) - 1)
+    if len(own) != len(levels):
+        raise CnerfError("_mlp_backward: one workspace per level")
     for i, (spec, packed, d_raw, B, S, stash, grads) in enumerate(levels):
         net, ptrs = spec.c(), _ptrs(grads)
         d_raw = _chk(d_raw, "d_raw" if len(levels) == 1 else "d_raw%d" % i)
-        if ws is None or i > 0:
-            ws = mlp_bwd_workspace(spec, B, S, packed.device)
+        ws = own[i] if own[i] is not None else mlp_bwd_workspace(spec, B, S, packed.device)
         dgrad.append([C.byref(net), _p(packed), _p(d_raw), B, S, _p(stash), _p(ws)])
         wgrad.append([C.byref(net), B, S, _p(stash), _p(ws), C.byref(ptrs)])
         units += B * S
@@ -484,18 +487,75 @@ def composite_norm_grad(d_raw: Tensor, raw: Tensor, noise: Optional[Tensor], ray
 def mlp_backward_pair(spec0: NetSpec, packed0: Tensor, d_raw0: Tensor, B0: int, S0: int, stash0: Tensor, grads0: List[Tensor],
                       spec1: NetSpec, packed1: Tensor, d_raw1: Tensor, B1: int, S1: int, stash1: Tensor, grads1: List[Tensor],
                       accumulate: bool = False, packed_bf0: Optional[Tensor] = None, packed_bf1: Optional[Tensor] = None,
-                      live: Optional[Tensor] = None, first0: int = 0, first1: int = 0):
+                      live: Optional[Tensor] = None, first0: int = 0, first1: int = 0, ws=None):
     """cnerf_mlp_bwd_pair: the backward of two independent networks (coarse / fine) as one dgrad grid, one wgrad grid and
     one reduction; gradients are written (or accumulated) into grads0 / grads1.  packed_bf0 AND packed_bf1: the dgrad and wgrad
     grids run in the opt-in bf16x3 arithmetic.  live: both levels belong to one ray batch whose live row count sits on the device
     (mlp_forward(live=...)): the halves of cnerf_mlp_bwd_pair_live (exact fp32); first0 / first1: that level's first rays carry
-    zero seeds and are left out of its backward."""
+    zero seeds and are left out of its backward.  ws = (ws0, ws1) (mlp_bwd_workspace each): run in these workspaces, which are the
+    caller's and hold dZ of both levels afterwards (mlp_input_grad_pair reads them)."""
     if live is not None and (packed_bf0 is not None or packed_bf1 is not None):
         raise CnerfError("mlp_backward_pair(live=...) is an exact-fp32 path")
     bf = packed_bf0 is not None and packed_bf1 is not None
     _mlp_backward([(spec0, packed_bf0 if bf else packed0, d_raw0, B0, S0, stash0, grads0),
                    (spec1, packed_bf1 if bf else packed1, d_raw1, B1, S1, stash1, grads1)],
-                  accumulate, bf, live, (first0, first1) if live is not None else ())
+                  accumulate, bf, live, (first0, first1) if live is not None else (), ws=ws)
+
+
+def mlp_input_grad_pair(spec0: NetSpec, packed0: Tensor, B0: int, S0: int, stash0: Tensor, ws0: Tensor,
+                        spec1: NetSpec, packed1: Tensor, B1: int, S1: int, stash1: Tensor, ws1: Tensor, want_dirs: bool = False):
+    """cnerf_mlp_input_grad_pair: mlp_input_grad of two levels as one grid, behind mlp_backward_pair(ws=(ws0, ws1)) ->
+    ((d_pts0, d_dirs_pt0 | None), (d_pts1, d_dirs_pt1 | None)), each the bits of the single call.  `packed`: the fp32 panels, also
+    behind the bf16x3 pair."""
+    n0, n1 = spec0.c(), spec1.c()
+    dev = packed0.device
+    out = [torch.empty(B * S, 3, device=dev, dtype=torch.float32) if on else None
+           for B, S in ((B0, S0), (B1, S1)) for on in (True, want_dirs)]
+    with _timed("mlp_input_grad_pair", B0 * S0 + B1 * S1):
+        _lib.check(_lib.load().cnerf_mlp_input_grad_pair(C.byref(n0), _p(packed0), B0, S0, _p(stash0), _p(ws0), _p(out[0]), _p(out[1]),
+                                                         C.byref(n1), _p(packed1), B1, S1, _p(stash1), _p(ws1), _p(out[2]), _p(out[3]),
+                                                         _stream()), "cnerf_mlp_input_grad_pair")
+    return (out[0], out[1]), (out[2], out[3])
+
+
+def rays_input_grad_pair(d_pts0: Tensor, d_dirs_pt0: Optional[Tensor], z0: Tensor, d_pts1: Tensor, d_dirs_pt1: Optional[Tensor],
+                         z1: Tensor, ray_stride: int) -> Tensor:
+    """cnerf_rays_input_grad_pair: rays_input_grad(level 0) + rays_input_grad(level 1) of one ray batch, bit for bit, as one launch
+    that writes every column of the [B, ray_stride] result (no fill in front).  z0 [B, S0], z1 [B, S1]."""
+    z0, z1 = _chk(z0, "z0"), _chk(z1, "z1")
+    B = z0.shape[0]
+    if z1.shape[0] != B:
+        raise CnerfError("rays_input_grad_pair: the two levels belong to one ray batch")
+    for t, zz, name in ((d_pts0, z0, "d_pts0"), (d_dirs_pt0, z0, "d_dirs_pt0"), (d_pts1, z1, "d_pts1"), (d_dirs_pt1, z1, "d_dirs_pt1")):
+        if t is not None and (t.numel() != zz.numel() * 3 or not t.is_contiguous() or t.dtype != torch.float32 or t.device != zz.device):
+            raise CnerfError(f"rays_input_grad_pair: {name} must be a contiguous float32 [B * S, 3] on the device of its level's z")
+    out = torch.empty(B, ray_stride, device=z0.device, dtype=torch.float32)
+    with _timed("rays_input_grad_pair", z0.numel() + z1.numel()):
+        _lib.check(_lib.load().cnerf_rays_input_grad_pair(_p(d_pts0), _p(d_dirs_pt0), _p(z0), z0.shape[1], _p(d_pts1), _p(d_dirs_pt1), _p(z1),
+                                                          z1.shape[1], B, _p(out), ray_stride, _stream()), "cnerf_rays_input_grad_pair")
+    return out
+
+
+def composite_norm_grad_pair(d_raw0: Tensor, raw0: Tensor, noise0: Optional[Tensor], d_raw1: Tensor, raw1: Tensor,
+                             noise1: Optional[Tensor], rays: Tensor) -> Tensor:
+    """cnerf_composite_norm_grad_pair: composite_norm_grad(level 0) + composite_norm_grad(level 1) for two levels that read the
+    same ray rows, bit for bit, as one launch that writes every column of the result."""
+    d_raw0, raw0, noise0 = _chk(d_raw0, "d_raw0"), _chk(raw0, "raw0"), _chk(noise0, "noise0")
+    d_raw1, raw1, noise1 = _chk(d_raw1, "d_raw1"), _chk(raw1, "raw1"), _chk(noise1, "noise1")
+    rays = _chk(rays, "rays")
+    B = rays.shape[0]
+    if raw0.shape[0] != B or raw1.shape[0] != B:
+        raise CnerfError("composite_norm_grad_pair: the two levels belong to one ray batch")
+    for d, r, nz, lv in ((d_raw0, raw0, noise0, 0), (d_raw1, raw1, noise1, 1)):
+        if d.shape != r.shape or r.dim() != 3 or (nz is not None and nz.shape != r.shape[:2]):
+            raise CnerfError(f"composite_norm_grad_pair: level {lv}: d_raw and raw are [B, S, ch] alike, noise [B, S]")
+    out = torch.empty_like(rays)
+    with _timed("composite_norm_grad_pair", raw0.shape[0] * (raw0.shape[1] + raw1.shape[1])):
+        _lib.check(_lib.load().cnerf_composite_norm_grad_pair(_p(d_raw0), _p(raw0), raw0.shape[-1], _p(noise0), raw0.shape[1],
+                                                              _p(d_raw1), _p(raw1), raw1.shape[-1], _p(noise1), raw1.shape[1],
+                                                              _p(rays), rays.shape[1], B, _p(out), _stream()),
+                   "cnerf_composite_norm_grad_pair")
+    return out
 
 
 # ------------------------------------------------------------------------------------------ render_rays as one call

@@ -6,7 +6,8 @@
 Same signatures, kwargs dictionaries and return structures; the bodies launch the gfx950 kernels of
 libcnerf_hip.so (include/cnerf.h).  Autograd is wired with two torch.autograd.Function nodes (fused
 encoding+MLP, compositing); sampling carries no gradient, exactly like the reference (R:397).  Sample points, view directions
-and the rays of render(rays=(rays_o, rays_d), ndc=False) take gradients too (csrc/mlp_igrad.hip, behind the same backward).
+and the rays of render(rays=(rays_o, rays_d), ndc=False) take gradients too (csrc/mlp_igrad.hip, behind the same backward), and so do
+the finished ray rows of render_loss(rows=...), on the folded training step (both levels in one grid per launch).
 
 `run_nerf_view.py` of this package layers the ConsistentNeRF additions (depth outputs, warp, hard masks,
 masked losses) on top of this module.
@@ -221,12 +222,15 @@ MERGE_BWD = os.environ.get("CNERF_MERGE_BWD", "1") != "0"
 class _LevelJob:
     """What the MLP backward of one level launches with, taken from its node (`ctx`) and the gradient of its output.  `d_raw` is
     made contiguous here: when the fine node parks, in ITS backward."""
-    __slots__ = ("spec", "packed", "packed_bf", "d_raw", "B", "S", "stash", "params", "model", "live", "skip")
+    __slots__ = ("spec", "packed", "packed_bf", "d_raw", "B", "S", "stash", "params", "model", "live", "skip", "needs", "z",
+                 "ray_stride", "dirs_given")
 
     def __init__(self, ctx, g_raw):
         self.spec, self.packed, self.packed_bf, self.d_raw = ctx.spec, ctx.packed, ctx.packed_bf, g_raw.contiguous()
         self.B, self.S, self.stash, self.params, self.model = ctx.B, ctx.S, ctx.stash, ctx.params, ctx.model
-        self.live, self.skip = ctx.live, ctx.skip
+        self.live, self.skip, self.needs = ctx.live, ctx.skip, ctx.needs_input_grad
+        # a level whose inputs take a gradient: the sample depths and the form of the inputs (_MlpFn.forward)
+        self.z, self.ray_stride, self.dirs_given = (ctx.z, ctx.ray_stride, ctx.dirs_given) if ctx.igrad else (None, None, False)
 
 
 class _LevelPair:
@@ -245,9 +249,21 @@ def _link_levels(raw_coarse, raw_fine):
         return
     if getattr(nc, "stash", None) is None or getattr(nf, "stash", None) is None or nc.model is nf.model:
         return
-    if getattr(nc, "igrad", False) or getattr(nf, "igrad", False):      # a level whose inputs take a gradient runs on its own
-        return                                                          # (_MlpFn._input_grads)
+    if getattr(nc, "igrad", False) or getattr(nf, "igrad", False):
+        # a level whose inputs take a gradient runs on its own (_MlpFn._input_grads) — except the two levels of one batch of ray rows
+        # that both hand a gradient to those rows and to their parameters (the camera chain): those pair up (_run_pair_rows)
+        if not (_rows_level(nc) and _rows_level(nf) and nc.B == nf.B and nc.ray_stride == nf.ray_stride
+                and bool(nc.spec.use_viewdirs) == bool(nf.spec.use_viewdirs)):
+            return
     nc.pair = nf.pair = _LevelPair(nc, nf)
+
+
+def _rows_level(n):
+    """A level that _link_levels may pair although its inputs take a gradient: the gradient goes to the ray rows alone (no points or
+    view directions given, so the view directions sit in the rows), the parameters take theirs, and the batch is not `live`."""
+    needs = n.needs_input_grad
+    return (n.igrad and needs[4] and not needs[3] and not needs[6] and n.ray_stride is not None and not n.dirs_given
+            and n.live is None and any(needs[10:]))
 
 
 def _direct_ok(needs, params):
@@ -308,6 +324,22 @@ def _run_pair(fine, coarse):
     _report_ready([fine.model, coarse.model], True)
 
 
+def _run_pair_rows(fine, coarse):
+    """_run_pair for two levels whose ray rows take a gradient too -> the [B, ray_stride] row gradient of BOTH levels: the paired
+    backward in workspaces kept here, then cnerf_mlp_input_grad_pair on them and cnerf_rays_input_grad_pair (every column written)."""
+    dev = fine.packed.device
+    ws = (ops.mlp_bwd_workspace(fine.spec, fine.B, fine.S, dev), ops.mlp_bwd_workspace(coarse.spec, coarse.B, coarse.S, dev))
+    ops.mlp_backward_pair(fine.spec, fine.packed, fine.d_raw, fine.B, fine.S, fine.stash, [p.grad for p in fine.params],
+                          coarse.spec, coarse.packed, coarse.d_raw, coarse.B, coarse.S, coarse.stash, [p.grad for p in coarse.params],
+                          accumulate=not _take_dropped(fine.params, coarse.params), packed_bf0=fine.packed_bf,
+                          packed_bf1=coarse.packed_bf, ws=ws)
+    _report_ready([fine.model, coarse.model], True)
+    (pts_f, dirs_f), (pts_c, dirs_c) = ops.mlp_input_grad_pair(fine.spec, fine.packed, fine.B, fine.S, fine.stash, ws[0],
+                                                                coarse.spec, coarse.packed, coarse.B, coarse.S, coarse.stash, ws[1],
+                                                                want_dirs=bool(fine.spec.use_viewdirs))
+    return ops.rays_input_grad_pair(pts_f, dirs_f, fine.z, pts_c, dirs_c, coarse.z, fine.ray_stride)
+
+
 class _MlpFn(torch.autograd.Function):
     """Fused gamma(x), gamma(d) + MLP (replaces R:37-52 + H:44-45 + H:107-130 and their autograd)."""
 
@@ -366,7 +398,7 @@ class _MlpFn(torch.autograd.Function):
             raise ops.CnerfError("the network's weights were updated twice between this bf16x3 forward pass and its backward "
                                  "(the bf16-plane copy it used has been re-packed)")
         if ctx.igrad:
-            return _MlpFn._input_grads(ctx, g_raw)
+            return _MlpFn._input_grads(ctx, g_raw) if pair is None else _MlpFn._rows_pair_backward(ctx, g_raw)
         # Parameters owned by FusedAdam carry their .grad as a view into the flat gradient buffer: under loss.backward()
         # the wgrad reduction accumulates straight into it (what AccumulateGrad would do with ~50 add/copy launches per
         # step) and autograd gets no per-tensor gradients back.  Anything else — plain nn.Parameters, and
@@ -396,12 +428,49 @@ class _MlpFn(torch.autograd.Function):
         return nret if direct else (None,) * 10 + tuple(grads)
 
     @staticmethod
+    def _rows_pair_backward(ctx, g_raw):
+        """The backward of a level that _link_levels paired although its ray rows take a gradient (_rows_level).  The fine node parks
+        under the conditions of the plain pair (both levels on the direct route, the coarse node certain to run in this pass) and
+        hands no row gradient back; the coarse node then launches both levels (_run_pair_rows) and returns the row gradient of both.
+        Anything else (the tensor route, torch.autograd.grad, a coarse node that does not run): each level alone, as unpaired."""
+        params, pair = ctx.params, ctx.pair
+        if pair.fine() is ctx:
+            c = pair.coarse()
+            if (pair.parked is None and _direct_ok(ctx.needs_input_grad[10:], params) and _engine_accumulates(params[0])
+                    and c is not None and c.stash is not None and _direct_ok(c.needs_input_grad[10:], c.params) and _ENGINE_QUERY(c)
+                    and _engine_accumulates(c.params[0])):
+                pair.parked = _LevelJob(ctx, g_raw)
+                ctx.stash = ctx.packed = ctx.params = ctx.model = ctx.z = None
+                return (None,) * (10 + len(params))
+            return _MlpFn._input_grads(ctx, g_raw)
+        parked, pair.parked = pair.parked, None
+        if parked is None:
+            return _MlpFn._input_grads(ctx, g_raw)
+        if _direct_ok(ctx.needs_input_grad[10:], params) and _engine_accumulates(params[0]):
+            g_rays = _run_pair_rows(parked, _LevelJob(ctx, g_raw))
+            ctx.stash = ctx.packed = ctx.params = ctx.model = ctx.z = None
+            return (None,) * 4 + (g_rays,) + (None,) * (5 + len(params))
+        # (cannot happen — the fine node checked this node's route — but never drop a gradient: the parked level alone, on the direct
+        # route it chose, and its row gradient added to this level's)
+        g_fine = _MlpFn._level_input_grads(parked)[1]
+        own = list(_MlpFn._input_grads(ctx, g_raw))
+        own[4] = own[4] + g_fine
+        return tuple(own)
+
+    @staticmethod
     def _input_grads(ctx, g_raw):
-        """The backward of a level whose sample positions / ray rows / view directions take a gradient: this level alone (never
-        parked or paired), the full backward when parameters take gradients too and the dgrad alone when they do not, then
-        cnerf_mlp_input_grad on the workspace the dgrad wrote and the per-ray sums."""
-        params, needs = ctx.params, ctx.needs_input_grad
-        job = _LevelJob(ctx, g_raw)
+        """The backward of a level whose sample positions / ray rows / view directions take a gradient, this level alone."""
+        g_pts, g_rays, g_dirs, grads = _MlpFn._level_input_grads(_LevelJob(ctx, g_raw))
+        n = len(ctx.params)
+        ctx.stash = ctx.packed = ctx.params = ctx.model = ctx.z = None
+        return (None, None, None, g_pts, g_rays, None, g_dirs, None, None, None) + (tuple(grads) if grads is not None else (None,) * n)
+
+    @staticmethod
+    def _level_input_grads(job):
+        """One level whose inputs take a gradient -> (g_pts, g_rays, g_dirs, the parameter gradients for autograd | None): the full
+        backward when parameters take gradients too and the dgrad alone when they do not, then cnerf_mlp_input_grad on the workspace
+        the dgrad wrote and the per-ray sums."""
+        params, needs = job.params, job.needs
         ws = ops.mlp_bwd_workspace(job.spec, job.B, job.S, job.packed.device)
         grads, direct = None, False
         if any(needs[10:]):
@@ -413,18 +482,16 @@ class _MlpFn(torch.autograd.Function):
             ops.mlp_dgrad(job.spec, job.packed, job.d_raw, job.B, job.S, job.stash, ws, packed_bf=job.packed_bf)
         need_pts, need_rays, _, need_dirs = needs[3:7]
         vd = bool(job.spec.use_viewdirs)
-        dirs_in_rows = vd and not ctx.dirs_given          # the view directions are the last three columns of the ray rows (R:350)
+        dirs_in_rows = vd and not job.dirs_given          # the view directions are the last three columns of the ray rows (R:350)
         d_pts, d_dirs_pt = ops.mlp_input_grad(job.spec, job.packed, job.B, job.S, job.stash, ws,
                                               want_dirs=vd and (need_dirs or (need_rays and dirs_in_rows)))
         g_pts = d_pts if need_pts else None
         g_rays = g_dirs = None
         if need_rays:
-            g_rays = ops.rays_input_grad(d_pts, d_dirs_pt if dirs_in_rows else None, ctx.z, job.B, job.S, ray_stride=ctx.ray_stride)
+            g_rays = ops.rays_input_grad(d_pts, d_dirs_pt if dirs_in_rows else None, job.z, job.B, job.S, ray_stride=job.ray_stride)
         if need_dirs and vd:
             g_dirs = ops.rays_input_grad(None, d_dirs_pt, None, job.B, job.S)
-        ctx.stash = ctx.packed = ctx.params = ctx.model = ctx.z = None
-        return (None, None, None, g_pts, g_rays, None, g_dirs, None, None, None) + (tuple(grads) if grads is not None and not direct
-                                                                                     else (None,) * len(params))
+        return g_pts, g_rays, g_dirs, (grads if grads is not None and not direct else None)
 
 
 class _CompositeFn(torch.autograd.Function):
@@ -472,6 +539,18 @@ def _needs_grad(*ts):
     return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in ts)
 
 
+def _norm_grad_levels(d_raw, raws, noises, rays):
+    """The gradient of a folded loss w.r.t. the ray rows, which raw2outputs reads through dists * |rays_d| only (R:283): it follows
+    from the d_raw the compositing-backward launches just produced, whatever the loss form.  Both levels: one launch that adds them
+    (cnerf_composite_norm_grad_pair); one level with a d_raw: the single kernel; none: no gradient."""
+    if d_raw[0] is not None and d_raw[1] is not None:
+        return ops.composite_norm_grad_pair(d_raw[0], raws[0], noises[0], d_raw[1], raws[1], noises[1], rays)
+    for lv in (0, 1):
+        if d_raw[lv] is not None:
+            return ops.composite_norm_grad(d_raw[lv], raws[lv], noises[lv], rays)
+    return None
+
+
 class _RenderLossFn(torch.autograd.Function):
     """raw2outputs of the LAST level (R:265-308) with the photometric loss of the training loop folded in (R:769-775):
     loss = img2mse(rgb_map, target) [+ img2mse(rgb0, target)] as ONE autograd node from (raw, raw_coarse) to the scalar.  Forward:
@@ -482,8 +561,8 @@ class _RenderLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw, raw_c, z, z_c, rays, noise, noise_c, white, target, rgb_c, loss_c):
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3] or ctx.needs_input_grad[4] or ctx.needs_input_grad[8]:
-            raise ops.CnerfError("render_loss: gradients w.r.t. z_vals / rays / target are not implemented (only w.r.t. raw)")
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3] or ctx.needs_input_grad[8]:
+            raise ops.CnerfError("render_loss: gradients w.r.t. z_vals / target are not implemented (only w.r.t. raw and the ray rows)")
         rgb, disp, acc, weights, depth, loss = ops.composite_forward_mse(raw, z, rays, noise, white, target, loss_add=loss_c)
         ctx.save_for_backward(raw, raw_c, z, z_c, rays, target, rgb, rgb_c)
         ctx.noise, ctx.noise_c, ctx.white = noise, noise_c, white
@@ -499,7 +578,8 @@ class _RenderLossFn(torch.autograd.Function):
             for lv, (r, zv, nz, c) in enumerate(((raw, z, ctx.noise, rgb), (raw_c, z_c, ctx.noise_c, rgb_c))):      # fine, then coarse
                 if r is not None and ctx.needs_input_grad[lv]:
                     d_raw[lv] = ops.composite_backward_mse(r, zv, rays, nz, ctx.white, c, target, g_loss)
-        return tuple(d_raw) + (None,) * 9
+        g_rays = _norm_grad_levels(d_raw, (raw, raw_c), (ctx.noise, ctx.noise_c), rays) if ctx.needs_input_grad[4] else None
+        return tuple(d_raw) + (None, None, g_rays) + (None,) * 6
 
 
 class _RenderClossFn(torch.autograd.Function):
@@ -518,8 +598,8 @@ class _RenderClossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw, raw_c, z, z_c, rays, noise, noise_c, white, L, rgb_c, depth_c, ws_c, *temps):
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
-            raise ops.CnerfError("render_loss: gradients w.r.t. z_vals / rays are not implemented (only w.r.t. raw)")
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            raise ops.CnerfError("render_loss: gradients w.r.t. z_vals are not implemented (only w.r.t. raw and the ray rows)")
         rgb, disp, acc, weights, depth, ws = ops.composite_forward_closs(raw, z, rays, noise, white, L)
         want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or (L.forms and any(ctx.needs_input_grad[12:]))
         ctx.n_temps = len(temps)
@@ -565,7 +645,8 @@ class _RenderClossFn(torch.autograd.Function):
                         g_temp[2 * lv:2 * lv + 2] = d_temp[2 * lv:2 * lv + 2] * g_loss
                 g_temps = tuple(g_temp[k].reshape(ctx.temp_shapes[k]) if ctx.needs_input_grad[12 + k] else None
                                 for k in range(ctx.n_temps))
-        return tuple(d_raw) + (None,) * 10 + g_temps
+        g_rays = _norm_grad_levels(d_raw, (raw, raw_c), (ctx.noise, ctx.noise_c), rays) if ctx.needs_input_grad[4] else None
+        return tuple(d_raw) + (None, None, g_rays) + (None,) * 7 + g_temps
 
 
 _ONES = {}
@@ -724,18 +805,43 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     return {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in all_ret.items()}
 
 
-def render_loss(H, W, K, target_s, chunk=1024 * 32, rays=None, **kwargs):
+def _rows_kwargs(rows, rays, kwargs, who="render_loss"):
+    """render_loss(rows=...): the checked call -> the kwargs render() takes instead, with the rows as `_rows` (_render renders them
+    as they are) and without ndc / near / far, which are baked into the rows."""
+    if rays is not None or kwargs.get('c2w') is not None:
+        raise ops.CnerfError(f"{who}: rows= is mutually exclusive with rays= and c2w= (the rows ARE the finished ray batch)")
+    if not torch.is_tensor(rows) or rows.dim() != 2 or rows.shape[1] not in (8, 11):
+        raise ops.CnerfError(f"{who}: rows must be a [B, 8 | 11] tensor in batchify_rays' row format (pose.camera_rows)")
+    vd = bool(kwargs.get('use_viewdirs', False))
+    if rows.shape[1] != (11 if vd else 8):
+        raise ops.CnerfError(f"{who}: rows of width {rows.shape[1]} with use_viewdirs={vd}: the rows carry the view directions in "
+                             "three more columns (width 11) exactly when the networks read them")
+    kw = {k: v for k, v in kwargs.items() if k not in ('ndc', 'near', 'far', 'c2w')}
+    kw['_rows'] = rows
+    return kw
+
+
+def render_loss(H, W, K, target_s, chunk=1024 * 32, rays=None, rows=None, **kwargs):
     """R:764-775 as one call — `rgb, disp, acc, extras = render(H, W, K, chunk=, rays=batch_rays, retraw=True, **render_kwargs_train);
     img_loss = img2mse(rgb, target_s); loss = img_loss (+ img2mse(extras['rgb0'], target_s))` — with the loss folded into the
     compositing launches (_RenderLossFn).  -> (loss, rgb, disp, acc, extras); the same values and, after loss.backward() (or
     run_nerf.backward(loss): no seed fill), the same parameter gradients bit for bit as the lines above, from 6 launches fewer.
-    The maps are detached.  Batches larger than `chunk`, or an empty one, take the lines above literally."""
+    The maps are detached.  Batches larger than `chunk`, or an empty one, take the lines above literally.
+    rows= [B, 8 | 11] (instead of rays= / c2w=): the finished ray batch in batchify_rays' row format, normally pose.camera_rows(...)
+    of learnable cameras; the width agrees with use_viewdirs.  `ndc` / `near` / `far` of the kwargs are already baked into the rows
+    and are dropped.  Rows that require grad take their gradient on the same folded route: the two compositing-backward launches, one
+    cnerf_composite_norm_grad_pair, the paired MLP backward, cnerf_mlp_input_grad_pair and cnerf_rays_input_grad_pair; parameter
+    gradients do not depend on whether the rows require grad.  Batches beyond one chunk, empty ones and a target that is not on the
+    device: batchify_rays(rows) + the lines above.  Not covered: all-reducing camera gradients across ranks, hipGraph capture of
+    the pose step."""
+    if rows is not None:
+        kwargs = _rows_kwargs(rows, rays, kwargs)
     if rays is not None and _needs_grad(rays[0], rays[1]):
-        raise ops.CnerfError("render_loss: gradients w.r.t. rays are not implemented on the folded-loss route (the loss leaves the "
-                             "compositing launches); use render(rays=...) + img2mse")
-    n = rays[0].reshape(-1, 3).shape[0] if rays is not None else 0
+        raise ops.CnerfError("render_loss: gradients w.r.t. rays=(rays_o, rays_d) are not implemented on the folded-loss route; pass "
+                             "the finished rows instead, render_loss(rows=pose.camera_rows(...)), or use render(rays=...) + img2mse")
+    n = rows.shape[0] if rows is not None else rays[0].reshape(-1, 3).shape[0] if rays is not None else 0
     tgt = target_s.reshape(-1, 3) if torch.is_tensor(target_s) else None
-    if (rays is None or n == 0 or n > min(chunk, ops.composite_mse_max_rays()) or tgt is None or not tgt.is_cuda or tgt.dtype != torch.float32 or tgt.shape[0] != n
+    if ((rays is None and rows is None) or n == 0 or n > min(chunk, ops.composite_mse_max_rays()) or tgt is None or not tgt.is_cuda or tgt.dtype != torch.float32 or tgt.shape[0] != n
             or kwargs.get('c2w') is not None):
         rgb, disp, acc, extras = render(H, W, K, chunk=chunk, rays=rays, **kwargs)
         loss = img2mse(rgb, target_s)
@@ -892,6 +998,12 @@ def _render_camera(H, W, K, chunk, c2w, ndc, near, far, use_viewdirs, with_depth
 def _render(H, W, K, chunk, rays, c2w, ndc, near, far, use_viewdirs, c2w_staticcam, with_depth, kwargs):
     net = kwargs.get("network_fn")
     device = next(net.parameters()).device if net is not None else _default_device()
+    rows = kwargs.get("_rows")
+    if rows is not None:       # render_loss(rows=...): the finished [B, 8 | 11] batch, rendered as it is (_rows_kwargs checked it)
+        kwargs = {k: v for k, v in kwargs.items() if k != "_rows"}
+        if rows.device != device or rows.dtype != torch.float32:
+            rows = rows.to(device=device, dtype=torch.float32)
+        return _render_batch(rows, (rows.shape[0],), chunk, with_depth, kwargs)
     if _needs_grad(c2w):
         raise ops.CnerfError("render(c2w=...) with c2w requiring grad: gradients w.r.t. a camera pose are not implemented — build "
                              "the rays from the pose with get_rays and pass render(rays=(rays_o, rays_d), ndc=False), or, with "
@@ -907,6 +1019,11 @@ def _render(H, W, K, chunk, rays, c2w, ndc, near, far, use_viewdirs, c2w_staticc
         k_extract = ['rgb_map', 'disp_map', 'acc_map'] + (['depth_map'] if with_depth else [])
         return [all_ret[k] for k in k_extract] + [{k: all_ret[k] for k in all_ret if k not in k_extract}]
     batch, sh = _ray_batch(H, W, K, rays, c2w, ndc, near, far, use_viewdirs, c2w_staticcam, device)
+    return _render_batch(batch, sh, chunk, with_depth, kwargs)
+
+
+def _render_batch(batch, sh, chunk, with_depth, kwargs):
+    """batchify_rays over the [B, 8 | 11] rows and render()'s result structure (R:127-137)."""
     all_ret = batchify_rays(batch, chunk, _with_depth=with_depth, **kwargs)
     for k in all_ret:
         if k not in ('loss', 'loss_terms'):          # (the scalars of render_loss pass through)
@@ -1138,9 +1255,9 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     valid dummy rays whose loss weight is 0): the MLP training kernels stop at the count, which never visits the host."""
     rays = ray_batch if ray_batch.is_contiguous() else ray_batch.contiguous()
     N_rays, dev = rays.shape[0], rays.device
-    if _needs_grad(rays) and (_target is not None or _live is not None):
-        raise ops.CnerfError("render_rays: gradients w.r.t. rays are not implemented on the folded-loss routes (render_loss, "
-                             "ss_step_loss) or for a `live` batch; use render(rays=...) and form the loss from its maps")
+    if _needs_grad(rays) and _live is not None:
+        raise ops.CnerfError("render_rays: gradients w.r.t. rays are not implemented for a `live` batch (ss_step_loss); use "
+                             "render_loss(rows=...) or render(rays=...) and form the loss from its maps")
     two = N_importance > 0
     if N_rays == 0:   # nothing to launch (the reference's batchify_rays raises on an empty batch; here: empty maps)
         last = network_fn if (network_fine is None or not two) else network_fine

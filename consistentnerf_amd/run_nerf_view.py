@@ -507,7 +507,7 @@ def _render_loss_lines(H, W, K, target_s, mask, depth_prior, chunk, rays, coef, 
 def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32, rays=None, hardmask_coef=0.2, depth_far=None,
                 rgb_w=1.0, depth_w=1.0, mono=None, patch_num=4, patch_size=16, patch_w=0.001, counts=None, ssim_w=0.0, _ss_coins=None,
                 rgb_form="hardmask", depth_form="hardmask", lp_coef=0.0, temp_rgb=None, temp_depth=None, lpips_w=0.0, lpips_fn=None,
-                **kwargs):
+                rows=None, **kwargs):
     """The loss of one run_nerf_view.train() step as ONE call (V:1636-1865 with the terms this package builds):
 
         rgb, disp, acc, depth_pred, extras = render(H, W, K, chunk=, rays=batch_rays, retraw=True, **render_kwargs_train)
@@ -558,7 +558,13 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
     bit equal to their lines; softlp / softmask to rounding (powf / expf against ATen's pow / exp).  counts with "norm" / "plain":
     the mean's denominator becomes counts[0] + counts[1]; with "hardmask_coef": (n1, n0) as for the colour term; with a softlp /
     softmask form: refused (their normaliser is a global sum of weights, which nothing all-reduces), as is _ss_coins with any
-    form."""
+    form.
+
+    rows= [B, 8 | 11] (instead of rays= / c2w=): the finished ray batch in batchify_rays' row format, normally
+    pose.camera_rows(...) of learnable cameras (width 11 exactly with use_viewdirs).  `ndc` / `near` / `far` of the kwargs are
+    already baked into the rows and are dropped (`far` is still the default of depth_far).  Rows that require grad take their
+    gradient on the folded route, as in run_nerf.render_loss, with every loss form; the lines route takes them too.  Not covered:
+    all-reducing camera gradients across ranks, hipGraph capture of the pose step, _ss_coins."""
     if rgb_form not in RGB_FORMS or depth_form not in DEPTH_FORMS:
         raise ValueError(f"render_loss: unknown loss form rgb_form={rgb_form!r} / depth_form={depth_form!r}: rgb_form is one of "
                          f"{RGB_FORMS}, depth_form one of {DEPTH_FORMS}")
@@ -585,11 +591,15 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
     if lpips_w == 0:
         lpips_fn = None
     far = float(kwargs.get('far', 1.)) if depth_far is None else float(depth_far)
-    n = rays[0].reshape(-1, 3).shape[0] if rays is not None else 0
+    if rows is not None:
+        if _ss_coins is not None:
+            raise ops.CnerfError("render_loss: rows= is not part of the in-loop consistency step (_ss_coins)")
+        kwargs = _R._rows_kwargs(rows, rays, kwargs)
+    n = rows.shape[0] if rows is not None else rays[0].reshape(-1, 3).shape[0] if rays is not None else 0
     P = int(patch_num) if mono is not None else 0
     ps2 = int(patch_size) * int(patch_size)
     tgt = target_s.reshape(-1, 3) if torch.is_tensor(target_s) else None
-    ok = (rays is not None and 0 < n <= chunk and tgt is not None and tgt.is_cuda and tgt.dtype == torch.float32 and tgt.shape[0] == n
+    ok = ((rays is not None or rows is not None) and 0 < n <= chunk and tgt is not None and tgt.is_cuda and tgt.dtype == torch.float32 and tgt.shape[0] == n
           and kwargs.get('c2w') is None and P <= 8 and P * ps2 <= n and not torch.is_tensor(kwargs.get('near'))
           and not torch.is_tensor(kwargs.get('far')))
     ok = ok and all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in temps)
@@ -602,6 +612,10 @@ def render_loss(H, W, K, target_s, mask=None, depth_prior=None, chunk=1024 * 32,
     if lP > 0:      # the folded LPIPS term: the HIP network on this device, the default forms (else the lines, never without the term)
         from .lpips import LPIPS
         ok = ok and isinstance(lpips_fn, LPIPS) and not forms and 0 < lP <= 8 and lP * ops.PATCH_SSIM_RAYS <= n
+    if ok and (_ss_coins is None or mask is not None) and rays is not None and _R._needs_grad(rays[0], rays[1]):
+        raise ops.CnerfError("render_loss: gradients w.r.t. rays=(rays_o, rays_d) are not implemented on the folded-loss route; pass "
+                             "the finished rows instead, render_loss(rows=pose.camera_rows(...)), or use render(rays=...) and form "
+                             "the loss from its maps")
     if _ss_coins is not None:       # the in-loop consistency step's primary terms (ss_step_loss): VT:941-969 on render()'s maps
         if not ok or mask is None:
             rgb, disp, acc, depth, extras = render(H, W, K, chunk=chunk, rays=rays, **kwargs)

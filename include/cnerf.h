@@ -41,6 +41,8 @@ extern "C" {
                                 * 6: + NDC and intrinsics gradients: cnerf_camera_rows / cnerf_camera_rows_bwd (+ cnerf_camera_rows_bwd_ws_floats), the
                                 * finished ray rows of chosen pixels from poses and K in device memory and their backward w.r.t. both, and
                                 * cnerf_ndc_rays_bwd; append-only.
+                                * 6: + camera gradients on the folded training step: cnerf_mlp_input_grad_pair, cnerf_rays_input_grad_pair,
+                                * cnerf_composite_norm_grad_pair (two levels of one ray batch in one grid each); append-only.
                                 * 6: + the in-loop consistency step as ONE render whose row count lives on the device: cnerf_ss_batch (the combined
                                 * batch + its live-row count), cnerf_mlp_fwd_live / cnerf_mlp_bwd_live / cnerf_mlp_bwd_pair_live (launches of a fixed
                                 * capacity that stop at a device-side count), cnerf_closs_finish_ss2 (the two-segment loss tail); cnerf_closs gains
@@ -864,6 +866,27 @@ int cnerf_camera_rows_bwd(int H, int W, float fx, float fy, float cx, float cy, 
  * the pre-NDC (rays_o, rays_d) [B, 3] -> (d_rays_o, d_rays_d) [B, 3], one thread per ray, through the same device function. */
 int cnerf_ndc_rays_bwd(const float* g_o, const float* g_d, const float* rays_o, const float* rays_d, int64_t B, float ndc_ax, float ndc_ay,
                        float* d_rays_o, float* d_rays_d, void* stream);
+
+/* ---- camera gradients on the folded training step: the input-gradient launches for BOTH levels of one ray batch in one grid each -- */
+/* cnerf_mlp_input_grad for two levels in one grid, behind cnerf_mlp_dgrad_pair / cnerf_mlp_dgrad_bf_pair on the two workspaces that
+ * launch wrote: ceil(B0 S0 / 32) + ceil(B1 S1 / 32) waves, the block index picks the level; per tile the arithmetic of the single
+ * call.  Each level has its own network geometry, sample count and ragged last tile.  d_dirs_pt0 / d_dirs_pt1 nullable (CNERF_E_ARG
+ * when given for a network without view directions). */
+int cnerf_mlp_input_grad_pair(const cnerf_net* net0, const float* packed0, int64_t B0, int S0, const float* stash0,
+                              const float* workspace0, float* d_pts0, float* d_dirs_pt0, const cnerf_net* net1, const float* packed1,
+                              int64_t B1, int S1, const float* stash1, const float* workspace1, float* d_pts1, float* d_dirs_pt1,
+                              void* stream);
+/* cnerf_rays_input_grad of two levels of one batch of B rays, added: every column of d_rays [B, ray_stride >= 8] is written —
+ * 0:3 = sum_s d_pts0 + sum_s d_pts1, 3:6 = sum_s z0 d_pts0 + sum_s z1 d_pts1, zeros behind, and with d_dirs_pt0 / d_dirs_pt1 (both or
+ * neither; ray_stride >= 11) the last three columns = their per-ray sums.  Each level's sum in the single call's order, rounded to
+ * fp32, then level 0 + level 1: equal to the sum of two single calls bit for bit. */
+int cnerf_rays_input_grad_pair(const float* d_pts0, const float* d_dirs_pt0, const float* z0, int S0, const float* d_pts1,
+                               const float* d_dirs_pt1, const float* z1, int S1, int64_t B, float* d_rays, int ray_stride, void* stream);
+/* cnerf_composite_norm_grad of two levels that read the same ray rows, added: every column of d_rays [B, ray_stride >= 8] is
+ * written, 3:6 = the level 0 term + the level 1 term (each formed and rounded as in the single call), all others zero. */
+int cnerf_composite_norm_grad_pair(const float* d_raw0, const float* raw0, int raw_ch0, const float* noise0, int S0, const float* d_raw1,
+                                   const float* raw1, int raw_ch1, const float* noise1, int S1, const float* rays, int ray_stride,
+                                   int64_t B, float* d_rays, void* stream);
 
 #ifdef __cplusplus
 }
