@@ -124,8 +124,9 @@ __global__ __launch_bounds__(64) void gen_rays_at_reduce_k(const double* __restr
 //                                                    5.8e-9 t2^5
 // The truncation error must stay below eps / 2 = 3.0e-8: 5.8e-9 t2^5 <= 3.0e-8 holds up to t2 = 1.39 (theta = 1.18).  The threshold
 // is t2 = 1: there the series is off by 0.1 eps (C) and 0.003 eps (A) before its own Horner roundings (about 1 eps), and from there
-// up the closed form of C stays within 5 eps.  At w = 0 exactly the series give A = 1, Bc = 1/2, C = -1/3, D = -1/12: the value is
-// the identity and the gradient the three generators applied to R0.
+// up the closed form of C stays within 5 eps.  At w = 0 exactly the series give A = 1, Bc = 1/2, C = -1/3, D = -1/12: the gradient
+// is the three generators applied to R0.  These fp32 coefficients are the BACKWARD's; the forward (pose_compose_k) evaluates A and Bc
+// in closed form in fp64 and copies R0 at w = 0.
 constexpr float POSE_SERIES_T2 = 1.0f;
 
 __device__ __forceinline__ float pose_A(float t2) {
@@ -148,7 +149,6 @@ __global__ void pose_compose_k(const float* __restrict__ c2w0, const float* __re
   const float* P = c2w0 + (int64_t)n * 12;
   float* out = c2w + (int64_t)n * 12;
   const float x = rot[3 * n], y = rot[3 * n + 1], z = rot[3 * n + 2];
-  const float t2 = x * x + y * y + z * z;
 #pragma unroll
   for (int r = 0; r < 3; ++r) out[4 * r + 3] = P[4 * r + 3] + trans[3 * n + r];
   if (x == 0.f && y == 0.f && z == 0.f) {      // Exp(0) = I: R0's own bits (a product with 0 would turn a -0 of R0 into +0)
@@ -156,15 +156,23 @@ __global__ void pose_compose_k(const float* __restrict__ c2w0, const float* __re
     for (int r = 0; r < 3; ++r) { out[4 * r] = P[4 * r]; out[4 * r + 1] = P[4 * r + 1]; out[4 * r + 2] = P[4 * r + 2]; }
     return;
   }
-  const float A = pose_A(t2), Ah = pose_A(0.25f * t2), Bc = 0.5f * Ah * Ah;
+  // The value is formed in fp64 at the fp32 inputs and rounded to fp32 once (one thread per view: the cost is nothing).  In fp32,
+  // E's diagonal 1 - Bc (y^2 + z^2) carries Bc's relative error (five roundings through the half angle's square) times Bc t2, which
+  // is 2 at theta = pi: R R^T - I of the composed rotation reached 13 eps there (random axes; 12 eps at theta = 10) against 1.4 eps
+  // of the rounded R0 itself.  Rounded once, every element is within half an ulp and R R^T - I stays at R0's own plus 1.7 eps.
+  // theta = sqrt(t2) cannot underflow here: the smallest fp32 squares to 2e-90.
+  const double xd = x, yd = y, zd = z;
+  const double t2 = xd * xd + yd * yd + zd * zd, th = sqrt(t2), hh = 0.5 * th;
+  const double A = sin(th) / th, Ah = sin(hh) / hh, Bc = 0.5 * Ah * Ah;
   // E = I + A K + Bc (w w^T - t2 I)
-  const float E[9] = {1.f - Bc * (y * y + z * z), Bc * x * y - A * z,          Bc * x * z + A * y,
-                      Bc * x * y + A * z,          1.f - Bc * (x * x + z * z), Bc * y * z - A * x,
-                      Bc * x * z - A * y,          Bc * y * z + A * x,          1.f - Bc * (x * x + y * y)};
+  const double E[9] = {1.0 - Bc * (yd * yd + zd * zd), Bc * xd * yd - A * zd,           Bc * xd * zd + A * yd,
+                       Bc * xd * yd + A * zd,           1.0 - Bc * (xd * xd + zd * zd), Bc * yd * zd - A * xd,
+                       Bc * xd * zd - A * yd,           Bc * yd * zd + A * xd,           1.0 - Bc * (xd * xd + yd * yd)};
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
-    for (int k = 0; k < 3; ++k) out[4 * r + k] = E[3 * r] * P[k] + E[3 * r + 1] * P[4 + k] + E[3 * r + 2] * P[8 + k];
+    for (int k = 0; k < 3; ++k)
+      out[4 * r + k] = (float)(E[3 * r] * (double)P[k] + E[3 * r + 1] * (double)P[4 + k] + E[3 * r + 2] * (double)P[8 + k]);
 }
 
 __global__ void pose_compose_bwd_k(const float* __restrict__ c2w0, const float* __restrict__ rot, const float* __restrict__ d_c2w, int N,

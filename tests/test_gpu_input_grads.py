@@ -175,17 +175,17 @@ RB, RNC, RNF, NEAR, FAR = 37, 16, 16, 2.0, 6.0
 KCAM = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]     # (only the NDC warp reads the intrinsics)
 
 
-def _ray_inputs():
-    b = I.ray_batch(RB, seed=3)
+def _ray_inputs(B=RB):
+    b = I.ray_batch(B, seed=3)
     rs = np.random.RandomState(7)
-    o, d = b[:, 0:3].copy(), (b[:, 3:6] * rs.uniform(0.5, 2.0, size=(RB, 1))).astype(np.float32)     # |d| in [0.5, 2.6]
-    G = {k: rs.normal(size=(RB, 3) if k.startswith("rgb") else (RB,)).astype(np.float32)
+    o, d = b[:, 0:3].copy(), (b[:, 3:6] * rs.uniform(0.5, 2.0, size=(B, 1))).astype(np.float32)     # |d| in [0.5, 2.6]
+    G = {k: rs.normal(size=(B, 3) if k.startswith("rgb") else (B,)).astype(np.float32)
          for k in ("rgb_map", "depth_map", "acc_map", "rgb0", "depth0")}
     return o, d, G
 
 
-def _ray_models(vd, dev):
-    D, W = (8, 128) if vd else (4, 128)      # (with a skip layer / without)
+def _ray_models(vd, dev, arch=None):
+    D, W = arch or ((8, 128) if vd else (4, 128))      # (with a skip layer / without)
     (coarse, sdc), (fine, sdf) = make_model(D, W, vd, 5, 21, dev), make_model(D, W, vd, 5, 22, dev)
     return D, W, coarse, fine, sdc, sdf
 
@@ -194,14 +194,14 @@ def _loss(maps, G, conv):
     return sum((maps[k] * conv(G[k])).sum() for k in G)
 
 
-def _run_rays(dev, vd, white, chunk):
+def _run_rays(dev, vd, white, chunk, B=RB, Nc=RNC, Nf=RNF, arch=None):
     """render(rays=(o, d)) with both requiring grad + backward of the mixed loss -> (d_rays_o, d_rays_d)."""
     from consistentnerf_amd import run_nerf_view as V
-    D, W, coarse, fine, _, _ = _ray_models(vd, dev)
-    o, d, G = _ray_inputs()
+    D, W, coarse, fine, _, _ = _ray_models(vd, dev, arch)
+    o, d, G = _ray_inputs(B)
     to, td = T(o, dev).requires_grad_(True), T(d, dev).requires_grad_(True)
     rgb, disp, acc, depth, extras = V.render(1, 1, KCAM, chunk=chunk, rays=(to, td), ndc=False, near=NEAR, far=FAR, use_viewdirs=vd,
-                                             **_kwargs(coarse, fine, RNC, RNF, 0.0, white, 0.0, False))
+                                             **_kwargs(coarse, fine, Nc, Nf, 0.0, white, 0.0, False))
     maps = dict(extras, rgb_map=rgb, depth_map=depth, acc_map=acc)
     _loss(maps, G, lambda g: T(g, dev)).backward()
     return to.grad, td.grad
@@ -210,29 +210,29 @@ def _run_rays(dev, vd, white, chunk):
 _RAYS_REF = {}
 
 
-def _rays_reference(dev, vd, white):
+def _rays_reference(dev, vd, white, B=RB, Nc=RNC, Nf=RNF, arch=None):
     """(float64 oracle gradients, float32 oracle gradients) of the rays form, on the kernel's masks and fine depths; once per case."""
-    key = (vd, white)
+    key = (vd, white, B, Nc, Nf, arch)
     if key in _RAYS_REF:
         return _RAYS_REF[key]
     from consistentnerf_amd import ops, run_nerf_view as V
-    D, W, coarse, fine, sdc, sdf = _ray_models(vd, dev)
-    o, d, G = _ray_inputs()
+    D, W, coarse, fine, sdc, sdf = _ray_models(vd, dev, arch)
+    o, d, G = _ray_inputs(B)
     # the kernel's own forward on the packed rows: ReLU patterns of both levels and the fine sample depths
     batch = ops.pack_rays(T(o, dev), T(d, dev), NEAR, FAR, vd, False)
-    ret = V.render_rays(batch, retraw=True, _debug=True, **_kwargs(coarse, fine, RNC, RNF, 0.0, white, 0.0, False))
-    masks_c = relu_masks(ret["_raw_coarse"].grad_fn.stash, RB * RNC, D, W, vd)
-    masks_f = relu_masks(ret["raw"].grad_fn.stash, RB * (RNC + RNF), D, W, vd)
+    ret = V.render_rays(batch, retraw=True, _debug=True, **_kwargs(coarse, fine, Nc, Nf, 0.0, white, 0.0, False))
+    masks_c = relu_masks(ret["_raw_coarse"].grad_fn.stash, B * Nc, D, W, vd)
+    masks_f = relu_masks(ret["raw"].grad_fn.stash, B * (Nc + Nf), D, W, vd)
     z_fine = ret["_z_vals"].detach().cpu()
 
     def run(dtype, flips):
         to, td = T(o).to(dtype).requires_grad_(True), T(d).to(dtype).requires_grad_(True)
-        cols = [to, td, torch.full((RB, 1), NEAR, dtype=dtype), torch.full((RB, 1), FAR, dtype=dtype)]
+        cols = [to, td, torch.full((B, 1), NEAR, dtype=dtype), torch.full((B, 1), FAR, dtype=dtype)]
         if vd:
             cols.append(td / torch.norm(td, dim=-1, keepdim=True))
         out = O.render_rays(torch.cat(cols, -1), {k: T(v).to(dtype) for k, v in sdc.items()}, {k: T(v).to(dtype) for k, v in sdf.items()},
-                            O.NetCfg(D, W, use_viewdirs=vd, output_ch=5), O.RenderCfg(RNC, RNF, 0.0, False, white, 0.0),
-                            u=torch.linspace(0.0, 1.0, RNF, dtype=dtype).expand(RB, RNF), z_fine=z_fine.to(dtype),
+                            O.NetCfg(D, W, use_viewdirs=vd, output_ch=5), O.RenderCfg(Nc, Nf, 0.0, False, white, 0.0),
+                            u=torch.linspace(0.0, 1.0, Nf, dtype=dtype).expand(B, Nf), z_fine=z_fine.to(dtype),
                             masks_coarse=masks_c, masks_fine=masks_f, flips=flips)
         _loss(out, G, lambda g: T(g).to(dtype)).backward()
         return to.grad.double(), td.grad.double()

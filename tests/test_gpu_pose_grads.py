@@ -170,7 +170,9 @@ def test_pose_compose_against_float64(dev, N, mag):
     fp32 (half an ulp per element), and an element of R^T R sums three such products.
     Measured on the MI355X (profiles/pose_gpu_tests.txt): rotation err 0 (rot = 0) .. 2.3e-7 (|rot| = 3), d_rot err 3.7e-8 .. 2.1e-7
     (float32 restatement 3.3e-8 .. 5.7e-7), d_trans exact; max|R^T R - I| 4.0e-8 .. 1.2e-7 up to |rot| = 1e-2, 2.2e-7 at 1 and 5.1e-7
-    (4.3 ulp) at 3, with R0's own 5.7e-8."""
+    (4.3 ulp) at 3, with R0's own 5.7e-8.  Since the forward forms the value in fp64 and rounds once (tests/test_gpu_grad_envelope.py
+    D found 13 u of R R^T - I near pi): rotation err 2.3e-8 .. 3.3e-8 at every non-zero angle, max|R^T R - I| 5.7e-8 .. 1.1e-7 (0.93 ulp);
+    d_rot as before."""
     from consistentnerf_amd import ops
     c2w0, rot, trans, G = _compose_inputs(N, mag)
     v64, r64, t64 = _compose_ref(c2w0, rot, trans, G, torch.float64)
